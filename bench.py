@@ -21,7 +21,9 @@ number of rows per step) and the per-b64 ME results (MeSbResults arrays + the pe
 all-gathered over RCCL once per step through libsvthip.so's own C entry (svt_hip_me_results_all_gather), on a side stream behind the ME
 launch so that it overlaps the prediction / RD kernels.
 `value` = luma pixels of the pictures fully processed per second, whole job (strong scaling: the pictures per step
-are fixed, each rank handles 1/N of the b64 rows), inputs resident in HBM.  `end_to_end` repeats the measurement with the
+are fixed, each rank handles 1/N of the b64 rows), inputs resident in HBM.  A plain run sets up, warms up, times the K steps, writes
+the last step's outputs when asked (--dump-outputs) and prints the line.  The per-kernel timings and rooflines, `end_to_end`, the other
+kernels' timings, the CPU baseline and the parity check run only with --full.  `end_to_end` repeats the measurement with the
 PCIe legs inside the step: 4 new input pictures uploaded (H2D, the 1/4 and 1/16 planes built on the device) and the gathered ME results
 copied back (D2H) per step, one step ahead / behind on the context's transfer stream.
 """
@@ -39,8 +41,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the end-to-end leg and the other kernels' timings")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-kernel timings and rooflines, the multi-GPU gather check, the end-to-end leg, the other kernels' "
+                         "timings, the CPU baseline and the parity check (a plain run does only the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the end-to-end leg and the other kernels' timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -640,6 +646,49 @@ def other_kernels(ctx, wl, ext):
     return out
 
 
+DUMP_BYTES = 60_000_000  # array bytes --dump-outputs writes in all: below 64 MB with the .npy headers
+
+
+def dump_outputs(path, wl, me_buf):
+    """What the last timed step left for a caller, as DIR/<name>.npy: the ME results of its pictures (`me_<field>`, one row per b64 of every
+    picture; `me_buf` holds all ranks' bands when world > 1), this rank's prediction and reconstruction planes (`pred`, `recon`, one row
+    per picture row) and the RD outputs of each depth (`rd<W>x<H>_<field>`, one row per job, `qcoeff` included).  8- and 16-bit values
+    are written as float32, 32- and 64-bit ones as float64 (every value the kernels write is below 2**53, so both are exact).  The arrays
+    share DUMP_BYTES, the smallest first; an array larger than its share keeps a sample of its rows, drawn from a generator seeded by its
+    name, so the same arguments select the same rows in every run and every build."""
+    import zlib
+    NP = len(PICS)
+    me = [wl.layout.unpack(me_buf, pi) for pi in range(NP)]
+    # (name, host array or device bytes, element dtype, rows, elements per row)
+    arrays = [(f"me_{n}", np.concatenate([m[n] for m in me]), dt, NP * wl.w64 * wl.h64, c) for n, dt, c in wl.layout.fields]
+    arrays += [(name, t.view(torch.uint8), np.dtype(np.uint16), NP * H, W) for name, t in (("pred", wl.pred), ("recon", wl.recon))]
+    for ts, _, _, outs, n, _ in wl.rd:
+        tag = f"rd{abi.TX_W[ts]}x{abi.TX_H[ts]}"
+        arrays += [(f"{tag}_{name}", outs[name], np.dtype(dt), n, k) for name, dt, k in abi.RD_OUT_FIELDS]
+        arrays.append((f"{tag}_qcoeff", outs["qcoeff"], np.dtype(np.int32), n, min(abi.TX_W[ts], 32) * min(abi.TX_H[ts], 32)))
+    out_size = lambda dt: 4 if dt.itemsize <= 2 else 8
+    arrays.sort(key=lambda e: e[3] * e[4] * out_size(e[2]))
+    os.makedirs(path, exist_ok=True)
+    left, sampled = DUMP_BYTES, []
+    for i, (name, a, dt, rows, per_row) in enumerate(arrays):
+        keep = min(rows, max(1, left // (len(arrays) - i) // (per_row * out_size(dt))))
+        idx = None
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(rows, keep, replace=False))
+            sampled.append(f"{name} {keep}/{rows}")
+        if isinstance(a, np.ndarray):
+            host = a if idx is None else a[idx]
+        else:
+            t = a[:rows * per_row * dt.itemsize].view(rows, per_row * dt.itemsize)
+            if idx is not None:
+                t = t[torch.from_numpy(idx).to(t.device)]
+            host = t.cpu().numpy().view(dt).reshape(len(t), per_row)
+        out = host.astype(np.float32 if out_size(dt) == 4 else np.float64)
+        np.save(os.path.join(path, name + ".npy"), out)
+        left -= out.nbytes
+    log(f"--dump-outputs: {len(arrays)} arrays, {(DUMP_BYTES - left) / 1e6:.1f} MB in {path}; row samples: {', '.join(sampled) or 'none'}")
+
+
 def main():
     a = parse_args()
     rank = int(os.environ.get("RANK", "0"))
@@ -697,30 +746,35 @@ def main():
     run(a.steps)
     barrier()
     dt = time.perf_counter() - t0
-    # kernel-level durations (HIP events on the launch stream), separate short pass so events do not perturb the timed loop
-    ev = {"me": [], "pred": [], "rd": [], **{f"rd{abi.TX_W[ts]}": [] for ts in RD_SIZES}}
-    run(max(N_SETS, min(a.steps, 6)), ev)
-    barrier()
-    # per kernel family: the median over the pass's launches (one disturbed launch -- a clock ramp, a neighbour on the PCIe switch -- would
-    # otherwise move a mean of six by a multiple)
-    kms = {k: float(np.median([s.elapsed_time(e) for s, e in v])) for k, v in ev.items()}
-    # the kernels of the ME launch one by one: the library brackets them with events of its own on the launch stream when asked to
-    # (svt_hip_context_set_me_timing; off in the timed loop)
-    chain = []
-    if wl.live:
-        ctx.set_me_timing(True)
-        for _ in range(max(N_SETS, 3)):
-            run(1)
-            chain.append(ctx.me_launch_times())
-        ctx.set_me_timing(False)
+    if a.dump_outputs and rank == 0:
+        k_last = (step_no[0] - 1) % 2
+        dump_outputs(a.dump_outputs, wl, (xch.out[k_last] if xch else wl.me_bufs[k_last]).cpu().numpy())
+    kms, chain_ms = {}, {}
+    if a.full:
+        # kernel-level durations (HIP events on the launch stream), separate short pass so events do not perturb the timed loop
+        ev = {"me": [], "pred": [], "rd": [], **{f"rd{abi.TX_W[ts]}": [] for ts in RD_SIZES}}
+        run(max(N_SETS, min(a.steps, 6)), ev)
         barrier()
-    chain_ms = {k: float(np.median([c.get(k, 0.0) for c in chain])) for k in (chain[0] if chain else {})}
+        # per kernel family: the median over the pass's launches (one disturbed launch -- a clock ramp, a neighbour on the PCIe switch -- would
+        # otherwise move a mean of six by a multiple)
+        kms = {k: float(np.median([s.elapsed_time(e) for s, e in v])) for k, v in ev.items()}
+        # the kernels of the ME launch one by one: the library brackets them with events of its own on the launch stream when asked to
+        # (svt_hip_context_set_me_timing; off in the timed loop)
+        chain = []
+        if wl.live:
+            ctx.set_me_timing(True)
+            for _ in range(max(N_SETS, 3)):
+                run(1)
+                chain.append(ctx.me_launch_times())
+            ctx.set_me_timing(False)
+            barrier()
+        chain_ms = {k: float(np.median([c.get(k, 0.0) for c in chain])) for k in (chain[0] if chain else {})}
     gather_check = None
-    if world > 1:
+    if a.full and world > 1:
         while (step_no[0] - 1) % N_SETS != 0:
             run(1)
         barrier()
-    if world > 1 and rank == 0:
+    if a.full and world > 1 and rank == 0:
         # outside the timed region, on the real RCCL path as in the rehearsal: the gathered buffers of all ranks, unpacked, must equal a
         # whole-picture run of this rank (two pictures with different band rotations)
         k = wl.last_k0
@@ -741,7 +795,7 @@ def main():
         rccl_ranks = int(n.value)
     # ---- end-to-end leg: the PCIe copies inside the step (4 new input pictures in, the gathered results out) ----
     e2e = None
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         NP = len(PICS)
         pool = {s: [wl.sets[s].pics[c] for c in CURS] for s in range(N_SETS)}
         pinned = []
@@ -800,11 +854,12 @@ def main():
                "d2h_bytes_per_step": int(host_out[0].numel()),
                "what": "the same step with 4 new padded 8-bit input planes uploaded from page-locked host memory (pyramid levels rebuilt on the device) and the gathered ME results copied back, per step; "
                        "the copies run one step ahead / behind on the context's transfer stream (svt_hip_pa_picture_update_ahead)"}
-    extras = other_kernels(ctx, wl, ext) if (not a.no_extras and world == 1 and rank == 0) else None
-    # leave the results of a step on picture set 0 behind for the parity leg (its ME results, prediction / reconstruction planes, RD outputs)
-    while (step_no[0] - 1) % N_SETS != 0:
-        run(1)
-    barrier()
+    extras = other_kernels(ctx, wl, ext) if (a.full and not a.no_extras and world == 1 and rank == 0) else None
+    if a.full:
+        # leave the results of a step on picture set 0 behind for the parity leg (its ME results, prediction / reconstruction planes, RD outputs)
+        while (step_no[0] - 1) % N_SETS != 0:
+            run(1)
+        barrier()
     t_all = torch.tensor([dt], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t_all, op=dist.ReduceOp.MAX)
@@ -812,24 +867,6 @@ def main():
     pictures = a.steps * len(PICS)
     value = pictures * W * H / dt / 1e6
     if rank == 0:
-        frac_rows = wl.rows_per_step / (wl.h64 * len(PICS))
-        me_bytes = (1.3125 * (1 + R) + 0.166 * R) * W * H * frac_rows * len(PICS)  # B_ME bytes per pixel x the pictures of one launch
-        dom = "me" if kms["me"] >= max(kms[f"rd{abi.TX_W[ts]}"] for ts in RD_SIZES) else "rd"  # the single kernel with the longest launch
-        # HBM bytes per launch from the PMC passes committed under profiles/ (same command, N = 1): rocprofv3 cannot run
-        # inside this process, so the figure is the recorded one; null when it does not describe this run
-        traffic, traffic_src = None, None
-        tf = os.path.join(ROOT, "profiles", "r03_hbm_traffic.json")
-        if world == 1 and os.path.exists(tf):
-            traffic = json.load(open(tf))["kernels"].get("me_launch", {}).get("hbm_bytes_per_launch")
-            traffic_src = "profiles/r03_hbm_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; the kernels of the ME launch summed)"
-        ach = me_bytes / (kms["me"] * 1e-3) / 1e9
-        rd_roof = {}
-        for ts, descs, _, _, n, _ in wl.rd:
-            px, npk = n * abi.TX_W[ts] * abi.TX_H[ts], min(abi.TX_W[ts], 32) * min(abi.TX_H[ts], 32)
-            by = px * 6 + n * npk * 4
-            ms = kms[f"rd{abi.TX_W[ts]}"]
-            rd_roof[f"rd_tx_kernel<{abi.TX_W[ts]}x{abi.TX_H[ts]}, 10>"] = {"avg_launch_ms": round(ms, 4), "algorithmic_bytes_per_launch": int(by), "achieved": round(by / ms / 1e6, 1),
-                                                                      "frac": round(by / ms / 1e6 / HBM_PEAK_GBS, 4)}
         out = {
             "metric": "ME+RD-cost Mpixels/s (2160p10 preset-6)", "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True,
@@ -839,22 +876,43 @@ def main():
                                    f"{N_SETS} picture sets alternate from step to step",
                        "pictures_per_step": len(PICS), "b64_rows_per_rank_per_step": wl.rows_per_step,
                        "parallelism": f"b64-row bands x{world} (left-over rows rotating over the ranks) + all-gather of ME results" + (f" via {xch.kind}" if xch else "")},
-            "roofline": {"bound": "hbm", "kernel": "ME launch = " + " -> ".join(k.replace("svt_hip_me_", "").replace("_kernel", "") for k in chain_ms) + " (svt_hip_me_*_kernel, one stream)",
-                         "kernel_chain_ms": {k: round(v, 4) for k, v in chain_ms.items()}, "achieved": round(ach, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": int(me_bytes), "avg_launch_ms": round(kms["me"], 4),
-                         "note": "the ME of a step is ONE launch of the C entry = a chain of kernels on one stream (dense pre-pass, then the per-block pipeline staged at its searches); "
-                                 "avg_launch_ms brackets the chain (HIP events on the launch stream), kernel_chain_ms each kernel (events the library records between them in a "
-                                 "separate pass; profiles/r03_kernel_stats_bench.csv has rocprofv3's averages of the same kernels).  By the task's rule the bound is HBM; the search "
-                                 "is issue-bound (SURVEY 8d): see valu_sad below", "longest_kernel": dom},
-            "rd_roofline": rd_roof,
-            # the longest SINGLE kernel of the step, whatever launch it belongs to (the ME launch is a chain of kernels)
-            "dominant_single_kernel": max([{"name": k, "avg_launch_ms": v["avg_launch_ms"], "bound": "hbm", "achieved": v["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                            "frac": v["frac"], "algorithmic_bytes_per_launch": v["algorithmic_bytes_per_launch"]} for k, v in rd_roof.items()]
-                                          + [{"name": k, "avg_launch_ms": round(v, 4), "bound": "valu (v_qsad_pk_u16_u8 issue)", "note": "one kernel of the ME chain: see roofline / roofline.valu_sad for the launch"}
-                                             for k, v in chain_ms.items()], key=lambda e: e["avg_launch_ms"]) if (rd_roof or chain_ms) else None,
-            "kernel_ms": {k: round(v, 4) for k, v in kms.items()},
         }
+        frac_rows = wl.rows_per_step / (wl.h64 * len(PICS))
+        if a.full:
+            me_bytes = (1.3125 * (1 + R) + 0.166 * R) * W * H * frac_rows * len(PICS)  # B_ME bytes per pixel x the pictures of one launch
+            dom = "me" if kms["me"] >= max(kms[f"rd{abi.TX_W[ts]}"] for ts in RD_SIZES) else "rd"  # the single kernel with the longest launch
+            # HBM bytes per launch from the PMC passes committed under profiles/ (same command, N = 1): rocprofv3 cannot run
+            # inside this process, so the figure is the recorded one; null when it does not describe this run
+            traffic, traffic_src = None, None
+            tf = os.path.join(ROOT, "profiles", "r03_hbm_traffic.json")
+            if world == 1 and os.path.exists(tf):
+                traffic = json.load(open(tf))["kernels"].get("me_launch", {}).get("hbm_bytes_per_launch")
+                traffic_src = "profiles/r03_hbm_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; the kernels of the ME launch summed)"
+            ach = me_bytes / (kms["me"] * 1e-3) / 1e9
+            rd_roof = {}
+            for ts, descs, _, _, n, _ in wl.rd:
+                px, npk = n * abi.TX_W[ts] * abi.TX_H[ts], min(abi.TX_W[ts], 32) * min(abi.TX_H[ts], 32)
+                by = px * 6 + n * npk * 4
+                ms = kms[f"rd{abi.TX_W[ts]}"]
+                rd_roof[f"rd_tx_kernel<{abi.TX_W[ts]}x{abi.TX_H[ts]}, 10>"] = {"avg_launch_ms": round(ms, 4), "algorithmic_bytes_per_launch": int(by), "achieved": round(by / ms / 1e6, 1),
+                                                                          "frac": round(by / ms / 1e6 / HBM_PEAK_GBS, 4)}
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": "ME launch = " + " -> ".join(k.replace("svt_hip_me_", "").replace("_kernel", "") for k in chain_ms) + " (svt_hip_me_*_kernel, one stream)",
+                             "kernel_chain_ms": {k: round(v, 4) for k, v in chain_ms.items()}, "achieved": round(ach, 2),
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                             "algorithmic_bytes_per_launch": int(me_bytes), "avg_launch_ms": round(kms["me"], 4),
+                             "note": "the ME of a step is ONE launch of the C entry = a chain of kernels on one stream (dense pre-pass, then the per-block pipeline staged at its searches); "
+                                     "avg_launch_ms brackets the chain (HIP events on the launch stream), kernel_chain_ms each kernel (events the library records between them in a "
+                                     "separate pass; profiles/r03_kernel_stats_bench.csv has rocprofv3's averages of the same kernels).  By the task's rule the bound is HBM; the search "
+                                     "is issue-bound (SURVEY 8d): see valu_sad below", "longest_kernel": dom},
+                "rd_roofline": rd_roof,
+                # the longest SINGLE kernel of the step, whatever launch it belongs to (the ME launch is a chain of kernels)
+                "dominant_single_kernel": max([{"name": k, "avg_launch_ms": v["avg_launch_ms"], "bound": "hbm", "achieved": v["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                                "frac": v["frac"], "algorithmic_bytes_per_launch": v["algorithmic_bytes_per_launch"]} for k, v in rd_roof.items()]
+                                              + [{"name": k, "avg_launch_ms": round(v, 4), "bound": "valu (v_qsad_pk_u16_u8 issue)", "note": "one kernel of the ME chain: see roofline / roofline.valu_sad for the launch"}
+                                                 for k, v in chain_ms.items()], key=lambda e: e["avg_launch_ms"]) if (rd_roof or chain_ms) else None,
+                "kernel_ms": {k: round(v, 4) for k, v in kms.items()},
+            })
         if xch:
             out["exchange"] = {"kind": xch.kind, "rccl_ranks": rccl_ranks, "bytes_per_step_all_ranks": int(sum(wl.layout.rank_bytes)), "uniform_bands": bool(wl.layout.uniform),
                                "check": gather_check}
@@ -862,7 +920,7 @@ def main():
             out["end_to_end"] = e2e
         if extras:
             out["other_kernels"] = extras
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             cb = cpu_baseline(wl)
             out["cpu_baseline"] = cb
             # SURVEY 8d's diagnostic for the search kernel: |a-b| evaluated per second against the chip's packed-SAD issue rate

@@ -1,6 +1,6 @@
 """Phase tables of the kernels of the ME chain from the diagnostic builds (tools/build_me_profile_lib.sh: -DSVT_HIP_ME_PROFILE, where lane 0 of
 each wave accumulates s_memtime deltas per phase of a block; one library per kernel of the chain) on bench.py's own ME launch; prints the share
-of a block's time per phase and writes gpurun_out/me_phase_table.txt.   usage (GPU box): python tools/me_phase_profile.py [mode ...]
+of a block's time per phase and writes $SVT_VERIFY_OUT/me_phase_table.txt (default verify_out/).   usage (GPU box): python tools/me_phase_profile.py [mode ...]
 (modes as in me_kernel.hip: 0 one-kernel form -- run with SVT_HIP_ME_STAGED=0 --, 1 mid1, 5 s2, 7 tail; default 7 1 5).  One process per
 mode (the library is chosen at import): the script re-runs itself as a child per mode before anything touches the GPU."""
 import ctypes as C
@@ -17,7 +17,8 @@ KERNEL = {0: "svt_hip_me_b64_kernel (one-kernel form)", 1: "svt_hip_me_mid1_kern
 if len(sys.argv) != 3 or sys.argv[1] != "--one":
     import subprocess
     modes = [int(m) for m in sys.argv[1:]] or [7, 1, 5]
-    os.makedirs("gpurun_out", exist_ok=True)
+    out_dir = os.environ.get("SVT_VERIFY_OUT", "verify_out")
+    os.makedirs(out_dir, exist_ok=True)
     texts = []
     for m in modes:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(m)], capture_output=True, text=True, env={**os.environ, **({"SVT_HIP_ME_STAGED": "0"} if m == 0 else {})})
@@ -25,7 +26,7 @@ if len(sys.argv) != 3 or sys.argv[1] != "--one":
             print(r.stderr[-2000:])
             sys.exit(r.returncode)
         texts.append(r.stdout)
-    open("gpurun_out/me_phase_table.txt", "w").write("\n\n".join(texts))
+    open(os.path.join(out_dir, "me_phase_table.txt"), "w").write("\n\n".join(texts))
     print("\n\n".join(texts))
     sys.exit(0)
 MODE = int(sys.argv[2])

@@ -1,4 +1,4 @@
-"""Turns the rocprofv3 outputs merged into gpurun_out/ by tools/final_verify.sh (<R>s = --stats, <R>f / <R>w = --pmc FETCH_SIZE / WRITE_SIZE,
+"""Turns the rocprofv3 outputs written into $SVT_VERIFY_OUT (default verify_out/) by tools/final_verify.sh (<R>s = --stats, <R>f / <R>w = --pmc FETCH_SIZE / WRITE_SIZE,
 <R>q = SQ counters, bench_final.log, me_phase_table.txt) into the committed summaries under profiles/."""
 import collections
 import csv
@@ -9,7 +9,8 @@ import shutil
 import sys
 
 R = sys.argv[1] if len(sys.argv) > 1 else "r03"
-CMD = "python3 bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-extras"
+OUT = os.environ.get("SVT_VERIFY_OUT", "verify_out")
+CMD = "python3 bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-extras"
 
 
 def one(pattern):
@@ -28,8 +29,8 @@ def short(k):
     return None
 
 
-shutil.copy(one(f'gpurun_out/{R}s/**/*kernel_stats.csv'), f'profiles/{R}_kernel_stats_bench.csv')
-b = json.loads(open('gpurun_out/bench_final.log').read().strip().split('\n')[-1])
+shutil.copy(one(f'{OUT}/{R}s/**/*kernel_stats.csv'), f'profiles/{R}_kernel_stats_bench.csv')
+b = json.loads(open(f'{OUT}/bench_final.log').read().strip().split('\n')[-1])
 out = {"command": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, in a separate pass, WRITE_SIZE) -- {CMD}",
        "unit_note": "rocprofv3 reports FETCH_SIZE / WRITE_SIZE in KiB, averaged here over the launches of the run.  gfx950 correction (MI355X_MICROARCH.md, HBM section): FETCH_SIZE "
                     "tallies the 128-byte requests of 16-byte-per-lane loads at 64 bytes, so it is doubled for the ME kernel (whose window staging is such loads); the RD kernels' figure "
@@ -37,7 +38,7 @@ out = {"command": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, in a separat
                     "Infinity-Cache hits.", "kernels": {}}
 for d, cn in ((R + 'f', 'FETCH_SIZE'), (R + 'w', 'WRITE_SIZE')):
     acc = collections.defaultdict(list)
-    for r in csv.DictReader(open(one(f'gpurun_out/{d}/**/*counter_collection.csv'))):
+    for r in csv.DictReader(open(one(f'{OUT}/{d}/**/*counter_collection.csv'))):
         acc[r['Kernel_Name']].append(float(r['Counter_Value']))
     for k, v in acc.items():
         if short(k):
@@ -64,7 +65,7 @@ json.dump(out, open(f'profiles/{R}_hbm_traffic.json', 'w'), indent=1)
 b['roofline']['traffic'] = out['kernels']['me_launch']['hbm_bytes_per_launch']  # the PMC passes of this very verification run
 json.dump(b, open(f'profiles/{R}_bench_final.json', 'w'), indent=1)
 acc = collections.defaultdict(list)
-for r in csv.DictReader(open(one(f'gpurun_out/{R}q/**/*counter_collection.csv'))):
+for r in csv.DictReader(open(one(f'{OUT}/{R}q/**/*counter_collection.csv'))):
     if short(r['Kernel_Name']) and 'fullpel' not in r['Kernel_Name']:
         acc[(short(r['Kernel_Name']), r['Counter_Name'])].append(float(r['Counter_Value']))
 avg = {k: sum(v) / len(v) for k, v in acc.items()}
@@ -85,21 +86,21 @@ with open(f'profiles/{R}_sq_counters.txt', 'w') as f:
 # MFMA evidence: the block-statistics launches of bench.py's `other_kernels` leg (hadamard_path's 16x16 / 32x32 tiles on the matrix cores)
 try:
     acc = collections.defaultdict(list)
-    for r in csv.DictReader(open(one(f'gpurun_out/{R}m/**/*counter_collection.csv'))):
+    for r in csv.DictReader(open(one(f'{OUT}/{R}m/**/*counter_collection.csv'))):
         if 'block_stats_kernel' in r['Kernel_Name']:
             acc[('block_stats_kernel<' + r['Kernel_Name'].split('block_stats_kernel<')[1].split('>')[0] + '>', r['Counter_Name'])].append(float(r['Counter_Value']))
     with open(f'profiles/{R}_mfma_counters.txt', 'w') as f:
-        f.write("rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_F16 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_BUSY_CYCLES -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline\n")
+        f.write("rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_F16 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_BUSY_CYCLES -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline\n")
         f.write("block_stats_kernel launches (average per launch); the 8-bit instantiation with `satd` requested runs hadamard_path's 16x16 / 32x32 tiles as v_mfma_f32_16x16x16_f16 pairs\n\n")
         for k in sorted(acc):
             f.write(f"{k[0]:62s} {k[1]:28s} {sum(acc[k]) / len(acc[k]):.4g}  ({len(acc[k])} launches)\n")
-        if os.path.exists('gpurun_out/hadamard_mfma.txt'):
+        if os.path.exists(f'{OUT}/hadamard_mfma.txt'):
             f.write("\ntools/ubench/hadamard_mfma (the 8x8 core + SATD alone, int16 residual blocks, VALU butterflies vs two f16 MFMAs per four blocks):\n")
-            f.write(open('gpurun_out/hadamard_mfma.txt').read())
+            f.write(open(f'{OUT}/hadamard_mfma.txt').read())
 except AssertionError:
     pass
-if os.path.exists('gpurun_out/me_phase_table.txt'):
-    shutil.copy('gpurun_out/me_phase_table.txt', f'profiles/{R}_me_phase_table.txt')
+if os.path.exists(f'{OUT}/me_phase_table.txt'):
+    shutil.copy(f'{OUT}/me_phase_table.txt', f'profiles/{R}_me_phase_table.txt')
 print(open(f'profiles/{R}_kernel_stats_bench.csv').read()[:900])
 print({k: (v["hbm_bytes_per_launch"], v.get("traffic_over_algorithmic")) for k, v in out["kernels"].items()})
 print(b["value"], b["kernel_ms"], b["roofline"], b.get("cpu_baseline"))
