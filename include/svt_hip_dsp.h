@@ -179,6 +179,43 @@ uint64_t svt_hip_spy_rd_bias(uint64_t sse, uint32_t area_width, uint32_t area_he
 /* Enqueues one batch on the context stream (asynchronous); one wave per job. */
 int svt_hip_block_stats_batch(SvtHipContext *ctx, const SvtHipBlockStatsDesc *d);
 
+/* ---- batched SSIM distortion (--tune 2 / 3 / 4) -------------------------------------------------------------------
+ * Per job, src = input, ref = prediction or reconstruction:
+ *   ssim       the block mean ssim() / ssim_hbd() returns (Codec/mode_decision.c:4781-4878): 8x8 tiles when both sides are multiples
+ *              of 8, else 4x4 tiles; each tile's similarity() (Codec/enc_dec_process.c:709-735) clamped to [0, 1], the scores added in
+ *              raster order, divided by the tile count
+ *   ssim_dist  svt_spatial_full_distortion_ssim_kernel (mode_decision.c:4879-4921): (uint64_t)((1 - ssim) * w * h * 100 * 7 * m), m = 1
+ *              (8-bit) or 8 (10-bit), plus (uint64_t)(svt_psy_distortion{,_hbd} * psy_rd) when psy_rd > 0.  The callers' own shifts
+ *              (<<= 4 ...) stay with the callers.
+ * Sides are multiples of 4 in 4..128 (the callers pass cropped transform sizes); subpel_x / subpel_y must be 0.  Bit-exact with the
+ * reference's fp64 arithmetic.  The psy term reads whole 8x8 (4x4) tiles, past a cropped block's right / bottom edge like the reference.
+ * Optional pyramids: 64x64 regions, each read once for the 85 nested blocks in the layout of SvtHipBlockStatsDesc's (slots pyramid_out_base
+ * + 85 k ...); their results equal 85 plain jobs. */
+typedef struct SvtHipSsimBatchDesc {
+    uint8_t  bit_depth; /* 8: planes are uint8; 10: planes are uint16 (at most 10 bits per sample) */
+    uint8_t  reserved[3];
+    uint32_t n_jobs;
+    uint32_t src_stride, ref_stride;  /* in samples */
+    const void           *src, *ref;  /* device pointers */
+    const SvtHipBlockJob *jobs;       /* device pointer, n_jobs entries */
+    double                psy_rd;     /* strength of the psy term; <= 0: none */
+    /* per-job outputs, device pointers, at least one of them */
+    double               *ssim;
+    uint64_t             *ssim_dist;
+    uint32_t              n_pyramids, pyramid_out_base;
+    const SvtHipBlockJob *pyramids;   /* device pointer, n_pyramids 64x64 regions */
+} SvtHipSsimBatchDesc;
+
+/* Enqueues one batch on the context stream (asynchronous); one wave per job or region.  Returns non-zero and enqueues nothing when the
+ * descriptor fails validation (null context / pointers, no output, bit depth other than 8 or 10).  The jobs live in device memory, where the
+ * host cannot read them without waiting: check a host copy with svt_hip_ssim_check_jobs before uploading it.  A job that fails that check
+ * anyway reads no sample and gets ssim = -1, ssim_dist = UINT64_MAX. */
+int    svt_hip_ssim_batch(SvtHipContext *ctx, const SvtHipSsimBatchDesc *d);
+/* Host arrays: non-zero (and svt_hip_last_error) when a job's sides are not multiples of 4 in 4..128 or its subpel is set; with
+ * `pyramids` != 0, when a region is not 64x64. */
+int    svt_hip_ssim_check_jobs(const SvtHipBlockJob *jobs, uint32_t n_jobs, int pyramids);
+size_t svt_hip_ssim_desc_size(void); /* sizeof(SvtHipSsimBatchDesc) as compiled */
+
 /* Full-pel motion-compensated prediction from ME results: every 16x16 PU copies the block of `ref` displaced by its
  * best integer MV (sb_best_mv = SvtHipMeResults.sb_best_mv, device pointer; list / ref_idx select the reference).
  * ref / pred are device planes of `bit_depth` 8 (uint8) or 10 (uint16), strides in samples, no padding needed

@@ -170,6 +170,17 @@ uint64_t svt_spatial_full_distortion_kernel_facade_hip(uint8_t *input, uint32_t 
                                                        bool hbd_md, uint8_t mode, uint8_t compound_type, uint8_t temporal_layer_index,
                                                        double psy_rd, uint8_t spy_rd);
 
+/* SSIM tiles (aom_dsp_rtcd.h:906-913; bodies Codec/mode_decision.c:4682-4780): the unclamped similarity() of one 8x8 / 4x4 tile, 8-bit or
+ * 10-bit samples (the _hbd forms) */
+double svt_ssim_8x8_hip(const uint8_t *s, uint32_t sp, const uint8_t *r, uint32_t rp);
+double svt_ssim_4x4_hip(const uint8_t *s, uint32_t sp, const uint8_t *r, uint32_t rp);
+double svt_ssim_8x8_hbd_hip(const uint16_t *s, uint32_t sp, const uint16_t *r, uint32_t rp);
+double svt_ssim_4x4_hbd_hip(const uint16_t *s, uint32_t sp, const uint16_t *r, uint32_t rp);
+/* svt_spatial_full_distortion_ssim_kernel (mode_decision.c:4879-4921; a plain function there, replaced at link level): sides multiples of 4
+ * in 4..128; with hbd the pointers are uint16_t planes and the offsets count samples */
+uint64_t svt_spatial_full_distortion_ssim_kernel_hip(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *recon, int32_t recon_offset,
+                                                     uint32_t recon_stride, uint32_t area_width, uint32_t area_height, bool hbd, double psy_rd);
+
 /* svt_aom_hadamard_NxN (common_dsp_rtcd.h:1075-1085), svt_aom_satd (aom_dsp_rtcd.h:209) */
 void svt_aom_hadamard_4x4_hip(const int16_t *src_diff, ptrdiff_t src_stride, int32_t *coeff);
 void svt_aom_hadamard_8x8_hip(const int16_t *src_diff, ptrdiff_t src_stride, int32_t *coeff);

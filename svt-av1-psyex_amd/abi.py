@@ -183,6 +183,13 @@ class BlockStatsDesc(C.Structure):
                 ("n_pyramids", C.c_uint32), ("pyramid_out_base", C.c_uint32), ("pyramids", C.c_void_p)]
 
 
+class SsimBatchDesc(C.Structure):  # SvtHipSsimBatchDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("reserved", C.c_uint8 * 3), ("n_jobs", C.c_uint32), ("src_stride", C.c_uint32), ("ref_stride", C.c_uint32),
+                ("src", C.c_void_p), ("ref", C.c_void_p), ("jobs", C.c_void_p), ("psy_rd", C.c_double), ("ssim", C.c_void_p), ("ssim_dist", C.c_void_p),
+                ("n_pyramids", C.c_uint32), ("pyramid_out_base", C.c_uint32), ("pyramids", C.c_void_p)]
+
+
+SSIM_OUT_FIELDS = [("ssim", "<f8"), ("ssim_dist", "<u8")]
 PYRAMID_BLOCKS = 85  # nested square blocks of a 64x64 region: 1 + 4 + 16 + 64, each level in raster order
 BLOCK_JOB_DTYPE = [("src_offset", "<u4"), ("ref_offset", "<u4"), ("width", "u1"), ("height", "u1"), ("subpel_x", "u1"), ("subpel_y", "u1")]
 STATS_OUT_FIELDS = [("sad", "<u4"), ("sse", "<u8"), ("variance", "<u4"), ("var_sse", "<u4"), ("satd", "<u4")]

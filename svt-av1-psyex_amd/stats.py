@@ -1,4 +1,4 @@
-"""Host-side helpers of the batched block-statistics entry (svt_hip_block_stats_batch)."""
+"""Host-side helpers of the batched block-statistics entry (svt_hip_block_stats_batch) and of the SSIM batch (svt_hip_ssim_batch)."""
 import ctypes as C
 
 import numpy as np
@@ -77,3 +77,39 @@ def run_hip(ctx, src, ref, jobs, bit_depth, satd=True, psy_rd=None, facade=None,
     if not satd:
         res.pop("satd")
     return res
+
+
+def check_ssim_jobs(jobs, pyramids=False):
+    """svt_hip_ssim_check_jobs on a host job array: raises api.SvtHipError when a job's size or sub-pixel phase is not one the SSIM batch takes."""
+    from . import api
+    L = api.lib()
+    jobs = np.ascontiguousarray(jobs, dtype=abi.BLOCK_JOB_DTYPE)
+    rc = L.svt_hip_ssim_check_jobs(C.c_void_p(jobs.ctypes.data), C.c_uint32(len(jobs)), C.c_int(1 if pyramids else 0))
+    if rc:
+        raise api.SvtHipError(f"svt_hip_ssim_check_jobs: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+
+
+def run_ssim_hip(ctx, src, ref, jobs, bit_depth, psy_rd=None, pyramids=None):
+    """svt_hip_ssim_batch on host planes: {"ssim": float64[n], "ssim_dist": uint64[n]} with n = len(jobs) + 85 * len(pyramids), the regions'
+    outputs behind the plain jobs' (slots len(jobs) + 85 k ...).  psy_rd None: no psy term."""
+    import torch
+    from . import api
+    L = api.lib()
+    check_ssim_jobs(jobs)
+    if pyramids is not None:
+        check_ssim_jobs(pyramids, pyramids=True)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
+    n_plain = len(jobs)
+    n = n_plain + (abi.PYRAMID_BLOCKS * len(pyramids) if pyramids is not None else 0)
+    t_src, t_ref, t_jobs = dev(src), dev(ref), dev(jobs if n_plain else np.zeros(1, abi.BLOCK_JOB_DTYPE))
+    outs = {name: torch.zeros(max(n, 1) * np.dtype(dt).itemsize, dtype=torch.uint8, device="cuda") for name, dt in abi.SSIM_OUT_FIELDS}
+    d = abi.SsimBatchDesc(bit_depth=bit_depth, n_jobs=n_plain, src_stride=src.shape[1], ref_stride=ref.shape[1], psy_rd=psy_rd or 0.0)
+    if pyramids is not None and len(pyramids):
+        t_pyr = dev(pyramids)
+        d.n_pyramids, d.pyramid_out_base, d.pyramids = len(pyramids), n_plain, t_pyr.data_ptr()
+    d.src, d.ref, d.jobs = t_src.data_ptr(), t_ref.data_ptr(), t_jobs.data_ptr()
+    d.ssim, d.ssim_dist = outs["ssim"].data_ptr(), outs["ssim_dist"].data_ptr()
+    torch.cuda.synchronize()
+    ctx.check(L.svt_hip_ssim_batch(ctx._h, C.byref(d)), "svt_hip_ssim_batch")
+    ctx.sync()
+    return {name: outs[name].cpu().numpy().view(dt)[:n] for name, dt in abi.SSIM_OUT_FIELDS}

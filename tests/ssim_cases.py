@@ -1,0 +1,136 @@
+"""The SSIM distortion of the SSIM tunes, restated in numpy and Python floats (IEEE doubles, one rounding per operation, no contraction), and
+the job generators of its tests.  Reference (Source/Lib):
+  svt_ssim_{8x8,4x4}{,_hbd}_c                      Codec/mode_decision.c:4682-4780   the five uint32_t moments of a tile
+  similarity                                      Codec/enc_dec_process.c:709-735   the tile score
+  ssim, ssim_{8x8,4x4}_blocks{,_hbd}              Codec/mode_decision.c:4781-4878   clamped scores, summed in raster order, / tile count
+  svt_spatial_full_distortion_ssim_kernel         Codec/mode_decision.c:4879-4921   (1 - ssim) * count * 100 * 7 * m [+ psy term]
+The psy term is the oracle's svt_psy_distortion restatement (oracle/stats_oracle.c: orc_psy_distortion)."""
+import ctypes as C
+import os
+
+import numpy as np
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ssim.npz")
+
+CC = {8: (26634, 239708), 10: (428658, 3857925)}  # (64^2 (.01 * max)^2, 64^2 (.03 * max)^2), enc_dec_process.c:700-703
+MASK32 = np.uint64(0xFFFFFFFF)
+
+# every AV1 block size, every transform size, and cropped transform sizes (cropped_tx_width / height: any multiple of 4 up to 128)
+AV1_BLOCKS = [(4, 4), (4, 8), (8, 4), (8, 8), (8, 16), (16, 8), (16, 16), (16, 32), (32, 16), (32, 32), (32, 64), (64, 32), (64, 64), (64, 128),
+              (128, 64), (128, 128), (4, 16), (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
+TX_SIZES = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (4, 8), (8, 4), (8, 16), (16, 8), (16, 32), (32, 16), (32, 64), (64, 32), (4, 16), (16, 4),
+            (8, 32), (32, 8), (16, 64), (64, 16)]
+CROPPED = [(12, 8), (20, 16), (60, 64), (4, 128), (128, 4), (12, 12), (28, 20), (124, 128), (128, 124), (36, 4), (44, 60), (100, 76), (8, 12), (4, 20)]
+SIZES = sorted(set(AV1_BLOCKS) | set(TX_SIZES) | set(CROPPED))
+PSY_RDS = (0.0, 0.4, 1.0, 2.5)
+
+# Planes of the fixtures: four 136 x 136 regions side by side (room for a 128x128 block and the psy term's whole tiles past a cropped edge).
+# src regions: 0 noise, 1 flat, 2 0 / max extremes, 3 a gradient with noise.  ref regions: 0 src region 0 perturbed, 1 a copy of src region 0
+# (src region 0 against it: every score exactly 1), 2 src region 0 inverted (negative scores: the clamp), 3 0 / max extremes.
+REGION = 136
+N_REGIONS = 4
+
+
+def make_planes(rng, bit_depth):
+    mx = (1 << bit_depth) - 1
+    dt = np.uint8 if bit_depth == 8 else np.uint16
+    R = REGION
+    yy, xx = np.mgrid[0:R, 0:R]
+    noise = rng.integers(0, mx + 1, (R, R))
+    src = [noise, np.full((R, R), rng.integers(0, mx + 1)), rng.integers(0, 2, (R, R)) * mx,
+           np.clip((xx + 2 * yy) * mx // (3 * R) + rng.integers(-mx // 16, mx // 16 + 1, (R, R)), 0, mx)]
+    ref = [np.clip(noise + rng.integers(-mx // 20, mx // 20 + 1, (R, R)), 0, mx), noise.copy(), mx - noise, rng.integers(0, 2, (R, R)) * mx]
+    return np.concatenate(src, axis=1).astype(dt), np.concatenate(ref, axis=1).astype(dt)
+
+
+def region_jobs(rng, sizes, pairs, per_size=1, stride=REGION * N_REGIONS):
+    """jobs (abi.BLOCK_JOB_DTYPE) for every size x (src region, ref region) pair, at random positions; the same offset inside both regions
+    (so that the copy / inverted regions line up with src region 0)"""
+    from svt_av1_psyex_amd import abi
+    out = []
+    for (w, h) in sizes:
+        for (a, b) in pairs:
+            for _ in range(per_size):
+                wp, hp = -(-w // 8) * 8, -(-h // 8) * 8
+                y, x = int(rng.integers(0, REGION - hp + 1)), int(rng.integers(0, REGION - wp + 1))
+                out.append((y * stride + a * REGION + x, y * stride + b * REGION + x, w, h, 0, 0))
+    return np.array(out, dtype=abi.BLOCK_JOB_DTYPE)
+
+
+ALL_PAIRS = [(0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (2, 3), (3, 0), (2, 2)]
+
+
+def tile_moments(s, r, n):
+    """[tiles_y, tiles_x, 5] uint64 arrays of (sum s, sum r, sum s^2, sum r^2, sum s r) mod 2^32 over the n x n tiles of equal-shaped s / r"""
+    h, w = s.shape
+    s = s.astype(np.uint64).reshape(h // n, n, w // n, n)
+    r = r.astype(np.uint64).reshape(h // n, n, w // n, n)
+    m = [s.sum(axis=(1, 3)), r.sum(axis=(1, 3)), (s * s).sum(axis=(1, 3)), (r * r).sum(axis=(1, 3)), (s * r).sum(axis=(1, 3))]
+    return np.stack(m, axis=-1) & MASK32
+
+
+def similarity(sum_s, sum_r, sum_sq_s, sum_sq_r, sum_sxr, count, bd):
+    """enc_dec_process.c:709-735, as written: Python ints -> floats at the same places the C converts"""
+    cc1, cc2 = CC[bd]
+    c1, c2 = (cc1 * count * count) >> 12, (cc2 * count * count) >> 12
+    ssim_n = (2.0 * sum_s * sum_r + c1) * (2.0 * count * sum_sxr - 2.0 * sum_s * sum_r + c2)
+    ssim_d = (float(sum_s) * sum_s + float(sum_r) * sum_r + c1) * (float(count) * sum_sq_s - float(sum_s) * sum_s + float(count) * sum_sq_r - float(sum_r) * sum_r + c2)
+    return ssim_n / ssim_d
+
+
+def tile_score(s, r, bd):
+    """svt_ssim_{8x8,4x4}{,_hbd}_c of one tile (s, r: n x n arrays): the unclamped score"""
+    n = s.shape[0]
+    m = [int(v) for v in tile_moments(s, r, n)[0, 0]]
+    return similarity(*m, n * n, bd)
+
+
+def block_ssim(s, r, bd):
+    """ssim() / ssim_hbd() of the w x h block s against r"""
+    h, w = s.shape
+    n = 8 if (w % 8 == 0 and h % 8 == 0) else 4
+    mo = tile_moments(s, r, n).reshape(-1, 5)
+    total, samples = 0.0, 0
+    for row in mo:  # raster order, one addition at a time
+        v = similarity(*(int(x) for x in row), n * n, bd)
+        v = 0 if v < 0 else (1 if v > 1 else v)  # CLIP3(0, 1, v)
+        total += v
+        samples += 1
+    return total / samples
+
+
+def psy_energy(oracle, src, so, sp, ref, ro, rp, w, h, bd):
+    """svt_psy_distortion{,_hbd} through the oracle (offsets in samples of the flattened planes)"""
+    oracle.orc_psy_distortion.restype = C.c_uint64
+    bpp = 1 if bd == 8 else 2
+    return int(oracle.orc_psy_distortion(C.c_void_p(src.ctypes.data + so * bpp), C.c_uint32(sp), C.c_void_p(ref.ctypes.data + ro * bpp), C.c_uint32(rp),
+                                         C.c_uint32(w), C.c_uint32(h), C.c_int(0 if bd == 8 else 1)))
+
+
+def ssim_distortion(ssim, w, h, bd, psy_rd=0.0, energy=0):
+    """svt_spatial_full_distortion_ssim_kernel from the block's ssim() and (for psy_rd > 0) its psy energy"""
+    count, m = w * h, (1 if bd == 8 else 8)
+    d = int((1 - ssim) * count * 100 * 7 * m)
+    if psy_rd > 0.0:
+        d += int(energy * psy_rd)
+    return d
+
+
+def run_jobs(oracle, src, ref, jobs, bd, psy_rd=0.0):
+    """{"ssim": float64[n], "ssim_dist": uint64[n]} of plain jobs on 2-D planes"""
+    sp, rp = src.shape[1], ref.shape[1]
+    fs, fr = np.ascontiguousarray(src).reshape(-1), np.ascontiguousarray(ref).reshape(-1)
+    ssim = np.zeros(len(jobs), np.float64)
+    dist = np.zeros(len(jobs), np.uint64)
+    for i, j in enumerate(jobs):
+        so, ro, w, h = int(j["src_offset"]), int(j["ref_offset"]), int(j["width"]), int(j["height"])
+        (sy, sx), (ry, rx) = divmod(so, sp), divmod(ro, rp)
+        ssim[i] = block_ssim(src[sy:sy + h, sx:sx + w], ref[ry:ry + h, rx:rx + w], bd)
+        e = psy_energy(oracle, fs, so, sp, fr, ro, rp, w, h, bd) if psy_rd > 0.0 else 0
+        dist[i] = ssim_distortion(ssim[i], w, h, bd, psy_rd, e)
+    return {"ssim": ssim, "ssim_dist": dist}
+
+
+def bits(a):
+    """float64 values as their uint64 bit patterns (exact comparisons)"""
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
