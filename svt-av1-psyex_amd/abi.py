@@ -248,3 +248,28 @@ class SubpelBatchDesc(C.Structure):
                 ("subpel_search_type", C.c_int32), ("mvp_th", C.c_int32), ("hp_mv_th", C.c_int32), ("mv_cost_type", C.c_int32),
                 ("error_per_bit", C.c_int32), ("mvjcost", C.c_void_p), ("mvcost", C.c_void_p * 2), ("best_mv", C.c_void_p), ("besterr", C.c_void_p),
                 ("distortion", C.c_void_p), ("sse", C.c_void_p), ("center_err", C.c_void_p)]
+
+
+# ---- include/svt_hip_tpl.h ----
+TPL_STATS_DTYPE = np.dtype([("srcrf_dist", "<i8"), ("recrf_dist", "<i8"), ("srcrf_rate", "<i8"), ("recrf_rate", "<i8"), ("mc_dep_rate", "<i8"),
+                            ("mc_dep_dist", "<i8"), ("mv_row", "<i2"), ("mv_col", "<i2"), ("reserved", "<u4"), ("ref_frame_poc", "<u8")])
+TPL_SRC_STATS_DTYPE = np.dtype([("srcrf_dist", "<i8"), ("srcrf_rate", "<i8"), ("ref_frame_poc", "<u8"), ("mv_row", "<i2"), ("mv_col", "<i2"),
+                                ("best_mode", "u1"), ("reserved", "u1", (3,)), ("best_rf_idx", "<i4"), ("best_intra_mode", "u1"),
+                                ("reserved2", "u1", (3,))])
+TPL_PAD = 32
+
+
+class TplRef(C.Structure):  # SvtHipTplRef
+    _fields_ = [("src", PlaneDesc), ("recon", PlaneDesc), ("picture_number", C.c_uint64), ("max_width", C.c_uint16), ("max_height", C.c_uint16),
+                ("usable", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class TplDesc(C.Structure):  # SvtHipTplDesc
+    _fields_ = [("cur", PlaneDesc), ("aligned_width", C.c_uint16), ("aligned_height", C.c_uint16), ("recon", PlaneDesc), ("me", MeResults),
+                ("n_pu", C.c_uint8), ("max_cand", C.c_uint8), ("max_refs", C.c_uint8), ("max_l0", C.c_uint8), ("enable_me_16x16", C.c_uint8),
+                ("reserved0", C.c_uint8 * 3), ("refs", (TplRef * MAX_REFS) * MAX_LISTS),
+                ("dispenser_search_level", C.c_uint8), ("subsample_tx", C.c_uint8), ("pf_shape", C.c_uint8), ("synth_blk_size", C.c_uint8),
+                ("disable_intra_pred", C.c_uint8), ("is_ref", C.c_uint8), ("slice_is_i", C.c_uint8), ("tpl_slice_is_i", C.c_uint8),
+                ("src_pass", C.c_uint8), ("store_src_stats", C.c_uint8), ("use_sad_in_src_search", C.c_uint8), ("intra_mode_end", C.c_uint8),
+                ("subpel_depth", C.c_uint8), ("compute_rate", C.c_uint8), ("in_loop_ois", C.c_uint8), ("reserved1", C.c_uint8 * 3),
+                ("quant", QuantRow), ("tpl_stats", C.c_void_p), ("n_tpl_stats", C.c_uint32), ("n_tpl_src_stats", C.c_uint32), ("tpl_src_stats", C.c_void_p)]

@@ -126,7 +126,8 @@ int svt_hip_context_create(SvtHipContext **out, int device) {
     { const char *e = getenv("SVT_HIP_ME_STAGED"); ctx->me_staged = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1; }
     // lane 0 (the asynchronous entries' stream) and this device's transform tables exist from the start; the borrowed
     // lanes are made when a synchronous entry first needs one
-    if (svt_hip_lane_setup(ctx, &ctx->lane[0], true) != SVT_HIP_OK || svt_hip_rd_tables_init(ctx) != SVT_HIP_OK) {
+    if (svt_hip_lane_setup(ctx, &ctx->lane[0], true) != SVT_HIP_OK || svt_hip_rd_tables_init(ctx) != SVT_HIP_OK ||
+        svt_hip_tpl_tables_init(ctx) != SVT_HIP_OK) {
         svt_hip_context_destroy(ctx);
         return SVT_HIP_ERR_NO_DEVICE;
     }
@@ -157,6 +158,7 @@ void svt_hip_context_destroy(SvtHipContext *ctx) {
     if (ctx->io_stream) { hipStreamSynchronize(ctx->io_stream); hipStreamDestroy(ctx->io_stream); }
     if (ctx->io_fence) hipEventDestroy(ctx->io_fence);
     svt_hip_rd_tables_free(ctx);
+    svt_hip_tpl_free(ctx);
     delete ctx;
 }
 

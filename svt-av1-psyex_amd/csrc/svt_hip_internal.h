@@ -55,6 +55,8 @@ struct SvtHipContext {
     uint32_t    me_waves_per_cu;       // 0: as many persistent ME waves per CU as fit; else an upper limit (svt_hip_context_set_me_waves_per_cu)
     hipStream_t io_stream;             // transfer stream of svt_hip_pa_picture_update_ahead (created on first use)
     hipEvent_t  io_fence;              // orders the transfer stream behind the context stream
+    void       *tpl_scratch;           // per-block state of svt_hip_tpl_dispense (tpl_kernel.hip), grown on demand, used in stream order
+    size_t      tpl_scratch_bytes;
 };
 
 struct SvtHipPaPicture {
@@ -110,4 +112,7 @@ int    svt_hip_scratch(SvtHipContext *ctx, SvtHipLane *lane, size_t bytes, void 
 // rd_kernel.hip: cosine / inverse-scan tables of the context's device
 int    svt_hip_rd_tables_init(SvtHipContext *ctx);
 void   svt_hip_rd_tables_free(SvtHipContext *ctx);
+// tpl_kernel.hip: its copy of the cosine table; the dispenser's scratch
+int    svt_hip_tpl_tables_init(SvtHipContext *ctx);
+void   svt_hip_tpl_free(SvtHipContext *ctx);
 #endif

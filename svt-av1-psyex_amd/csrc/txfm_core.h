@@ -1,0 +1,369 @@
+// txfm_core.h -- device code shared by the kernels that run the AV1 integer transforms (rd_kernel.hip, tpl_kernel.hip): the 1-D
+// forward / inverse DCT, ADST and identity kernels of the reference, by structure, the shift / clamp helpers of the 2-D passes and
+// the wave reductions.  Each translation unit that includes it has its own copy of the constant tables; c_cospi is filled at context
+// creation (svt_hip_rd_tables_init, svt_hip_tpl_tables_init).
+#ifndef SVT_HIP_TXFM_CORE_H
+#define SVT_HIP_TXFM_CORE_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace {
+
+typedef unsigned long long u64;
+typedef long long          i64;
+
+__constant__ int32_t c_cospi[4][64]; // cospi_arr(bit), bit 10..13 (round(cos(j*pi/128) * 2^bit)), filled at init
+// svt_aom_eb_av1_sinpi_arr_data rows for cos_bit 10..13 (Codec/inv_transforms.c:3228-3234)
+__constant__ int32_t c_sinpi[4][5] = {{0, 330, 621, 836, 951}, {0, 660, 1241, 1672, 1901}, {0, 1321, 2482, 3344, 3803}, {0, 2642, 4964, 6689, 7606}};
+
+struct TxGeom { uint8_t w, h; };
+__host__ __device__ constexpr int tx_wide(int s) { constexpr uint8_t t[19] = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64}; return t[s]; }
+__host__ __device__ constexpr int tx_high(int s) { constexpr uint8_t t[19] = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16}; return t[s]; }
+__host__ __device__ constexpr int ilog2c(int n) { return n <= 1 ? 0 : 1 + ilog2c(n >> 1); }
+__host__ __device__ constexpr int brevc(int v, int bits) { int r = 0; for (int i = 0; i < bits; i++) r |= ((v >> i) & 1) << (bits - 1 - i); return r; }
+
+// fwd_txfm_shift_ls (Codec/transforms.h:27-45), fwd_cos_bit_col/row (:47-50), inv shifts (Codec/inv_transforms.c:17-35),
+// av1_get_tx_scale_tab (Codec/full_loop.h:53)
+__device__ const int8_t  c_fwd_shift[19][3] = {{2, 0, 0},  {2, -1, 0}, {2, -2, 0}, {2, -4, 0}, {0, -2, -2}, {2, -1, 0}, {2, -1, 0}, {2, -2, 0}, {2, -2, 0}, {2, -4, 0},
+                                               {2, -4, 0}, {0, -2, -2}, {2, -4, -2}, {2, -1, 0}, {2, -1, 0}, {2, -2, 0}, {2, -2, 0}, {0, -2, 0}, {2, -4, 0}};
+__device__ const int8_t  c_fwd_cos_col[5][5] = {{13, 13, 13, 0, 0}, {13, 13, 13, 12, 0}, {13, 13, 13, 12, 13}, {0, 13, 13, 12, 13}, {0, 0, 13, 12, 13}};
+__device__ const int8_t  c_fwd_cos_row[5][5] = {{13, 13, 12, 0, 0}, {13, 13, 13, 12, 0}, {13, 13, 12, 13, 12}, {0, 12, 13, 12, 11}, {0, 0, 12, 11, 10}};
+__device__ const int8_t  c_inv_shift0[19]    = {0, -1, -2, -2, -2, 0, 0, -1, -1, -1, -1, -1, -1, -1, -1, -2, -2, -2, -2};
+__device__ const uint8_t c_log_scale[19]     = {0, 0, 0, 1, 2, 0, 0, 0, 0, 1, 1, 2, 2, 0, 0, 0, 0, 1, 1};
+// 1-D kernel of the column (vertical) / row (horizontal) pass per TxType: 0 DCT, 1 ADST, 2 FLIPADST, 3 identity (vtx_tab/htx_tab)
+__device__ const uint8_t c_vtx[16] = {0, 1, 0, 1, 2, 0, 2, 1, 2, 3, 0, 3, 1, 3, 2, 3};
+__device__ const uint8_t c_htx[16] = {0, 0, 1, 1, 0, 2, 2, 2, 1, 3, 3, 0, 3, 1, 3, 2};
+
+// ((int64)a * b) >> sh (0 < sh < 32) for operands that fit 24 signed bits, low 32 bits of the result: three full-rate instructions
+// (v_mul_i32_i24, v_mul_hi_i32_i24, v_alignbit_b32) instead of the quarter-rate 32 x 32 -> 64 multiply
+__device__ __forceinline__ int32_t mul24_shr(int32_t a, int32_t b, int sh) {
+    int32_t hi;
+    asm("v_mul_hi_i32_i24 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
+    return (int32_t)__builtin_amdgcn_alignbit((uint32_t)hi, (uint32_t)__mul24(a, b), (uint32_t)sh);
+}
+__device__ __forceinline__ int32_t rshift64(i64 v, int bit) { return (int32_t)((v + ((i64)1 << (bit - 1))) >> bit); }
+// half_btf of the reference (Codec/transforms.h / inv_transforms.h): two 32-bit wrapping products, summed and rounded in
+// 64 bits.  MUL == 1 (inverse transforms): both operands of every product fit 24 signed bits -- cos weights < 2^13, data
+// < 2^19 behind the reference's own stage clamps (clamp_value to bd + 8 / 16..18 bits) -- so the full-rate v_mul_i32_i24
+// returns the same low 32 bits as the quarter-rate v_mul_lo_u32.  Forward transforms keep the 32-bit multiply: their
+// data range depends on the caller's samples.
+// MUL == 2: the caller has bounded the data so that |a| + |b| < 2^18 (weights <= 2^13): neither product wraps and their sum with the rounding
+// term stays below 2^31, so the whole butterfly is three full-rate 32-bit instructions with the reference's exact result.
+template <int MUL> __device__ __forceinline__ int32_t hbtf(int32_t w0, int32_t a, int32_t w1, int32_t b, int bit) {
+    if constexpr (MUL == 2) return (__mul24(w1, b) + (__mul24(w0, a) + (1 << (bit - 1)))) >> bit; // two v_mad_i32_i24 + a shift
+    i64 s;
+    if constexpr (MUL == 1) s = (i64)__mul24(w0, a) + (i64)__mul24(w1, b);
+    else s = (i64)(int32_t)((uint32_t)w0 * (uint32_t)a) + (i64)(int32_t)((uint32_t)w1 * (uint32_t)b);
+    return (int32_t)((s + ((i64)1 << (bit - 1))) >> bit);
+}
+// clamp_value of a SUM or DIFFERENCE inside an inverse pass.  The reference widens to 64 bits before it clamps; here the operands are at most
+// 20-bit numbers -- the pass inputs are clamped to bd + 8 / 16 bits on entry, every butterfly output is clamped again, and a half_btf output is
+// below sqrt(2) times its inputs -- so the 32-bit sum is the same number and the clamp is one v_med3_i32.
+__device__ __forceinline__ int32_t clamp32(int32_t v, int bit) {
+    const int32_t hi = (1 << (bit - 1)) - 1, lo = -(1 << (bit - 1));
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+__device__ __forceinline__ int32_t clampv(i64 v, int bit) {
+    const i64 hi = ((i64)1 << (bit - 1)) - 1, lo = -((i64)1 << (bit - 1));
+    return (int32_t)(v < lo ? lo : (v > hi ? hi : v));
+}
+__device__ __forceinline__ int32_t clampv(int32_t v, int bit) { return clamp32(v, bit); } // a 32-bit value against a range of at most 32 bits: the same number
+__device__ __forceinline__ int32_t wadd(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
+__device__ __forceinline__ int32_t wsub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }
+
+// ---------------------------------------------------------------------------------------------------------
+// DCT flow graph, by structure.  x[M..2M) is the odd part of a 2M-point DCT:
+//   rotation stage k (k = 1..log2(M)-1): lanes in the middle half of every group of 2t (t = M >> k) are rotated
+//     with their mirror image (3M-1-p); angle (1 + 4*brev(group)) * (64 >> k); symmetric 2x2 blocks, so the same
+//     stage serves both directions;
+//   butterfly stage k: groups of t, even groups sum-first, odd groups difference-first;
+//   final stage: lane M+i with 2M-1-i, angle 64 - (2*brev(i)+1)*(32/M).
+// CLAMP < 0: forward transform (no clamps); otherwise the reference's clamp_value(stage_range) of the inverse.
+// ---------------------------------------------------------------------------------------------------------
+template <int M, int K, int MUL> __device__ __forceinline__ void odd_rot(int32_t *x, const int32_t *c, int bit) {
+    constexpr int t = M >> K;
+    if constexpr (K == 1) {
+#pragma unroll
+        for (int j = 0; j < M / 4; j++) {
+            const int p = M + M / 4 + j, m = 3 * M - 1 - p;
+            const int32_t a = x[p], b = x[m];
+            x[p] = hbtf<MUL>(-c[32], a, c[32], b, bit);
+            x[m] = hbtf<MUL>(c[32], b, c[32], a, bit);
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < (1 << (K - 2)); g++) {
+            const int A = (1 + 4 * brevc(g, K - 2)) * (64 >> K), B = 64 - A, base = M + g * 2 * t;
+#pragma unroll
+            for (int j = 0; j < t / 2; j++) {
+                const int p = base + t / 2 + j, m = 3 * M - 1 - p;
+                const int32_t a = x[p], b = x[m];
+                x[p] = hbtf<MUL>(-c[A], a, c[B], b, bit);
+                x[m] = hbtf<MUL>(c[A], b, c[B], a, bit);
+            }
+#pragma unroll
+            for (int j = 0; j < t / 2; j++) {
+                const int p = base + t + j, m = 3 * M - 1 - p;
+                const int32_t a = x[p], b = x[m];
+                x[p] = hbtf<MUL>(-c[B], a, -c[A], b, bit);
+                x[m] = hbtf<MUL>(c[B], b, -c[A], a, bit);
+            }
+        }
+    }
+}
+template <int M, int K, int CLAMP> __device__ __forceinline__ void odd_bfly(int32_t *x) {
+    constexpr int t = M >> K;
+#pragma unroll
+    for (int g = 0; g < M / t; g++) {
+#pragma unroll
+        for (int j = 0; j < t / 2; j++) {
+            const int i0 = M + g * t + j, i1 = M + g * t + t - 1 - j;
+            const int32_t lo = x[i0], hi = x[i1];
+            int32_t s, d;
+            if constexpr (CLAMP < 0) { s = wadd(lo, hi); d = (g & 1) ? wsub(hi, lo) : wsub(lo, hi); }
+            else { s = clamp32(lo + hi, CLAMP); d = clamp32((g & 1) ? hi - lo : lo - hi, CLAMP); }
+            x[i0] = (g & 1) ? d : s;
+            x[i1] = (g & 1) ? s : d;
+        }
+    }
+}
+template <int M, bool INV, int MUL = INV ? 1 : 0> __device__ __forceinline__ void odd_final(int32_t *x, const int32_t *c, int bit) {
+#pragma unroll
+    for (int i = 0; i < M / 2; i++) {
+        const int A = 64 - (2 * brevc(i, ilog2c(M)) + 1) * (32 / M), B = 64 - A, p = M + i, m = 2 * M - 1 - i;
+        const int32_t a = x[p], b = x[m];
+        if constexpr (!INV) { x[p] = hbtf<MUL>(c[A], a, c[B], b, bit); x[m] = hbtf<MUL>(c[A], b, -c[B], a, bit); }
+        else { x[p] = hbtf<MUL>(c[A], a, -c[B], b, bit); x[m] = hbtf<MUL>(c[B], a, c[A], b, bit); }
+    }
+}
+template <int M, int K, int FM> struct OddFwd {
+    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, int bit) {
+        if constexpr (K < ilog2c(M)) {
+            odd_rot<M, K, FM>(x, c, bit);
+            odd_bfly<M, K, -1>(x);
+            OddFwd<M, K + 1, FM>::run(x, c, bit);
+        }
+    }
+};
+template <int M, int K, int CLAMP, int IM> struct OddInv {
+    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, int bit) {
+        if constexpr (K >= 1) {
+            odd_bfly<M, K, CLAMP>(x);
+            odd_rot<M, K, IM>(x, c, bit);
+            OddInv<M, K - 1, CLAMP, IM>::run(x, c, bit);
+        }
+    }
+};
+// FM (forward multiply mode): 0 = 32-bit wrapping products (any input), 1 = full-rate 24-bit multiplies -- exact whenever every node of the
+// pass fits 24 signed bits, which the callers establish from the block's largest residual (see fwd_mul24_safe)
+template <int N, int FM> __device__ __forceinline__ void fdct_core(int32_t *x, const int32_t *c, int bit) {
+    if constexpr (N == 2) {
+        const int32_t a = x[0], b = x[1];
+        x[0] = hbtf<FM>(c[32], a, c[32], b, bit);
+        x[1] = hbtf<FM>(-c[32], b, c[32], a, bit);
+    } else {
+        constexpr int M = N / 2;
+#pragma unroll
+        for (int i = 0; i < M; i++) { const int32_t a = x[i], b = x[N - 1 - i]; x[i] = wadd(a, b); x[N - 1 - i] = wsub(a, b); }
+        fdct_core<M, FM>(x, c, bit);
+        OddFwd<M, 1, FM>::run(x, c, bit);
+        odd_final<M, false, FM>(x, c, bit);
+    }
+}
+// IM (inverse multiply mode): 1 = 24-bit products summed in 64 bits (any clamped input), 2 = the three-instruction butterflies, exact while
+// every node of the pass is below 2^18 (weights <= 2^12): the callers measure the pass input
+template <int N, int CLAMP, int IM> __device__ __forceinline__ void idct_core(int32_t *x, const int32_t *c, int bit) {
+    if constexpr (N == 2) {
+        const int32_t a = x[0], b = x[1];
+        x[0] = hbtf<IM>(c[32], a, c[32], b, bit);
+        x[1] = hbtf<IM>(c[32], a, -c[32], b, bit);
+    } else {
+        constexpr int M = N / 2;
+        odd_final<M, true, IM>(x, c, bit);
+        OddInv<M, ilog2c(M) - 1, CLAMP, IM>::run(x, c, bit);
+        idct_core<M, CLAMP, IM>(x, c, bit);
+#pragma unroll
+        for (int i = 0; i < M; i++) { const int32_t a = x[i], b = x[N - 1 - i]; x[i] = clamp32(a + b, CLAMP); x[N - 1 - i] = clamp32(a - b, CLAMP); }
+    }
+}
+template <int N> __device__ __forceinline__ void permute_brev(int32_t *x) { // out[k] = in[brev(k)]: an involution, swap pairs
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const int r = brevc(k, ilog2c(N));
+        if (r > k) { const int32_t t = x[k]; x[k] = x[r]; x[r] = t; }
+    }
+}
+
+// ---- ADST 8 / 16 (svt_av1_fadst8/16_new, iadst8/16_new) and ADST 4 ----
+template <int N> __host__ __device__ constexpr int adst_perm(int k) { // P_N[2j] = P_{N/2}[j], P_N[2j+1] = N-1-P_{N/2}[j], P_2 = {0,1}
+    if constexpr (N == 2) return k;
+    else return (k & 1) ? N - 1 - adst_perm<N / 2>(k >> 1) : adst_perm<N / 2>(k >> 1);
+}
+template <int N, int HH, int MUL> __device__ __forceinline__ void adst_rot(int32_t *x, const int32_t *c, int bit) {
+#pragma unroll
+    for (int b = 0; b < N; b += 2 * HH) {
+        if constexpr (HH == 2) {
+            const int32_t a = x[b + 2], d = x[b + 3];
+            x[b + 2] = hbtf<MUL>(c[32], a, c[32], d, bit);
+            x[b + 3] = hbtf<MUL>(c[32], a, -c[32], d, bit);
+        } else {
+#pragma unroll
+            for (int j = 0; j < HH / 4; j++) {
+                const int A = (4 * j + 1) * (64 / HH), B = 64 - A, p = b + HH + 2 * j, q = b + HH + HH / 2 + 2 * j;
+                int32_t a = x[p], d = x[p + 1];
+                x[p]     = hbtf<MUL>(c[A], a, c[B], d, bit);
+                x[p + 1] = hbtf<MUL>(c[B], a, -c[A], d, bit);
+                a = x[q]; d = x[q + 1];
+                x[q]     = hbtf<MUL>(-c[B], a, c[A], d, bit);
+                x[q + 1] = hbtf<MUL>(c[A], a, c[B], d, bit);
+            }
+        }
+    }
+}
+template <int N, int HH, int CLAMP> __device__ __forceinline__ void adst_bfly(int32_t *x) {
+#pragma unroll
+    for (int b = 0; b < N; b += 2 * HH)
+#pragma unroll
+        for (int j = 0; j < HH; j++) {
+            const int32_t a = x[b + j], d = x[b + j + HH];
+            if constexpr (CLAMP < 0) { x[b + j] = wadd(a, d); x[b + j + HH] = wsub(a, d); }
+            else { x[b + j] = clamp32(a + d, CLAMP); x[b + j + HH] = clamp32(a - d, CLAMP); }
+        }
+}
+template <int N, int MUL> __device__ __forceinline__ void adst_last(int32_t *x, const int32_t *c, int bit) {
+#pragma unroll
+    for (int j = 0; j < N / 2; j++) {
+        const int A = (4 * j + 1) * (64 / (2 * N)), B = 64 - A;
+        const int32_t a = x[2 * j], d = x[2 * j + 1];
+        x[2 * j]     = hbtf<MUL>(c[A], a, c[B], d, bit);
+        x[2 * j + 1] = hbtf<MUL>(c[B], a, -c[A], d, bit);
+    }
+}
+template <int N, int HH, int FM> struct AdstFwd {
+    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, int bit) {
+        if constexpr (HH < N) { adst_rot<N, HH, FM>(x, c, bit); adst_bfly<N, HH, -1>(x); AdstFwd<N, HH * 2, FM>::run(x, c, bit); }
+    }
+};
+template <int N, int HH, int CLAMP, int IM> struct AdstInv {
+    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, int bit) {
+        if constexpr (HH >= 2) { adst_bfly<N, HH, CLAMP>(x); adst_rot<N, HH, IM>(x, c, bit); AdstInv<N, HH / 2, CLAMP, IM>::run(x, c, bit); }
+    }
+};
+template <int N, int FM> __device__ __forceinline__ void fadst(int32_t *x, const int32_t *c, int bit) {
+    int32_t y[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) { const int32_t v = x[adst_perm<N>(k)]; y[k] = (__builtin_popcount(k) & 1) ? (int32_t)(0u - (uint32_t)v) : v; }
+    AdstFwd<N, 2, FM>::run(y, c, bit);
+    adst_last<N, FM>(y, c, bit);
+#pragma unroll
+    for (int j = 0; j < N / 2; j++) { x[2 * j] = y[2 * j + 1]; x[2 * j + 1] = y[N - 2 - 2 * j]; }
+}
+template <int N, int CLAMP, int IM> __device__ __forceinline__ void iadst(int32_t *x, const int32_t *c, int bit) {
+    int32_t y[N];
+#pragma unroll
+    for (int j = 0; j < N / 2; j++) { y[2 * j + 1] = x[2 * j]; y[N - 2 - 2 * j] = x[2 * j + 1]; }
+    adst_last<N, IM>(y, c, bit);
+    AdstInv<N, N / 2, CLAMP, IM>::run(y, c, bit);
+#pragma unroll
+    for (int k = 0; k < N; k++) x[adst_perm<N>(k)] = (__builtin_popcount(k) & 1) ? (int32_t)(0u - (uint32_t)y[k]) : y[k];
+}
+#define MUL32(a, b) ((int32_t)((uint32_t)(a) * (uint32_t)(b)))
+__device__ __forceinline__ void adst4(int32_t *x, int bit, bool inverse) { // transforms.c:1415-1503, inv_transforms.c:722-806
+    const int32_t *s = c_sinpi[bit - 10];
+    const int32_t x0 = x[0], x1 = x[1], x2 = x[2], x3 = x[3];
+    if (!(x0 | x1 | x2 | x3)) return;
+    if (!inverse) {
+        const int32_t s7 = wsub(wadd(x0, x1), x3);
+        const int32_t a0 = wadd(wadd(MUL32(s[1], x0), MUL32(s[2], x1)), MUL32(s[4], x3)), a1 = MUL32(s[3], s7);
+        const int32_t a2 = wadd(wsub(MUL32(s[4], x0), MUL32(s[1], x1)), MUL32(s[2], x3)), a3 = MUL32(s[3], x2);
+        x[0] = rshift64(wadd(a0, a3), bit); x[1] = rshift64(a1, bit); x[2] = rshift64(wsub(a2, a3), bit); x[3] = rshift64(wadd(wsub(a2, a0), a3), bit);
+    } else {
+        const int32_t s7 = wadd(wsub(x0, x2), x3);
+        const int32_t a0 = wadd(wadd(MUL32(s[1], x0), MUL32(s[4], x2)), MUL32(s[2], x3));
+        const int32_t a1 = wsub(wsub(MUL32(s[2], x0), MUL32(s[1], x2)), MUL32(s[4], x3)), a3 = MUL32(s[3], x1), a2 = MUL32(s[3], s7);
+        x[0] = rshift64(wadd(a0, a3), bit); x[1] = rshift64(wadd(a1, a3), bit); x[2] = rshift64(a2, bit); x[3] = rshift64(wsub(wadd(a0, a1), a3), bit);
+    }
+}
+template <int N> __device__ __forceinline__ void identity(int32_t *x) { // transforms.c:2205-2236, inv_transforms.c:2331-2363
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        if constexpr (N == 4) x[i] = rshift64((i64)x[i] * 5793, 12);
+        else if constexpr (N == 8) x[i] = (int32_t)((uint32_t)x[i] * 2u);
+        else if constexpr (N == 16) x[i] = rshift64((i64)x[i] * 2 * 5793, 12);
+        else if constexpr (N == 32) x[i] = (int32_t)((uint32_t)x[i] * 4u);
+        else x[i] = rshift64((i64)x[i] * 4 * 5793, 12);
+    }
+}
+// 1-D dispatch: type 0 DCT, 1/2 ADST (flips are applied by the 2-D passes), 3 identity.  Wave-uniform switch.
+template <int N, int FM> __device__ __forceinline__ void fwd_1d(int32_t *x, int type, int bit) {
+    const int32_t *c = c_cospi[bit - 10];
+    if (type == 3) identity<N>(x);
+    else if (type == 0) { fdct_core<N, FM>(x, c, bit); permute_brev<N>(x); }
+    else if constexpr (N == 4) adst4(x, bit, false);
+    else if constexpr (N <= 16) fadst<N, FM>(x, c, bit);
+}
+// A block's forward transform may use the 24-bit multiplies when |residual| <= 4095: a node of a 1-D pass is a sum of at most N inputs of that
+// pass with weights of magnitude <= 1, so with the up-shift of at most 2 in front of the column pass and the down-shifts between the passes
+// (fwd_txfm_shift_ls, transforms.h:27-45) no node of any of the 19 sizes exceeds 64 * 65,520 < 2^22; the cosine weights are < 2^14.  Any
+// 8- / 10-bit picture satisfies it; samples outside the bit depth (the reference accepts any uint16) take the 32-bit path.
+// The three-instruction butterflies (hbtf<2>) need every node of the pass below 2^17: N x the largest input of the pass (measured over the wave).
+__device__ __forceinline__ bool pass_fits_17_bits(uint32_t wave_max_abs_input, int n) { return (unsigned long long)wave_max_abs_input * (unsigned)n < (1u << 17); }
+template <int N, int CLAMP, int IM> __device__ __forceinline__ void inv_1d(int32_t *x, int type) {
+    const int32_t *c = c_cospi[2]; // INV_COS_BIT = 12
+    if (type == 3) identity<N>(x);
+    else if (type == 0) { permute_brev<N>(x); idct_core<N, CLAMP, IM>(x, c, 12); }
+    else if constexpr (N == 4) adst4(x, 12, true);
+    else if constexpr (N <= 16) iadst<N, CLAMP, IM>(x, c, 12);
+}
+// every node of an inverse pass is a sum of at most N pass inputs with weights of magnitude <= 1 (the stage clamps only shrink it): below 2^18
+// when N x the largest |input| is
+__device__ __forceinline__ bool ipass_fits_18_bits(uint32_t wave_max_abs_input, int n) { return (unsigned long long)wave_max_abs_input * (unsigned)n < (1u << 18); }
+// largest magnitude of a vector: the largest and the smallest element are tracked instead (one v_max3_i32 / v_min3_i32 per PAIR of elements
+// each; |x| first would be two instructions per element before the max)
+struct HiLo {
+    int32_t hi = 0, lo = 0;
+    __device__ __forceinline__ void take(int32_t a, int32_t b) { hi = max(max(hi, a), b); lo = min(min(lo, a), b); }
+    __device__ __forceinline__ void take(int32_t a) { hi = max(hi, a); lo = min(lo, a); }
+    __device__ __forceinline__ uint32_t max_abs() const { return (uint32_t)max(hi, -lo); }
+};
+template <int N> __device__ __forceinline__ uint32_t vec_max_abs(const int32_t *x) {
+    HiLo m;
+    if constexpr (N % 2 == 0) {
+#pragma unroll
+        for (int i = 0; i < N; i += 2) m.take(x[i], x[i + 1]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i++) m.take(x[i]);
+    }
+    return m.max_abs();
+}
+// SAFE32: the caller knows |x| < 2^30 (a pass that took the bounded butterflies, or an inverse pass, whose outputs are clamped to <= 18 bits):
+// the rounding add cannot wrap and the reference's 64-bit round_shift is the same two 32-bit instructions
+template <int N, bool SAFE32 = false> __device__ __forceinline__ void shift_vec(int32_t *x, int sh) { // svt_av1_round_shift_array_c(x, N, -sh)
+    if (sh < 0) {
+#pragma unroll
+        for (int i = 0; i < N; i++) x[i] = SAFE32 ? ((x[i] + (1 << (-sh - 1))) >> -sh) : rshift64(x[i], -sh);
+    } else if (sh > 0) {
+#pragma unroll
+        for (int i = 0; i < N; i++) x[i] = (int32_t)((uint32_t)x[i] << sh);
+    }
+}
+
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+    return v;
+}
+
+} // namespace
+#endif

@@ -1,0 +1,93 @@
+"""Host-side helpers for the TPL dispenser (svt_hip_tpl_dispense, include/svt_hip_tpl.h): descriptor construction from a case
+(tests/tpl_dispenser_cases.py layout: padded numpy planes, ME arrays, controls) and torch-backed runners.  torch is plumbing here;
+the compute is in libsvthip.so."""
+import ctypes as C
+
+import numpy as np
+
+from . import abi, api
+
+
+def _lib():
+    L = api.lib()
+    L.svt_hip_tpl_desc_size.restype = C.c_size_t
+    return L
+
+
+def desc_size():
+    return _lib().svt_hip_tpl_desc_size()
+
+
+def plane(ptr, buf, pad, width, height):
+    return abi.PlaneDesc(buffer_y=ptr, stride_y=buf.shape[1], org_x=pad, org_y=pad, width=width, height=height)
+
+
+def make_desc(case, pad, cur, recon, refs, me, tpl_stats, tpl_src_stats):
+    """SvtHipTplDesc of a case (level 4 / 5 controls: SAD search, DC_PRED, FULL_PEL = 3, no rate); cur / recon / refs[(l, r)] = (src_ptr, recon_ptr) / me = (total, mv, cand) / outputs: pointers."""
+    c = case
+    d = abi.TplDesc(aligned_width=c["aligned_width"], aligned_height=c["aligned_height"], n_pu=c["n_pu"], max_cand=c["max_cand"],
+                    max_refs=c["max_refs"], max_l0=c["max_l0"], enable_me_16x16=c["enable_me_16x16"], dispenser_search_level=c["level"],
+                    subsample_tx=c["sub"], pf_shape=c["pf"], synth_blk_size=c["synth"], disable_intra_pred=c["disable_intra_pred"], is_ref=c["is_ref"],
+                    slice_is_i=c["slice_is_i"], tpl_slice_is_i=c["tpl_slice_is_i"], src_pass=c["src_pass"], store_src_stats=c["store_src_stats"],
+                    use_sad_in_src_search=1, intra_mode_end=0, subpel_depth=3, compute_rate=0, in_loop_ois=1,
+                    n_tpl_stats=len(c["tpl_stats"]), n_tpl_src_stats=len(c["tpl_src_stats"]))
+    d.cur = plane(cur, c["cur"], pad, c["width"], c["height"])
+    d.recon = plane(recon, c["recon"], pad, c["recon_width"], c["recon_height"])
+    for (lst, ref), r in c["refs"].items():
+        e = d.refs[lst][ref]
+        e.src = plane(refs[(lst, ref)][0], r["src"], pad, c["width"], c["height"])
+        e.recon = plane(refs[(lst, ref)][1], r["recon"], pad, c["width"], c["height"])
+        e.picture_number, e.max_width, e.max_height, e.usable = r["poc"], r["max_width"], r["max_height"], r["usable"]
+    if me is not None:
+        d.me.total_me_candidate_index, d.me.me_mv_array, d.me.me_candidate_array = me
+    for i, f in enumerate(abi.QUANT_ROW_DTYPE):
+        getattr(d.quant, f[0])[:] = c["quant"][f[0]]
+    d.tpl_stats, d.tpl_src_stats = tpl_stats, tpl_src_stats
+    return d
+
+
+def check_desc(d):
+    """svt_hip_tpl_check_desc: raises api.SvtHipError when the descriptor is refused."""
+    L = _lib()
+    rc = L.svt_hip_tpl_check_desc(C.byref(d))
+    if rc:
+        raise api.SvtHipError(f"svt_hip_tpl_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+
+
+def upload_case(case):
+    """Device copies of a case's inputs and outputs (torch uint8 tensors), keyed like the case."""
+    import torch
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    t = dict(cur=dev(case["cur"]), recon=dev(case["recon"]), tpl_stats=dev(case["tpl_stats"]), tpl_src_stats=dev(case["tpl_src_stats"]),
+             refs={k: (dev(r["src"]), dev(r["recon"])) for k, r in case["refs"].items()})
+    me = case["me"]
+    t["me"] = (dev(me["total"]), dev(me["mv"]), dev(me["cand"])) if not case["slice_is_i"] else None
+    return t
+
+
+def dispense_dev(ctx, case, t, pad, me_ptrs=None, recon_ptr=None, ref_ptrs=None):
+    """Enqueues svt_hip_tpl_dispense on the device tensors `t` (upload_case layout); me_ptrs / recon_ptr / ref_ptrs override the ME
+    result pointers, the recon plane and the (src, recon) planes of references with device buffers the caller already holds."""
+    me = me_ptrs if me_ptrs is not None else (tuple(x.data_ptr() for x in t["me"]) if t["me"] is not None else None)
+    refs = {k: (v[0].data_ptr(), v[1].data_ptr()) for k, v in t["refs"].items()}
+    if ref_ptrs:
+        refs.update(ref_ptrs)
+    d = make_desc(case, pad, t["cur"].data_ptr(), recon_ptr if recon_ptr is not None else t["recon"].data_ptr(), refs, me,
+                  t["tpl_stats"].data_ptr(), t["tpl_src_stats"].data_ptr())
+    ctx.check(_lib().svt_hip_tpl_dispense(ctx._h, C.byref(d)), "svt_hip_tpl_dispense")
+    return d
+
+
+def download(case, t):
+    return (t["tpl_stats"].cpu().numpy().view(abi.TPL_STATS_DTYPE).copy(), t["tpl_src_stats"].cpu().numpy().view(abi.TPL_SRC_STATS_DTYPE).copy(),
+            t["recon"].cpu().numpy().reshape(case["recon"].shape).copy())
+
+
+def run_tpl_hip(ctx, case, pad):
+    """Uploads the case, dispenses it, returns (tpl_stats grid, tpl_src_stats, padded recon plane) as numpy arrays."""
+    import torch
+    t = upload_case(case)
+    torch.cuda.synchronize()
+    dispense_dev(ctx, case, t, pad)
+    ctx.sync()
+    return download(case, t)

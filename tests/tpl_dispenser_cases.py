@@ -1,0 +1,384 @@
+"""A readable restatement of the TPL dispenser for levels 4 and 5 (SAD source search, DC-only intra, full-pel, no rate):
+tpl_mc_flow_dispenser_sb_generic (Source/Lib/Codec/src_ops_process.c:519-1200) called for every b64 in raster order,
+result_model_store (:266-340) and svt_aom_generate_padding of the recon picture (Codec/pic_operators.c:397-443).  The control
+flow, neighbour fills, DC prediction, SADs, MV clamp, arg-min, grid writes and padding are restated here; the transform /
+quantizer / inverse-reconstruction arithmetic is the oracle's RD batch (pyoracle.rd_batch, quant_kind 2, the TPL tx_size table of
+tests/tpl_cases.py), whose equality with the reference's chain tests/test_tpl_chain.py checks.
+
+Also the seeded cases (pictures, references, candidate lists, MVs) shared by the CPU and GPU tests.  A case is a dict of numpy
+arrays and numbers; planes are padded uint8 arrays with the sample (x, y) at [PAD + y, PAD + x]."""
+import numpy as np
+
+import pyoracle
+from svt_av1_psyex_amd import abi, rd
+from tpl_cases import TPL_TX_SIZE
+
+PAD = 40          # padding of every plane of the cases (>= TPL_PADX / TPL_PADY = 32)
+TPL_PADX = 32
+NEWMV, DC_PRED = 16, 0
+INT64_MAX = (1 << 63) - 1
+# tpl_blk_idx_tab (:353-355): z-order of the blocks of a b64 -> the ME's raster PU index
+ME_IDX = {16: [5, 6, 9, 10, 7, 8, 11, 12, 13, 14, 17, 18, 15, 16, 19, 20], 32: [1, 2, 3, 4]}
+
+
+def wrap16(v):
+    return ((int(v) + 0x8000) & 0xFFFF) - 0x8000
+
+
+def blocks_in_order(case):
+    """(x, y, b64_index, me_index) of every block in the reference's order: b64s in raster order, blocks in z-order."""
+    S = 16 << case["level"]
+    nb64x, nb64y = (case["aligned_width"] + 63) // 64, (case["aligned_height"] + 63) // 64
+    for b64 in range(nb64x * nb64y):
+        ox, oy = (b64 % nb64x) * 64, (b64 // nb64x) * 64
+        for me in ME_IDX[S]:
+            if S == 16:
+                lx, ly = (me - 5) % 4, (me - 5) // 4
+            else:
+                lx, ly = (me - 1) % 2, (me - 1) // 2
+            yield ox + lx * S, oy + ly * S, b64, me
+
+
+def at(plane, x, y):
+    return int(plane[PAD + y, PAD + x])
+
+
+def block(plane, x, y, S):
+    return plane[PAD + y:PAD + y + S, PAD + x:PAD + x + S]
+
+
+def neighbours_open_loop(plane, x, y, bw, bh, width, height):
+    """svt_aom_update_neighbor_samples_array_open_loop_mb{,_recon} with use_top_righ_bottom_left = update_top_neighbor = 1
+    (Codec/enc_intra_prediction.c:1127-1290): returns (above[0..2bw), left[0..2bh)), the samples after the top-left one."""
+    nw, nh = 2 * bw, 2 * bh
+    above = [127] * (nw + 1)
+    left = [129] * (nh + 1)
+    above[0] = left[0] = at(plane, x - 1, y - 1) if (x != 0 and y != 0) else 128
+    li = 1  # left_ref pointer (index into left)
+    count = nw
+    if x != 0:
+        if y == 0:
+            left[li - 1] = at(plane, x - 1, y)
+        count = count - ((y + count) - height) if (y + count) > height else count
+        for i in range(count):
+            left[li + i] = at(plane, x - 1, y + i)
+        li += count + (nw - count)
+        for i in range(bh):
+            left[li - bh + i] = left[li - bh - 1]
+    elif y != 0:
+        count = count - ((y + count) - height) if (y + count) > height else count
+        v = at(plane, x, y - 1)
+        for i in range(count + 1):
+            left[li - 1 + i] = v
+        above[0] = v
+    else:
+        li += count
+    count = nw
+    if y != 0:
+        count = count - ((x + count) - width) if (x + count) > width else count
+        for i in range(count):
+            above[1 + i] = at(plane, x + i, y - 1)
+        if x != 0:
+            for i in range(bw):
+                above[1 + bw + i] = above[1 + bw - 1]
+    elif x != 0:
+        count = count - ((x + count) - width) if (x + count) > width else count
+        v = left[li - count]
+        for i in range(count + 1):
+            above[i] = v
+    return above[1:], left[1:]
+
+
+def dc_pred(plane, x, y, S, width, height):
+    """The DC predictor of the dispenser (:624-659, :1054-1087): get_neighbor_samples_dc for blocks inside the picture that are
+    not on its top row or left column, the open-loop fill otherwise; svt_aom_dc_pred[x > 0][y > 0]."""
+    inside = x + S <= width and y + S <= height
+    if x > 0 and y > 0 and inside:
+        above = [at(plane, x + i, y - 1) for i in range(S)]
+        left = [at(plane, x - 1, y + i) for i in range(S)]
+    else:
+        above, left = neighbours_open_loop(plane, x, y, S, S, width, height)
+    if x > 0 and y > 0:
+        return (sum(above[:S]) + sum(left[:S]) + S) // (2 * S)
+    if x > 0:
+        return (sum(left[:S]) + S // 2) // S
+    if y > 0:
+        return (sum(above[:S]) + S // 2) // S
+    return 128
+
+
+def chain(case, src_tile, pred_tile):
+    """subtract -> svt_av1_wht_fwd_txfm (pf_shape, rows every 1 << subsample_tx) -> get_quantize_error -> inverse: (recon_error, eob,
+    the reconstruction of the transformed rows over pred_tile) as pyoracle.rd_batch computes them."""
+    S, sub, level = src_tile.shape[0], case["sub"], case["level"]
+    ts = TPL_TX_SIZE[level][sub]
+    fields = dict(bit_depth=8, quant_kind=2, tx_size=ts, src_stride=S << sub, pred_stride=S << sub)
+    jobs = np.zeros(1, dtype=abi.JOB_DTYPE)
+    jobs["pf_shape"] = case["pf"]
+    out = pyoracle.rd_batch(fields, np.ascontiguousarray(src_tile), np.ascontiguousarray(pred_tile), jobs, case["quant"][None], want_coeffs=False)
+    shift = 0 if ts == 3 else 2
+    return max(int(out["dist_coeff"][0, 0]) >> shift, 1), int(out["eob"][0, 0]), out["recon"]
+
+
+def result_model_store(case, grid, st, x, y, S):
+    st = dict(st)
+    for k in ("srcrf_dist", "recrf_dist", "srcrf_rate", "recrf_rate"):
+        st[k] = max(1, st[k])
+    G, aw = case["synth"], case["aligned_width"]
+    stride = (aw + G - 1) // G
+    base = (y // G) * stride + (x // G)
+    cells = [base]
+    if G == 16 and S == 32:
+        for k in ("srcrf_dist", "recrf_dist", "srcrf_rate", "recrf_rate"):
+            st[k] = max(1, st[k] // 4)
+        cells = [base, base + 1, base + stride, base + stride + 1]
+    for c in cells:
+        if c < len(grid):  # the grid's allocation ends here (the reference would write on)
+            for k, v in st.items():
+                grid[c][k] = v
+
+
+def generate_padding(buf, width, height, org_x, org_y):
+    for y in range(org_y, org_y + height):
+        buf[y, :org_x] = buf[y, org_x]
+        buf[y, org_x + width:2 * org_x + width] = buf[y, org_x + width - 1]
+    for k in range(org_y):
+        buf[org_y - 1 - k, :] = buf[org_y, :]
+        buf[org_y + height + k, :] = buf[org_y + height - 1, :]
+
+
+def restate(case):
+    """Returns (tpl_stats grid, tpl_src_stats, padded recon) after one dispense of the case (its arrays are not modified)."""
+    S = 16 << case["level"]
+    sub, step = case["sub"], 1 << case["sub"]
+    W, H = case["width"], case["height"]
+    cur = case["cur"]
+    rec = case["recon"].copy()
+    grid = case["tpl_stats"].copy()
+    srcst = case["tpl_src_stats"].copy()
+    a16w = (case["aligned_width"] + 15) >> 4
+    me = case["me"]
+    n_pu, max_cand, max_refs, max_l0 = case["n_pu"], case["max_cand"], case["max_refs"], case["max_l0"]
+    for x, y, b64, me_idx in blocks_in_order(case):
+        if x + S // 2 > W or y + S // 2 > H:
+            continue
+        mbo = me_idx if case["enable_me_16x16"] else (me_idx - 1) // 4
+        st = dict(srcrf_dist=0, recrf_dist=0, srcrf_rate=0, recrf_rate=0, mc_dep_rate=0, mc_dep_dist=0, mv_row=0, mv_col=0, ref_frame_poc=0)
+        best_mv, best_rf, best_poc, best_mode = (0, 0), -1, 0, DC_PRED
+        si = (y >> 4) * a16w + (x >> 4)
+        if case["src_pass"]:
+            best_inter = best_intra = INT64_MAX
+            if not case["disable_intra_pred"]:
+                dc = dc_pred(cur, x, y, S, W, H)
+                best_intra = int(np.abs(block(cur, x, y, S).astype(np.int32) - dc).sum())
+            n = 0 if case["slice_is_i"] else int(me["total"][b64 * n_pu + mbo])
+            for ci in range(n):
+                cand = int(me["cand"][(b64 * n_pu + mbo) * max_cand + ci])
+                direction = cand & 3
+                if direction > 1:
+                    continue
+                lst = direction
+                ref = (cand >> 2) & 3 if lst == 0 else (cand >> 4) & 3
+                r = case["refs"].get((lst, ref))
+                if r is None or not r["usable"]:
+                    continue
+                mv = int(me["mv"][(b64 * n_pu + mbo) * max_refs + (max_l0 if lst else 0) + ref])
+                mx, my = wrap16(wrap16(mv & 0xFFFF) << 3), wrap16(wrap16(mv >> 16) << 3)
+                if x + (mx >> 3) < -TPL_PADX:
+                    mx = wrap16((-TPL_PADX - x) << 3)
+                if x + S + (mx >> 3) > TPL_PADX + r["max_width"] - 1:
+                    mx = wrap16(((TPL_PADX + r["max_width"] - 1) - (x + S)) << 3)
+                if y + (my >> 3) < -TPL_PADX:
+                    my = wrap16((-TPL_PADX - y) << 3)
+                if y + S + (my >> 3) > TPL_PADX + r["max_height"] - 1:
+                    my = wrap16(((TPL_PADX + r["max_height"] - 1) - (y + S)) << 3)
+                cost = int(np.abs(block(cur, x, y, S).astype(np.int32) - block(r["src"], x + (mx >> 3), y + (my >> 3), S)).sum())
+                if cost < best_inter:
+                    best_poc, best_rf, best_inter, best_mv = r["poc"], lst * 4 + ref, cost, (my, mx)
+            if best_inter < best_intra:
+                best_mode = NEWMV
+            if best_mode == NEWMV:
+                r = case["refs"][(best_rf >> 2, best_rf & 3)]
+                re, _, _ = chain(case, block(cur, x, y, S), block(r["src"], x + (best_mv[1] >> 3), y + (best_mv[0] >> 3), S))
+                st["srcrf_dist"] = (re << 4) << sub
+            if case["store_src_stats"]:
+                s = srcst[si]
+                s["srcrf_dist"], s["srcrf_rate"], s["mv_row"], s["mv_col"] = st["srcrf_dist"], 0, best_mv[0], best_mv[1]
+                s["best_rf_idx"], s["ref_frame_poc"], s["best_mode"], s["best_intra_mode"] = best_rf, best_poc, best_mode, DC_PRED
+        else:
+            s = srcst[si]
+            st["srcrf_dist"], st["srcrf_rate"] = int(s["srcrf_dist"]), int(s["srcrf_rate"])
+            best_mv, best_rf, best_poc, best_mode = (int(s["mv_row"]), int(s["mv_col"])), int(s["best_rf_idx"]), int(s["ref_frame_poc"]), int(s["best_mode"])
+        # recon path (:979-1198)
+        if best_mode == NEWMV:
+            r = case["refs"][(best_rf >> 2, best_rf & 3)]
+            pred = block(r["recon"], x + (best_mv[1] >> 3), y + (best_mv[0] >> 3), S).copy()
+        else:
+            pred = np.full((S, S), dc_pred(rec, x, y, S, W, H), np.uint8)
+        re, eob, out = chain(case, block(cur, x, y, S), pred)
+        dst = block(rec, x, y, S)
+        dst[:] = pred
+        if (not case["disable_intra_pred"] or case["is_ref"]) and eob:
+            for i in range(0, S, step):
+                dst[i:i + step] = out[i]
+        st["recrf_dist"] = (re << 4) << sub
+        if best_mode != NEWMV:
+            st["srcrf_dist"], st["srcrf_rate"] = st["recrf_dist"], 0
+        st["recrf_dist"] = max(st["srcrf_dist"], st["recrf_dist"])
+        st["recrf_rate"] = max(st["srcrf_rate"], st["recrf_rate"])
+        if not case["tpl_slice_is_i"] and best_rf != -1:
+            st["mv_row"], st["mv_col"], st["ref_frame_poc"] = best_mv[0], best_mv[1], best_poc
+        result_model_store(case, grid, st, x, y, S)
+    generate_padding(rec, case["recon_width"], case["recon_height"], PAD, PAD)
+    return grid, srcst, rec
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+def padded(rng, W, H, base=None, amp=None):
+    """A padded picture: random (or base + noise) samples inside, edge-replicated padding (as the reference pads its inputs)."""
+    if base is None:
+        inner = rng.integers(0, 256, (H, W))
+        inner = (inner + np.roll(inner, 1, 0) + np.roll(inner, 1, 1) + np.roll(inner, (1, 1), (0, 1))) // 4  # some spatial correlation
+    else:
+        inner = base[PAD:PAD + H, PAD:PAD + W].astype(np.int32)
+        shift = (int(rng.integers(-3, 4)), int(rng.integers(-3, 4)))
+        inner = np.roll(inner, shift, (0, 1)) + rng.integers(-amp, amp + 1, inner.shape)
+    buf = np.zeros((H + 2 * PAD, W + 2 * PAD), np.uint8)
+    buf[PAD:PAD + H, PAD:PAD + W] = np.clip(inner, 0, 255)
+    generate_padding(buf, W, H, PAD, PAD)
+    return buf if base is None else (buf, shift)
+
+
+def make_case(seed, W, H, level=0, sub=0, pf=2, synth=16, disable_intra_pred=0, is_ref=1, slice_is_i=0, src_pass=1, store_src_stats=1,
+              unusable=(), enable_me_16x16=1, n_refs=(2, 1), amp=6, qstep=(40, 52), max_shrink=(0, 0)):
+    rng = np.random.default_rng(seed)
+    aw, ah = (W + 7) & ~7, (H + 7) & ~7
+    cur = padded(rng, W, H)
+    refs = {}
+    poc = 100
+    for lst in range(2):
+        for ref in range(n_refs[lst]):
+            src, shift = padded(rng, W, H, base=cur, amp=amp)
+            refs[(lst, ref)] = dict(src=src, shift=shift, recon=padded(rng, W, H, base=src, amp=3)[0], poc=poc + (lst * 8 + ref + 1) * (1 if lst else -1),
+                                    max_width=W - max_shrink[0], max_height=H - max_shrink[1], usable=int((lst, ref) not in unusable))
+    n_pu = abi.n_pu(enable_me_16x16, 0)
+    max_cand, max_refs, max_l0 = 23, 7, 4
+    n_b64 = ((aw + 63) // 64) * ((ah + 63) // 64)
+    total = rng.integers(0, 6, n_b64 * n_pu).astype(np.uint8)
+    cand = np.zeros(n_b64 * n_pu * max_cand, np.uint8)
+    for i in range(n_b64 * n_pu):
+        for c in range(max_cand):
+            d = int(rng.choice([0, 0, 1, 2])) if n_refs[1] else int(rng.choice([0, 0, 2]))
+            r0, r1 = int(rng.integers(0, n_refs[0])), int(rng.integers(0, max(n_refs[1], 1)))
+            cand[i * max_cand + c] = d | (r0 << 2) | (r1 << 4)
+    mvx = rng.integers(-12, 13, n_b64 * n_pu * max_refs)
+    mvy = rng.integers(-12, 13, n_b64 * n_pu * max_refs)
+    near = rng.random(mvx.shape) < 0.5  # half of the MVs close to the motion of the reference (a roll of the current picture)
+    slot = np.arange(mvx.size) % max_refs
+    for (lst, ref), r in refs.items():
+        sel = near & (slot == (max_l0 if lst else 0) + ref)
+        mvy = np.where(sel, r["shift"][0] + rng.integers(-1, 2, mvy.shape), mvy)
+        mvx = np.where(sel, r["shift"][1] + rng.integers(-1, 2, mvx.shape), mvx)
+    far = rng.random(mvx.shape) < 0.1  # some MVs far outside the picture: the clamp
+    mvx = np.where(far, rng.integers(-400, 400, mvx.shape), mvx)
+    mv = ((mvx & 0xFFFF) | ((mvy & 0xFFFF) << 16)).astype(np.uint32)
+    synth_cells = ((aw + synth - 1) // synth) * ((ah + synth - 1) // synth) + 8  # a few cells past the grid: writes there are dropped
+    tpl_stats = np.zeros(synth_cells, abi.TPL_STATS_DTYPE)
+    tpl_stats.view(np.uint8)[:] = 0xA5  # untouched cells keep this
+    a16 = ((aw + 15) // 16) * ((ah + 15) // 16)
+    src_stats = np.zeros(a16, abi.TPL_SRC_STATS_DTYPE)
+    recon = (np.arange((H + 2 * PAD) * (W + 2 * PAD)) * 37 % 251).astype(np.uint8).reshape(H + 2 * PAD, W + 2 * PAD)  # a known pattern
+    return dict(width=W, height=H, aligned_width=aw, aligned_height=ah, cur=cur, recon=recon, recon_width=W, recon_height=H, refs=refs,
+                me=dict(total=total, cand=cand, mv=mv), n_pu=n_pu, max_cand=max_cand, max_refs=max_refs, max_l0=max_l0,
+                enable_me_16x16=enable_me_16x16, level=level, sub=sub, pf=pf, synth=synth, disable_intra_pred=disable_intra_pred, is_ref=is_ref,
+                slice_is_i=slice_is_i, tpl_slice_is_i=slice_is_i, src_pass=src_pass, store_src_stats=store_src_stats,
+                quant=rd.quant_row_from_step(*qstep), tpl_stats=tpl_stats, tpl_src_stats=src_stats)
+
+
+def seeded_grid():
+    """The axes of the dispenser: level 4 (16x16, subsample_tx 0) / level 5 (32x32, subsample_tx 2), synth 16 / 32, intra on / off,
+    is_ref, an I-slice picture, a stored-stats (src_pass 0) picture, an unusable reference, sizes that leave blocks half inside or out."""
+    cases = []
+    i = 0
+    for level, sub in ((0, 0), (1, 2)):
+        for synth in (16, 32):
+            for dis in (0, 1):
+                for is_ref in (0, 1):
+                    cases.append((f"L{level}_s{synth}_dis{dis}_ref{is_ref}", dict(seed=10 + i, W=200, H=136, level=level, sub=sub, synth=synth,
+                                                                                 disable_intra_pred=dis, is_ref=is_ref)))
+                    i += 1
+    cases += [
+        ("islice_L0", dict(seed=50, W=168, H=120, level=0, sub=0, slice_is_i=1)),
+        ("islice_L1_s16", dict(seed=51, W=168, H=120, level=1, sub=2, synth=16, slice_is_i=1)),
+        ("unusable_ref", dict(seed=52, W=152, H=104, unusable=((0, 0),), disable_intra_pred=1)),
+        ("odd_size_L1", dict(seed=53, W=232, H=178, level=1, sub=2, synth=16)),  # 32-blocks half inside; aligned width 232 = 7.25 x 32
+        ("odd_size_L0_s32", dict(seed=54, W=210, H=150, level=0, synth=32)),
+        ("no16x16_L0", dict(seed=55, W=128, H=96, enable_me_16x16=0)),
+        ("sub1_pf0", dict(seed=56, W=128, H=96, level=0, sub=1, pf=0)),
+        ("pf1_L1_sub0", dict(seed=57, W=128, H=128, level=1, sub=0, pf=1, synth=32)),
+        ("max_size_below_picture", dict(seed=58, W=200, H=136, max_shrink=(40, 24), disable_intra_pred=1)),  # the clamp reads max_width / max_height
+        ("small_picture", dict(seed=59, W=40, H=24, n_refs=(1, 0))),
+    ]
+    return cases
+
+
+def src_pass0_case(seed=60, **kw):
+    """A case whose stored TplSrcStats come from a first dispense of the same picture (what tpl_src_data_ready reuses)."""
+    c = make_case(seed, **kw)
+    _, srcst, _ = restate(c)
+    c2 = dict(c)
+    c2["tpl_src_stats"] = srcst
+    c2["src_pass"], c2["store_src_stats"] = 0, 0
+    return c2
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The reference fixture (tools/gen_tpl_golden.py): the cases it was made from and the checksum that pins their inputs
+import hashlib  # noqa: E402
+import os  # noqa: E402
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tpl_dispenser.npz")
+FIXTURE_CASES = [
+    ("L4_s16", dict(seed=200, W=136, H=104)),
+    ("L4_s32_intra_off_nonref", dict(seed=201, W=136, H=104, synth=32, disable_intra_pred=1, is_ref=0)),
+    ("L4_intra_off_ref", dict(seed=202, W=136, H=104, disable_intra_pred=1, is_ref=1)),
+    ("L4_nonref", dict(seed=203, W=136, H=104, is_ref=0)),
+    ("L5_s32", dict(seed=204, W=136, H=104, level=1, sub=2, synth=32)),
+    ("L5_s16_intra_off", dict(seed=205, W=136, H=104, level=1, sub=2, synth=16, disable_intra_pred=1)),
+    ("islice", dict(seed=206, W=120, H=88, slice_is_i=1)),
+    ("unusable_ref", dict(seed=207, W=120, H=88, unusable=((0, 0),))),
+    ("odd_size_L5", dict(seed=208, W=150, H=98, level=1, sub=2, synth=16)),
+    ("odd_size_L4_s32", dict(seed=209, W=150, H=98, synth=32)),
+    ("max_size_below_picture", dict(seed=210, W=136, H=104, max_shrink=(40, 24), disable_intra_pred=1)),
+    ("no16x16", dict(seed=211, W=120, H=88, enable_me_16x16=0)),
+]
+
+
+def input_checksum(c):
+    """sha256 over every input array of a case (planes, candidate lists, MVs, the recon buffer's and the stored stats' initial contents)."""
+    h = hashlib.sha256()
+    arrays = [c["cur"], c["recon"], c["tpl_stats"], c["tpl_src_stats"], c["me"]["total"], c["me"]["cand"], c["me"]["mv"], c["quant"]]
+    for k in sorted(c["refs"]):
+        arrays += [c["refs"][k]["src"], c["refs"][k]["recon"]]
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).view(np.uint8).tobytes())
+    return np.frombuffer(h.digest(), np.uint8).copy()
+
+
+def fixture_cases(recon_of):
+    """(name, kwargs, case) of the fixture in order.  The stored-stats case reuses the TplSrcStats of the first case's picture; the
+    sliding-window pair's second picture takes the first one's TPL recon (recon_of(case): the fixture's, or the reference's while the
+    fixture is made) as its list-0 recon-path reference."""
+    for name, kw in FIXTURE_CASES:
+        yield name, kw, make_case(**kw)
+    kw = dict(seed=200, W=136, H=104)
+    first = make_case(**kw)
+    c = make_case(**kw)
+    c["tpl_src_stats"] = restate(first)[1]
+    c["src_pass"], c["store_src_stats"] = 0, 0
+    yield "src_pass0", kw, c
+    a = make_case(220, 136, 104, n_refs=(1, 0))
+    yield "window_picture_1", dict(seed=220), a
+    b = make_case(221, 136, 104, n_refs=(1, 0))
+    b["refs"][(0, 0)]["recon"] = recon_of(a)
+    yield "window_picture_2", dict(seed=221), b
