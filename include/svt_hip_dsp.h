@@ -91,7 +91,8 @@ typedef struct SvtHipFwdTxBatchDesc {
     uint32_t n_jobs;
     uint32_t residual_stride;    /* in samples */
     const int16_t     *residual; /* device pointers */
-    const SvtHipTxJob *jobs;     /* src_offset: the block in `residual`; tx_type; pf_shape 0 / 1 / 2 = full / _N2 / _N4 */
+    const SvtHipTxJob *jobs;     /* src_offset: the block in `residual`; tx_type; pf_shape 0 / 1 / 2 = full / _N2 / _N4, 3 = the DC coefficient alone
+                                  * (av1_estimate_transform_ONLY_DC, transforms.c:2925-2946); only its two low bits are read */
     int32_t           *coeff;    /* [n_jobs][W * H] */
 } SvtHipFwdTxBatchDesc;
 int svt_hip_fwd_txfm_batch(SvtHipContext *ctx, const SvtHipFwdTxBatchDesc *d);

@@ -118,10 +118,11 @@ def config_from_preset_ref(preset_desc):
 
 
 # ---- CPU mirrors of the batched device entries (same descriptors, host pointers): checkers for tests / smoke / bench baseline ----
-def rd_batch(desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, want_recon=True, qmatrix=None, iqmatrix=None, impl="oracle"):
+def rd_batch(desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, want_recon=True, qmatrix=None, iqmatrix=None, impl="oracle", recon_init=None):
     """CPU mirror of svt_hip_rd_batch on host numpy arrays (test infrastructure; imports oracle/).  impl: "oracle" = the C
     restatement (oracle/rd_oracle.c); "ref" / "ref_simd" = the reference's own `_c` / AVX2+SSE4.1 kernels chained by
-    oracle/ref_harness.c:ref_rd_batch (build container, or wherever oracle/_ref/libsvtref.so travelled to)."""
+    oracle/ref_harness.c:ref_rd_batch (build container, or wherever oracle/_ref/libsvtref.so travelled to).  recon_init: the recon plane before
+    the call (None = a copy of pred)."""
     if impl == "oracle":
         fn = load_oracle().orc_rd_batch
     else:
@@ -135,7 +136,7 @@ def rd_batch(desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, want_re
     if want_coeffs:
         for name in ("coeff", "qcoeff", "dqcoeff"):
             out[name] = np.zeros((n, npk), np.int32)
-    recon = pred.copy() if want_recon else None
+    recon = (pred.copy() if recon_init is None else np.array(recon_init, pred.dtype).reshape(pred.shape)) if want_recon else None
     d = abi.RdBatchDesc(n_jobs=n, src=src.ctypes.data, pred=pred.ctypes.data, recon=recon.ctypes.data if want_recon else None,
                         jobs=jobs.ctypes.data, quant_rows=quant_rows.ctypes.data, n_quant_rows=len(quant_rows), **desc_fields)
     for name in out:

@@ -91,4 +91,14 @@ int orc_rd_batch(const SvtHipRdBatchDesc *d) {
     free(res); free(co); free(q); free(dq); free(p16); free(r16);
     return 0;
 }
-size_t orc_sizeof_dsp(int what) { return what == 0 ? sizeof(SvtHipRdBatchDesc) : what == 1 ? sizeof(SvtHipTxJob) : sizeof(SvtHipQuantRow); }
+/* sizes of the descriptors as compiled: 0 SvtHipRdBatchDesc, 1 SvtHipTxJob, 2 SvtHipQuantRow, 3 SvtHipFwdTxBatchDesc, 4 SvtHipInvTxBatchDesc */
+size_t orc_sizeof_dsp(int what) {
+    switch (what) {
+    case 0: return sizeof(SvtHipRdBatchDesc);
+    case 1: return sizeof(SvtHipTxJob);
+    case 2: return sizeof(SvtHipQuantRow);
+    case 3: return sizeof(SvtHipFwdTxBatchDesc);
+    case 4: return sizeof(SvtHipInvTxBatchDesc);
+    default: return 0;
+    }
+}

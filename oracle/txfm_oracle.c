@@ -342,15 +342,14 @@ void orc_fwd_txfm2d(const int16_t *input, int32_t *output, uint32_t stride, int 
     free(buf);
 }
 
-/* svt_av1_inv_txfm2d_add_{WxH}_c: `input` holds min(W,32) x min(H,32) coefficients (the reference's packed
- * layout for 64-point sizes); recon = clip(pred + residual) in `bd` bits, read and written as uint16. */
-void orc_inv_txfm2d_add(const int32_t *input, const uint16_t *out_r, int32_t stride_r, uint16_t *out_w, int32_t stride_w, int tx_type,
-                        int tx_size, int bd) {
+/* The row pass of svt_av1_inv_txfm2d_add_{WxH}_c: buf (W x H, row-major) = the shifted row outputs, i.e. the column pass's inputs
+ * before its clamp.  Exported (orc_inv_txfm2d_rows) for tests that aim at the magnitude of the column pass's input. */
+static void inv_rows(const int32_t *input, int32_t *buf, int tx_type, int tx_size, int bd) {
     const int W = k_tx_w[tx_size], H = k_tx_h[tx_size], Wp = W > 32 ? 32 : W, Hp = H > 32 ? 32 : H;
-    const int vt = k_vtx[tx_type], ht = k_htx[tx_type], ud = (vt == 2), lr = (ht == 2);
-    const int row_clamp = bd == 8 ? 16 : (bd == 10 ? 18 : 20), col_clamp = bd == 12 ? 18 : 16; /* svt_av1_gen_inv_stage_range */
+    const int ht = k_htx[tx_type];
+    const int row_clamp = bd == 8 ? 16 : (bd == 10 ? 18 : 20); /* svt_av1_gen_inv_stage_range */
     const int rect = (W == 2 * H || H == 2 * W);
-    int32_t *buf = (int32_t *)calloc((size_t)W * H, sizeof(int32_t)), tin[64], tout[64];
+    int32_t tin[64];
     for (int r = 0; r < H; r++) {
         for (int c = 0; c < W; c++) {
             const int32_t v = (r < Hp && c < Wp) ? input[r * Wp + c] : 0;
@@ -360,6 +359,18 @@ void orc_inv_txfm2d_add(const int32_t *input, const uint16_t *out_r, int32_t str
         inv_1d(tin, buf + r * W, W, ht, 12, row_clamp);
         shift_arr(buf + r * W, W, k_inv_shift0[tx_size]);
     }
+}
+void orc_inv_txfm2d_rows(const int32_t *input, int32_t *buf, int tx_type, int tx_size, int bd) { inv_rows(input, buf, tx_type, tx_size, bd); }
+
+/* svt_av1_inv_txfm2d_add_{WxH}_c: `input` holds min(W,32) x min(H,32) coefficients (the reference's packed
+ * layout for 64-point sizes); recon = clip(pred + residual) in `bd` bits, read and written as uint16. */
+void orc_inv_txfm2d_add(const int32_t *input, const uint16_t *out_r, int32_t stride_r, uint16_t *out_w, int32_t stride_w, int tx_type,
+                        int tx_size, int bd) {
+    const int W = k_tx_w[tx_size], H = k_tx_h[tx_size];
+    const int vt = k_vtx[tx_type], ht = k_htx[tx_type], ud = (vt == 2), lr = (ht == 2);
+    const int col_clamp = bd == 12 ? 18 : 16; /* svt_av1_gen_inv_stage_range */
+    int32_t *buf = (int32_t *)calloc((size_t)W * H, sizeof(int32_t)), tin[64], tout[64];
+    inv_rows(input, buf, tx_type, tx_size, bd);
     for (int c = 0; c < W; c++) {
         for (int r = 0; r < H; r++) tin[r] = clampv(buf[r * W + (lr ? W - 1 - c : c)], bd + 6 > 16 ? bd + 6 : 16);
         inv_1d(tin, tout, H, vt, 12, col_clamp);

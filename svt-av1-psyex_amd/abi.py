@@ -103,6 +103,12 @@ class InvTxBatchDesc(C.Structure):
                 ("dqcoeff", C.c_void_p)]
 
 
+class FwdTxBatchDesc(C.Structure):
+    """SvtHipFwdTxBatchDesc (include/svt_hip_dsp.h)."""
+    _fields_ = [("tx_size", C.c_uint8), ("reserved", C.c_uint8 * 3), ("n_jobs", C.c_uint32), ("residual_stride", C.c_uint32), ("residual", C.c_void_p),
+                ("jobs", C.c_void_p), ("coeff", C.c_void_p)]
+
+
 class PredJob(C.Structure):
     """SvtHipPredJob (include/svt_hip_dsp.h)."""
     _fields_ = [("ref", C.c_void_p), ("sb_best_mv", C.c_void_p), ("pred", C.c_void_p), ("b64_row_start", C.c_uint32), ("b64_row_count", C.c_uint32),

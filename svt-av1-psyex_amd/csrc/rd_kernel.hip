@@ -205,11 +205,13 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     int32_t *dq_out = (p.d.dqcoeff && valid) ? p.d.dqcoeff + (size_t)job * NP : nullptr;
     const int32_t zb_c[2]  = {log_scale ? ((q.zbin[0] + (1 << (log_scale - 1))) >> log_scale) : q.zbin[0], log_scale ? ((q.zbin[1] + (1 << (log_scale - 1))) >> log_scale) : q.zbin[1]};
     const int32_t rnd_c[2] = {log_scale ? ((q.round[0] + (1 << (log_scale - 1))) >> log_scale) : q.round[0], log_scale ? ((q.round[1] + (1 << (log_scale - 1))) >> log_scale) : q.round[1]};
-    // The common case as a loop of its own (wave-uniform test): "b" quantizer, flat matrix, every coefficient of the wave below 2^16, the whole
+    // The common case as a loop of its own: "b" quantizer, flat matrix, every coefficient of the wave below 2^16, the whole
     // block kept, nothing but the quantized coefficients asked for.  A lane's first coefficient may be the DC one (its constants are
     // selected per lane); all later ones are AC, whose constants stay in scalar registers.  Every product has 24-bit operands (see the
     // general loop below), |coeff - dqcoeff| <= max(|coeff|, dequant) < 2^16: the squares are exact in 32 bits.
-    const bool fast_q = q24 && !qm && p.d.quant_kind == 0 && !co_out && !dq_out && __all(pf == 0); // (co_out / dq_out: null for every job or none)
+    // Not always wave-uniform: in a partial last wave with coeff or dqcoeff requested, the lanes of the missing blocks (null co_out / dq_out)
+    // take this loop while the wave's real blocks take the general one.  Both loops are exact and the missing blocks store nothing.
+    const bool fast_q = q24 && !qm && p.d.quant_kind == 0 && !co_out && !dq_out && __all(pf == 0);
     if (fast_q) {
         static_assert(NP % LW == 0, "every lane of a block walks the same number of coefficients");
         // The scan positions of a lane's first kScanAhead coefficients (the low frequencies: where the non-zero levels are) are fetched ahead,

@@ -38,19 +38,32 @@ def grid_jobs(width, height, stride, tx_size, tx_type=0, quant_row=0, org=0):
     return jobs
 
 
-def run_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, want_recon=True, qmatrix=None, iqmatrix=None):
-    """Runs svt_hip_rd_batch on device copies of the inputs; returns numpy results."""
+OPTIONAL_OUTPUTS = ("coeff", "qcoeff", "dqcoeff", "cul_level", "recon")  # eob .. sse are mandatory
+
+
+def run_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, want_recon=True, qmatrix=None, iqmatrix=None, outputs=None,
+            spare_jobs=0, fill=0, recon_init=None):
+    """Runs svt_hip_rd_batch on device copies of the inputs; returns numpy results.
+    outputs: the optional outputs to request, a subset of OPTIONAL_OUTPUTS; None = cul_level plus what want_coeffs / want_recon select.
+    Every per-job output array gets `spare_jobs` slots past n_jobs; all of them start as the byte `fill` and come back whole.
+    recon_init: the recon plane's content before the call (same shape and dtype as pred); None = a copy of pred."""
     import torch
+    if outputs is None:
+        outputs = ("cul_level",) + (("coeff", "qcoeff", "dqcoeff") if want_coeffs else ()) + (("recon",) if want_recon else ())
+    unknown = set(outputs) - set(OPTIONAL_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown RD outputs {sorted(unknown)}")
     ts = desc_fields["tx_size"]
     npk = min(abi.TX_W[ts], 32) * min(abi.TX_H[ts], 32)
     n = len(jobs)
+    slots = n + spare_jobs
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
     t_src, t_pred, t_jobs, t_q = dev(src), dev(pred), dev(jobs), dev(quant_rows)
-    outs = {name: torch.zeros(n * k * np.dtype(dt).itemsize, dtype=torch.uint8, device="cuda") for name, dt, k in abi.RD_OUT_FIELDS}
-    if want_coeffs:
-        for name in ("coeff", "qcoeff", "dqcoeff"):
-            outs[name] = torch.zeros(n * npk * 4, dtype=torch.uint8, device="cuda")
-    t_rec = t_pred.clone() if want_recon else None
+    shapes = {name: (np.dtype(dt), k) for name, dt, k in abi.RD_OUT_FIELDS if name != "cul_level" or name in outputs}
+    shapes.update({name: (np.dtype(np.int32), npk) for name in ("coeff", "qcoeff", "dqcoeff") if name in outputs})
+    outs = {name: torch.full((slots * k * dt.itemsize,), fill, dtype=torch.uint8, device="cuda") for name, (dt, k) in shapes.items()}
+    want_recon = "recon" in outputs
+    t_rec = (t_pred.clone() if recon_init is None else dev(np.asarray(recon_init, pred.dtype).reshape(pred.shape))) if want_recon else None
     d = abi.RdBatchDesc(n_jobs=n, src=t_src.data_ptr(), pred=t_pred.data_ptr(), recon=t_rec.data_ptr() if want_recon else None,
                         jobs=t_jobs.data_ptr(), quant_rows=t_q.data_ptr(), n_quant_rows=len(quant_rows), **desc_fields)
     for name, t in outs.items():
@@ -61,12 +74,41 @@ def run_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, wan
     torch.cuda.synchronize()
     ctx.check(api.lib().svt_hip_rd_batch(ctx._h, C.byref(d)), "svt_hip_rd_batch")
     ctx.sync()
-    res = {}
-    for name, dt, k in abi.RD_OUT_FIELDS:
-        res[name] = outs[name].cpu().numpy().view(dt).reshape(n, k)
-    if want_coeffs:
-        for name in ("coeff", "qcoeff", "dqcoeff"):
-            res[name] = outs[name].cpu().numpy().view(np.int32).reshape(n, npk)
+    res = {name: outs[name].cpu().numpy().view(dt).reshape(slots, k) for name, (dt, k) in shapes.items()}
     if want_recon:
         res["recon"] = t_rec.cpu().numpy().view(pred.dtype).reshape(pred.shape)
     return res
+
+
+def run_fwd_hip(ctx, tx_size, residual, jobs, spare_jobs=0, fill=0):
+    """Runs svt_hip_fwd_txfm_batch on a device copy of the int16 residual plane (2-D, row stride = its width); returns the int32
+    coefficients [n_jobs + spare_jobs, W * H], every slot starting as the byte `fill`."""
+    import torch
+    residual = np.ascontiguousarray(residual, np.int16)
+    n, wh = len(jobs), abi.TX_W[tx_size] * abi.TX_H[tx_size]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
+    t_res, t_jobs = dev(residual), dev(jobs)
+    t_co = torch.full(((n + spare_jobs) * wh * 4,), fill, dtype=torch.uint8, device="cuda")
+    d = abi.FwdTxBatchDesc(tx_size=tx_size, n_jobs=n, residual_stride=residual.shape[1], residual=t_res.data_ptr(), jobs=t_jobs.data_ptr(),
+                           coeff=t_co.data_ptr())
+    torch.cuda.synchronize()
+    ctx.check(api.lib().svt_hip_fwd_txfm_batch(ctx._h, C.byref(d)), "svt_hip_fwd_txfm_batch")
+    ctx.sync()
+    return t_co.cpu().numpy().view(np.int32).reshape(n + spare_jobs, wh)
+
+
+def run_inv_hip(ctx, bit_depth, tx_size, pred, jobs, dqcoeff, recon=None):
+    """Runs svt_hip_inv_txfm_batch: pred and recon are 2-D planes of the same dtype (uint8: 8-bit only; uint16), each with its
+    own row stride; recon = None runs in place (the recon plane IS the prediction plane).  Returns the recon plane."""
+    import torch
+    pred = np.ascontiguousarray(pred)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    t_pred, t_co, t_jobs = dev(pred), dev(np.ascontiguousarray(dqcoeff, np.int32)), dev(jobs)
+    out = pred if recon is None else np.ascontiguousarray(recon, pred.dtype)
+    t_rec = t_pred if recon is None else dev(out)
+    d = abi.InvTxBatchDesc(bit_depth=bit_depth, sample_bytes=pred.dtype.itemsize, tx_size=tx_size, n_jobs=len(jobs), pred_stride=pred.shape[1],
+                           recon_stride=out.shape[1], pred=t_pred.data_ptr(), recon=t_rec.data_ptr(), jobs=t_jobs.data_ptr(), dqcoeff=t_co.data_ptr())
+    torch.cuda.synchronize()
+    ctx.check(api.lib().svt_hip_inv_txfm_batch(ctx._h, C.byref(d)), "svt_hip_inv_txfm_batch")
+    ctx.sync()
+    return t_rec.cpu().numpy().view(pred.dtype).reshape(out.shape)

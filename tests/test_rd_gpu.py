@@ -153,9 +153,14 @@ def test_leaf_inverse_transforms(hip_ctx, oracle, tx_size):
         L.svt_hip_leaf_bind(None)
 
 
-@pytest.mark.parametrize("tx_size,bd,sample_bytes", [(2, 10, 2), (3, 8, 1), (4, 10, 2), (9, 8, 2), (12, 10, 2), (0, 8, 1)])
+_INV_BATCH_CASES = [(2, 10, 2), (3, 8, 1), (4, 10, 2), (9, 8, 2), (12, 10, 2), (0, 8, 1)]
+_INV_BATCH_CASES += [c for ts in range(19) for c in ((ts, 8, 1), (ts, 10, 2)) if c not in _INV_BATCH_CASES]
+
+
+@pytest.mark.parametrize("tx_size,bd,sample_bytes", _INV_BATCH_CASES)
 def test_inverse_batch_matches_oracle(hip_ctx, oracle, tx_size, bd, sample_bytes):
-    """svt_hip_inv_txfm_batch: a plane's worth of blocks in one launch, read plane != write plane, uint8 and uint16 storage."""
+    """svt_hip_inv_txfm_batch: a plane's worth of blocks in one launch, read plane != write plane, uint8 and uint16 storage; all 19 sizes,
+    uint8 storage at 8 bits for every size."""
     import ctypes as C
     import torch
     from svt_av1_psyex_amd import abi, api, rd
@@ -176,17 +181,13 @@ def test_inverse_batch_matches_oracle(hip_ctx, oracle, tx_size, bd, sample_bytes
         off = int(jb["pred_offset"])
         oracle.orc_inv_txfm2d_add(C.c_void_p(co[j].ctypes.data), C.c_void_p(p16.ctypes.data + 2 * off), C.c_int32(PW), C.c_void_p(want.ctypes.data + 2 * off),
                                   C.c_int32(PW), int(jb["tx_type"]), tx_size, bd)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-    t_pred, t_co, t_jobs = dev(pred), dev(co), dev(jobs)
-    t_rec = torch.zeros(PH * PW * sample_bytes, dtype=torch.uint8, device="cuda")
-    d = abi.InvTxBatchDesc(bit_depth=bd, sample_bytes=sample_bytes, tx_size=tx_size, n_jobs=len(jobs), pred_stride=PW, recon_stride=PW, pred=t_pred.data_ptr(),
-                           recon=t_rec.data_ptr(), jobs=t_jobs.data_ptr(), dqcoeff=t_co.data_ptr())
-    torch.cuda.synchronize()
-    hip_ctx.check(api.lib().svt_hip_inv_txfm_batch(hip_ctx._h, C.byref(d)), "svt_hip_inv_txfm_batch")
-    hip_ctx.sync()
-    got = t_rec.cpu().numpy().view(dt).reshape(PH, PW)
+    got = rd.run_inv_hip(hip_ctx, bd, tx_size, pred, jobs, co, recon=np.zeros((PH, PW), dt))
     assert np.array_equal(got.astype(np.uint16), want)
-    d.sample_bytes = 1 if bd == 10 else 3
+    # the same descriptor with a storage size the bit depth does not allow is refused (real device buffers: nothing may launch on it)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    t_pred, t_rec, t_co, t_jobs = dev(pred), dev(np.zeros_like(pred)), dev(co), dev(jobs)
+    d = abi.InvTxBatchDesc(bit_depth=bd, sample_bytes=1 if bd == 10 else 3, tx_size=tx_size, n_jobs=len(jobs), pred_stride=PW, recon_stride=PW,
+                           pred=t_pred.data_ptr(), recon=t_rec.data_ptr(), jobs=t_jobs.data_ptr(), dqcoeff=t_co.data_ptr())
     assert api.lib().svt_hip_inv_txfm_batch(hip_ctx._h, C.byref(d)) == 2
 
 
