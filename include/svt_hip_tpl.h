@@ -108,6 +108,84 @@ int    svt_hip_tpl_dispense(SvtHipContext *ctx, const SvtHipTplDesc *d);
 int    svt_hip_tpl_check_desc(const SvtHipTplDesc *d);
 size_t svt_hip_tpl_desc_size(void); /* sizeof(SvtHipTplDesc) as compiled */
 
+/* ---- The TPL group: tpl_mc_flow (Source/Lib/Codec/src_ops_process.c:1783-1956) and svt_aom_generate_r0beta (:1585-1677) ----
+ *
+ * One call runs up to three stages over the window of a TPL group (frames in decode order, frames_in_sw <= 512), all on the context
+ * stream, asynchronously:
+ *   1. DISPENSE: tpl_mc_flow's frame loop.  For f = 0 .. n-1: the grid's first ceil(width / s) * ceil(height / s) cells are zeroed
+ *      (:1841-1845, s = synth_blk_size), then, when tpl_valid_pic, the dispenser runs on frame f's SvtHipTplDesc.
+ *   2. SYNTHESIZE: for f = n-1 .. 0 with tpl_valid_pic, tpl_mc_flow_synthesizer (:1571-1584, tpl_model_update{,_b} :1480-1565):
+ *      mc_dep_dist / mc_dep_rate of every cell of frame f propagated into the cells of the frame its ref_frame_poc names (the FIRST
+ *      frame of the window with that picture_number; none: nothing).  One launch per frame; the adds are 64-bit integer atomics, so
+ *      the grids are bit-exact whatever the order of arrival.
+ *   3. R0BETA: svt_aom_generate_r0beta + generate_lambda_scaling_factor (:176-223) for every frame that supplies outputs: r0 and
+ *      tpl_is_valid, one tpl_beta per superblock, one tpl_rdmult_scaling_factors entry per synth cell.  Running stage 3 alone on one
+ *      frame is how rate control asks for r0 / beta later (rc_process.c:3316-3319), e.g. after another group rewrote the grid.
+ *
+ * Reproduced as the reference has it:
+ *   - the synthesizer, generate_r0beta and generate_lambda_scaling_factor index the grid at row stride (mi_cols_sr >> shift), i.e.
+ *     floor(ceil(w / 16) / 2) with synth 32, while the dispenser writes at ceil(aligned_width / 32): when ceil(w / 16) is odd the last
+ *     column of a row reads the next row's first cell (e.g. 720x1280);
+ *   - the synthesizer bounds the quadrants by the reference picture's aligned size; generate_r0beta's picture sum runs over the aligned
+ *     rows and the unscaled columns (rounded up to 16), its per-superblock sums cut at the unscaled height rounded up to 16;
+ *   - GET_MV_RAWPEL rounding of the MV, round_floor, RDCOST, int64 wrap-around and C's truncating division;
+ *   - r0 is written only when mc_dep_cost_base != 0; otherwise it keeps its value, which beta then reads.
+ * Defined where the reference is not:
+ *   - a cell with recrf_dist == 0 propagates nothing.  The dispenser leaves such cells (blocks less than half inside, :578-580) at
+ *     zero with ref_frame_poc 0, so with picture 0 in the window the reference divides by zero there (SIGFPE on x86);
+ *   - a cell whose ref_frame_poc resolves to its own frame propagates nothing.  Every such cell the dispenser writes is intra
+ *     (recrf == srcrf, equal rates) and propagates zero in the reference, so this only removes a read / write race.
+ */
+#define SVT_HIP_TPL_MAX_GROUP 512 /* MAX_TPL_GROUP_SIZE */
+#define SVT_HIP_TPL_STAGE_DISPENSE   1u
+#define SVT_HIP_TPL_STAGE_SYNTHESIZE 2u
+#define SVT_HIP_TPL_STAGE_R0BETA     4u
+
+/* One frame of the window, in decode order.  Every buffer pointer is a DEVICE pointer; `dispense` is a host pointer. */
+typedef struct SvtHipTplGroupFrame {
+    uint64_t        picture_number;
+    uint8_t         tpl_valid_pic;  /* pcs->tpl_valid_pic[frame_idx] */
+    uint8_t         reserved[3];
+    int32_t         base_rdmult;    /* pa_me_data->base_rdmult (the host computes it from qIndex as :1372 does); read by stage 3 */
+    SvtHipTplStats *tpl_stats;      /* the frame's grid (pa_me_data->tpl_stats) */
+    uint32_t        n_tpl_stats;    /* cells it holds: >= ceil(width / s) * ceil(height / s) */
+    uint32_t        n_beta;         /* entries of beta: >= ceil(aligned_width / sb_size) * ceil(aligned_height / sb_size) */
+    /* stage 1: the dispenser of this frame, read when tpl_valid_pic (may be NULL otherwise); its tpl_stats must be this frame's grid,
+     * its aligned size and synth_blk_size the group's, its cur plane width x height */
+    const SvtHipTplDesc *dispense;
+    /* stage 3 outputs; all four NULL: the frame supplies none.  r0 is read as well (see above). */
+    double         *r0;
+    uint8_t        *tpl_is_valid;
+    double         *beta;           /* pa_me_data->tpl_beta, raster order of the superblocks */
+    double         *scaling;        /* pa_me_data->tpl_rdmult_scaling_factors */
+    uint32_t        n_scaling;      /* entries: >= ceil(mi_cols_sr / n) * ceil(mi_rows / n), n = s / 4, mi_cols_sr = ceil(width / 16) * 4 */
+    uint32_t        reserved2;
+} SvtHipTplGroupFrame;
+
+typedef struct SvtHipTplGroupDesc {
+    uint16_t width, height;                 /* enhanced_unscaled_pic (== enhanced_pic without super-res) */
+    uint16_t aligned_width, aligned_height; /* pcs->aligned_width / height: mi_cols / mi_rows = >> 2 */
+    uint8_t  synth_blk_size;                /* 16 or 32 */
+    uint8_t  sb_size;                       /* scs->sb_size: 64 or 128 */
+    uint8_t  compute_rate;                  /* must be 0: delta_rate_cost's log / pow are not reproduced bit for bit on the device */
+    uint8_t  superres_denom;                /* must be 8 (SCALE_NUMERATOR: no super-res / resize) */
+    uint32_t stages;                        /* SVT_HIP_TPL_STAGE_* */
+    uint32_t n_frames;                      /* 1 .. SVT_HIP_TPL_MAX_GROUP */
+    const SvtHipTplGroupFrame *frames;      /* host array of n_frames */
+} SvtHipTplGroupDesc;
+
+/* Enqueues the selected stages on the context stream (asynchronous).  Returns non-zero and enqueues nothing -- no grid or output is
+ * written -- when svt_hip_tpl_group_check_desc refuses the descriptor (SVT_HIP_ERR_BAD_PARAM). */
+int    svt_hip_tpl_group(SvtHipContext *ctx, const SvtHipTplGroupDesc *d);
+/* Host-only validation of the whole descriptor, every frame and every embedded SvtHipTplDesc (svt_hip_tpl_check_desc) included:
+ * SVT_HIP_ERR_BAD_PARAM for compute_rate, a synth_blk_size other than 16 / 32, superres_denom other than 8, sb_size other than
+ * 64 / 128, n_frames 0 or above 512, no or unknown stages, aligned sizes below the picture size, null pointers, grids shorter than
+ * the reference's allocation or than any cell a stage reads, two frames sharing grid cells (stage 2), beta / scaling shorter than
+ * stage 3 writes, a dispenser descriptor that does not match the frame. */
+int    svt_hip_tpl_group_check_desc(const SvtHipTplGroupDesc *d);
+size_t svt_hip_tpl_group_desc_size(void);  /* sizeof(SvtHipTplGroupDesc) as compiled */
+size_t svt_hip_tpl_group_frame_size(void); /* sizeof(SvtHipTplGroupFrame) as compiled */
+
 #ifdef __cplusplus
 }
 #endif

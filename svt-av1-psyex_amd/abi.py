@@ -279,3 +279,19 @@ class TplDesc(C.Structure):  # SvtHipTplDesc
                 ("src_pass", C.c_uint8), ("store_src_stats", C.c_uint8), ("use_sad_in_src_search", C.c_uint8), ("intra_mode_end", C.c_uint8),
                 ("subpel_depth", C.c_uint8), ("compute_rate", C.c_uint8), ("in_loop_ois", C.c_uint8), ("reserved1", C.c_uint8 * 3),
                 ("quant", QuantRow), ("tpl_stats", C.c_void_p), ("n_tpl_stats", C.c_uint32), ("n_tpl_src_stats", C.c_uint32), ("tpl_src_stats", C.c_void_p)]
+
+TPL_MAX_GROUP = 512
+TPL_STAGE_DISPENSE, TPL_STAGE_SYNTHESIZE, TPL_STAGE_R0BETA = 1, 2, 4
+
+
+class TplGroupFrame(C.Structure):  # SvtHipTplGroupFrame
+    _fields_ = [("picture_number", C.c_uint64), ("tpl_valid_pic", C.c_uint8), ("reserved", C.c_uint8 * 3), ("base_rdmult", C.c_int32),
+                ("tpl_stats", C.c_void_p), ("n_tpl_stats", C.c_uint32), ("n_beta", C.c_uint32), ("dispense", C.POINTER(TplDesc)),
+                ("r0", C.c_void_p), ("tpl_is_valid", C.c_void_p), ("beta", C.c_void_p), ("scaling", C.c_void_p), ("n_scaling", C.c_uint32),
+                ("reserved2", C.c_uint32)]
+
+
+class TplGroupDesc(C.Structure):  # SvtHipTplGroupDesc
+    _fields_ = [("width", C.c_uint16), ("height", C.c_uint16), ("aligned_width", C.c_uint16), ("aligned_height", C.c_uint16),
+                ("synth_blk_size", C.c_uint8), ("sb_size", C.c_uint8), ("compute_rate", C.c_uint8), ("superres_denom", C.c_uint8),
+                ("stages", C.c_uint32), ("n_frames", C.c_uint32), ("frames", C.POINTER(TplGroupFrame))]

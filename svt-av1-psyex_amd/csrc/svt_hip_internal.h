@@ -57,6 +57,10 @@ struct SvtHipContext {
     hipEvent_t  io_fence;              // orders the transfer stream behind the context stream
     void       *tpl_scratch;           // per-block state of svt_hip_tpl_dispense (tpl_kernel.hip), grown on demand, used in stream order
     size_t      tpl_scratch_bytes;
+    void       *tpl_group_dev;         // svt_hip_tpl_group's frame tables: SVT_HIP_TPL_GROUP_RING slots on the device (tpl_synth_kernel.hip)
+    void       *tpl_group_host;        // their pinned staging copies
+    hipEvent_t  tpl_group_done[4];     // recorded behind the last launch that reads slot i (SVT_HIP_TPL_GROUP_RING)
+    int         tpl_group_next;
 };
 
 struct SvtHipPaPicture {
@@ -115,4 +119,10 @@ void   svt_hip_rd_tables_free(SvtHipContext *ctx);
 // tpl_kernel.hip: its copy of the cosine table; the dispenser's scratch
 int    svt_hip_tpl_tables_init(SvtHipContext *ctx);
 void   svt_hip_tpl_free(SvtHipContext *ctx);
+// the dispenser's launches for a descriptor svt_hip_tpl_check_desc accepted, with ctx->async_mu HELD by the caller
+struct SvtHipTplDesc;
+int    svt_hip_tpl_dispense_locked(SvtHipContext *ctx, const SvtHipTplDesc *d);
+// tpl_synth_kernel.hip: the group entry's frame tables
+#define SVT_HIP_TPL_GROUP_RING 4
+void   svt_hip_tpl_group_free(SvtHipContext *ctx);
 #endif

@@ -439,6 +439,7 @@ int svt_hip_tpl_tables_init(SvtHipContext *ctx) {
 }
 
 void svt_hip_tpl_free(SvtHipContext *ctx) {
+    svt_hip_tpl_group_free(ctx);
     if (ctx->tpl_scratch) hipFree(ctx->tpl_scratch);
     ctx->tpl_scratch = nullptr;
     ctx->tpl_scratch_bytes = 0;
@@ -490,10 +491,9 @@ int svt_hip_tpl_check_desc(const SvtHipTplDesc *d) {
 #undef BAD
 }
 
-int svt_hip_tpl_dispense(SvtHipContext *ctx, const SvtHipTplDesc *d) {
-    if (!ctx) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_tpl_dispense: null context");
-    int rc = svt_hip_tpl_check_desc(d);
-    if (rc) return rc;
+} // extern "C"
+
+int svt_hip_tpl_dispense_locked(SvtHipContext *ctx, const SvtHipTplDesc *d) {
     TplParams p;
     p.d     = *d;
     p.size  = 16 << d->dispenser_search_level;
@@ -507,8 +507,6 @@ int svt_hip_tpl_dispense(SvtHipContext *ctx, const SvtHipTplDesc *d) {
     const int ts = ts_tab[d->dispenser_search_level][p.sub];
     p.iscan = ctx->iscan_dev + (size_t)ts * 3 * 1024;
     const int n_blk = p.nbx * p.nby;
-    std::lock_guard<std::mutex> g(ctx->async_mu);
-    hipSetDevice(ctx->device);
     const size_t bytes = sizeof(TplBlk) * (size_t)n_blk;
     if (bytes > ctx->tpl_scratch_bytes) {
         if (ctx->tpl_scratch) { SVT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); hipFree(ctx->tpl_scratch); ctx->tpl_scratch = nullptr; ctx->tpl_scratch_bytes = 0; }
@@ -524,6 +522,17 @@ int svt_hip_tpl_dispense(SvtHipContext *ctx, const SvtHipTplDesc *d) {
     case 10: return launch_all<10>(ctx, p, n_blk);
     default: return launch_all<16>(ctx, p, n_blk);
     }
+}
+
+extern "C" {
+
+int svt_hip_tpl_dispense(SvtHipContext *ctx, const SvtHipTplDesc *d) {
+    if (!ctx) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_tpl_dispense: null context");
+    int rc = svt_hip_tpl_check_desc(d);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(ctx->async_mu);
+    hipSetDevice(ctx->device);
+    return svt_hip_tpl_dispense_locked(ctx, d);
 }
 
 } // extern "C"

@@ -91,3 +91,115 @@ def run_tpl_hip(ctx, case, pad):
     dispense_dev(ctx, case, t, pad)
     ctx.sync()
     return download(case, t)
+
+
+# ---- the TPL group: svt_hip_tpl_group (dispense / synthesize / r0beta over a window) ----
+OUT_FILL = 0x5C  # bytes the r0beta outputs are pre-filled with: what is not written keeps them
+
+
+def _group_lib():
+    L = api.lib()
+    L.svt_hip_tpl_group_desc_size.restype = C.c_size_t
+    L.svt_hip_tpl_group_frame_size.restype = C.c_size_t
+    return L
+
+
+def group_desc_size():
+    return _group_lib().svt_hip_tpl_group_desc_size()
+
+
+def group_frame_size():
+    return _group_lib().svt_hip_tpl_group_frame_size()
+
+
+def make_group_desc(win, stages, grids, outputs=None, dispense=None):
+    """SvtHipTplGroupDesc of a window (tests/tpl_group_cases.py layout).  grids: per frame (pointer, cells); outputs: per frame None or
+    (r0, tpl_is_valid, beta, n_beta, scaling, n_scaling) pointers / counts; dispense: per frame None or an abi.TplDesc.  The frame array
+    and the dispenser descriptors are kept alive by the returned descriptor."""
+    fr = win["frames"]
+    frames = (abi.TplGroupFrame * len(fr))()
+    for i, f in enumerate(fr):
+        e = frames[i]
+        e.picture_number, e.tpl_valid_pic, e.base_rdmult = f["poc"], f["valid"], f["base_rdmult"]
+        e.tpl_stats, e.n_tpl_stats = grids[i]
+        if outputs and outputs[i] is not None:
+            e.r0, e.tpl_is_valid, e.beta, e.n_beta, e.scaling, e.n_scaling = outputs[i]
+        if dispense and dispense[i] is not None:
+            e.dispense = C.pointer(dispense[i])
+    d = abi.TplGroupDesc(width=win["width"], height=win["height"], aligned_width=win["aligned_width"], aligned_height=win["aligned_height"],
+                         synth_blk_size=win["synth"], sb_size=win["sb_size"], compute_rate=0, superres_denom=8, stages=stages,
+                         n_frames=len(fr), frames=frames)
+    d._keep = (frames, dispense)
+    return d
+
+
+def group_check_desc(d):
+    """svt_hip_tpl_group_check_desc: raises api.SvtHipError when the descriptor is refused."""
+    L = _group_lib()
+    rc = L.svt_hip_tpl_group_check_desc(C.byref(d))
+    if rc:
+        raise api.SvtHipError(f"svt_hip_tpl_group_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+
+
+def upload_window(win, n_beta, n_scaling, tail=4):
+    """Device copies of a window: per frame its grid (or, for a dispensed window, its dispenser case's tensors, upload_case), r0 holding
+    the frame's r0 value, tpl_is_valid / beta / scaling pre-filled with OUT_FILL and `tail` entries past what stage 3 writes."""
+    import torch
+    t = dict(frames=[])
+    for f in win["frames"]:
+        e = {}
+        if "case" in f:
+            e["case"] = upload_case(f["case"])
+            e["grid"] = e["case"]["tpl_stats"]
+        else:
+            e["grid"] = torch.from_numpy(np.ascontiguousarray(f["grid"]).view(np.uint8).copy()).cuda()
+        e["r0"] = torch.tensor([f["r0"]], dtype=torch.float64).cuda()
+        e["valid"] = torch.full((1,), OUT_FILL, dtype=torch.uint8).cuda()
+        e["beta"] = torch.full(((n_beta + tail) * 8,), OUT_FILL, dtype=torch.uint8).cuda()
+        e["scaling"] = torch.full(((n_scaling + tail) * 8,), OUT_FILL, dtype=torch.uint8).cuda()
+        t["frames"].append(e)
+    return t
+
+
+def enqueue_group(ctx, win, t, stages, n_beta, n_scaling, outputs=True, over=None):
+    """svt_hip_tpl_group on the tensors of upload_window; a dispensed window's pictures take the previous picture's TPL recon as their
+    list-0 recon-path reference.  over(desc) may change the descriptor first.  Returns the call's status."""
+    grids, outs, disp = [], [], []
+    for i, (f, e) in enumerate(zip(win["frames"], t["frames"])):
+        grids.append((e["grid"].data_ptr(), e["grid"].numel() // abi.TPL_STATS_DTYPE.itemsize))
+        outs.append((e["r0"].data_ptr(), e["valid"].data_ptr(), e["beta"].data_ptr(), n_beta, e["scaling"].data_ptr(), n_scaling)
+                    if outputs and f["outputs"] else None)
+        if "case" in f:
+            tc = e["case"]
+            refs = {k: (v[0].data_ptr(), v[1].data_ptr()) for k, v in tc["refs"].items()}
+            if i:
+                refs[(0, 0)] = (tc["refs"][(0, 0)][0].data_ptr(), t["frames"][i - 1]["case"]["recon"].data_ptr())
+            me = tuple(x.data_ptr() for x in tc["me"]) if tc["me"] is not None else None
+            disp.append(make_desc(f["case"], 40, tc["cur"].data_ptr(), tc["recon"].data_ptr(), refs, me, tc["tpl_stats"].data_ptr(),
+                                  tc["tpl_src_stats"].data_ptr()))
+        else:
+            disp.append(None)
+    d = make_group_desc(win, stages, grids, outs, disp)
+    if over:
+        over(d)
+    return _group_lib().svt_hip_tpl_group(ctx._h, C.byref(d))
+
+
+def download_window(t):
+    """Per frame: (grid, r0, tpl_is_valid, beta bytes as uint64, scaling bytes as uint64, padded recon plane or None)."""
+    out = []
+    for e in t["frames"]:
+        rec = e["case"]["recon"].cpu().numpy().copy() if "case" in e else None
+        out.append((e["grid"].cpu().numpy().view(abi.TPL_STATS_DTYPE).copy(), float(e["r0"].cpu()[0]), int(e["valid"].cpu()[0]),
+                    e["beta"].cpu().numpy().view(np.uint64).copy(), e["scaling"].cpu().numpy().view(np.uint64).copy(), rec))
+    return out
+
+
+def run_group_hip(ctx, win, stages, n_beta, n_scaling, outputs=True):
+    """Uploads a window, runs the stages, returns download_window's per-frame results."""
+    import torch
+    t = upload_window(win, n_beta, n_scaling)
+    torch.cuda.synchronize()
+    ctx.check(enqueue_group(ctx, win, t, stages, n_beta, n_scaling, outputs), "svt_hip_tpl_group")
+    ctx.sync()
+    return download_window(t)

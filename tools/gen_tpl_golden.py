@@ -250,13 +250,14 @@ SOURCES = ["Codec/enc_intra_prediction.c", "Codec/intra_prediction.c", "Codec/tr
            "Codec/aom_dsp_rtcd.c", "Codec/svt_log.c", "Codec/mode_decision.c", "Codec/inter_prediction.c", "ASM_SSE2/pic_operators_intrin_sse2.c"]
 
 
-def build(ref, tmp):
+def build(ref, tmp, harness=HARNESS):
+    """Compiles the reference sources with `harness` (C text that #includes src_ops_process.c) into a library; returns it, initialised."""
     lib = os.path.join(ref, "Source", "Lib")
     inc = [f"-I{ref}/Source/API"] + [f"-I{lib}/{d}" for d in ("Codec", "C_DEFAULT", "Globals", "ASM_SSE2", "ASM_SSSE3", "ASM_SSE4_1", "ASM_AVX2")]
     inc += [f"-I{ref}/third_party/fastfeat", f"-I{ref}/third_party/safestringlib", f"-I{ROOT}/include"]
     flags = ["-O2", "-DNDEBUG", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w", "-msse4.1", "-DARCH_X86_64=1", "-DEN_AVX512_SUPPORT=0",
              "-DEXCLUDE_HASH=1", "-DREPRODUCIBLE_BUILDS=0"] + inc
-    open(os.path.join(tmp, "harness.c"), "w").write(HARNESS)
+    open(os.path.join(tmp, "harness.c"), "w").write(harness)
     open(os.path.join(tmp, "exports.map"), "w").write(VERSION_SCRIPT)
     procs, objs = [], []
     for src in [os.path.join(lib, s) for s in SOURCES] + [os.path.join(tmp, "harness.c")]:
