@@ -15,7 +15,8 @@ _seq_cache = {}
 
 
 def sequence(width, height, n_frames, seed, kind="pan"):
-    """uint8 luma frames [n, h, w].  kinds: pan, noise (i.i.d.), flat, extremes (0 vs 255)."""
+    """uint8 luma frames [n, h, w].  kinds: pan, noise (i.i.d.), flat, extremes (0 vs 255), mixed (pan, with the 48x48
+    tiles (tx, ty) where (tx + 2 ty) % 3 == 0 replaced by fresh i.i.d. noise in every frame: nothing predicts those, the rest pans)."""
     key = (width, height, n_frames, seed, kind)
     if key not in _seq_cache:
         if kind == "pan":
@@ -24,6 +25,12 @@ def sequence(width, height, n_frames, seed, kind="pan"):
             s = synth.to_8bit(synth.synth_sequence(width, height, n_frames, seed, pan=(23, -11 + 11)))
         elif kind == "noise":
             s = np.random.default_rng(seed).integers(0, 256, (n_frames, height, width), dtype=np.uint8)
+        elif kind == "mixed":
+            s = synth.to_8bit(synth.synth_sequence(width, height, n_frames, seed)).copy()
+            ty, tx = np.mgrid[0:height, 0:width] // 48
+            tiles = (tx + 2 * ty) % 3 == 0
+            fresh = np.random.default_rng(seed).integers(0, 256, s.shape, dtype=np.uint8)
+            s[:, tiles] = fresh[:, tiles]
         elif kind == "flat":
             s = np.full((n_frames, height, width), 128, np.uint8)
         elif kind == "extremes":

@@ -6,14 +6,15 @@ quantizer / inverse-reconstruction arithmetic is the oracle's RD batch (pyoracle
 tests/tpl_cases.py), whose equality with the reference's chain tests/test_tpl_chain.py checks.
 
 Also the seeded cases (pictures, references, candidate lists, MVs) shared by the CPU and GPU tests.  A case is a dict of numpy
-arrays and numbers; planes are padded uint8 arrays with the sample (x, y) at [PAD + y, PAD + x]."""
+arrays and numbers; planes are padded uint8 arrays with the sample (x, y) at [pad + y, pad + x], pad = case["pad"] where the case has
+one (planes shared with ME carry the ME's padding, tests/me_tpl_cases.py), else PAD."""
 import numpy as np
 
 import pyoracle
 from svt_av1_psyex_amd import abi, rd
 from tpl_cases import TPL_TX_SIZE
 
-PAD = 40          # padding of every plane of the cases (>= TPL_PADX / TPL_PADY = 32)
+PAD = 40          # padding of every plane of the seeded cases (>= TPL_PADX / TPL_PADY = 32)
 TPL_PADX = 32
 NEWMV, DC_PRED = 16, 0
 INT64_MAX = (1 << 63) - 1
@@ -39,35 +40,35 @@ def blocks_in_order(case):
             yield ox + lx * S, oy + ly * S, b64, me
 
 
-def at(plane, x, y):
-    return int(plane[PAD + y, PAD + x])
+def at(plane, x, y, pad=PAD):
+    return int(plane[pad + y, pad + x])
 
 
-def block(plane, x, y, S):
-    return plane[PAD + y:PAD + y + S, PAD + x:PAD + x + S]
+def block(plane, x, y, S, pad=PAD):
+    return plane[pad + y:pad + y + S, pad + x:pad + x + S]
 
 
-def neighbours_open_loop(plane, x, y, bw, bh, width, height):
+def neighbours_open_loop(plane, x, y, bw, bh, width, height, pad=PAD):
     """svt_aom_update_neighbor_samples_array_open_loop_mb{,_recon} with use_top_righ_bottom_left = update_top_neighbor = 1
     (Codec/enc_intra_prediction.c:1127-1290): returns (above[0..2bw), left[0..2bh)), the samples after the top-left one."""
     nw, nh = 2 * bw, 2 * bh
     above = [127] * (nw + 1)
     left = [129] * (nh + 1)
-    above[0] = left[0] = at(plane, x - 1, y - 1) if (x != 0 and y != 0) else 128
+    above[0] = left[0] = at(plane, x - 1, y - 1, pad) if (x != 0 and y != 0) else 128
     li = 1  # left_ref pointer (index into left)
     count = nw
     if x != 0:
         if y == 0:
-            left[li - 1] = at(plane, x - 1, y)
+            left[li - 1] = at(plane, x - 1, y, pad)
         count = count - ((y + count) - height) if (y + count) > height else count
         for i in range(count):
-            left[li + i] = at(plane, x - 1, y + i)
+            left[li + i] = at(plane, x - 1, y + i, pad)
         li += count + (nw - count)
         for i in range(bh):
             left[li - bh + i] = left[li - bh - 1]
     elif y != 0:
         count = count - ((y + count) - height) if (y + count) > height else count
-        v = at(plane, x, y - 1)
+        v = at(plane, x, y - 1, pad)
         for i in range(count + 1):
             left[li - 1 + i] = v
         above[0] = v
@@ -77,7 +78,7 @@ def neighbours_open_loop(plane, x, y, bw, bh, width, height):
     if y != 0:
         count = count - ((x + count) - width) if (x + count) > width else count
         for i in range(count):
-            above[1 + i] = at(plane, x + i, y - 1)
+            above[1 + i] = at(plane, x + i, y - 1, pad)
         if x != 0:
             for i in range(bw):
                 above[1 + bw + i] = above[1 + bw - 1]
@@ -89,15 +90,15 @@ def neighbours_open_loop(plane, x, y, bw, bh, width, height):
     return above[1:], left[1:]
 
 
-def dc_pred(plane, x, y, S, width, height):
+def dc_pred(plane, x, y, S, width, height, pad=PAD):
     """The DC predictor of the dispenser (:624-659, :1054-1087): get_neighbor_samples_dc for blocks inside the picture that are
     not on its top row or left column, the open-loop fill otherwise; svt_aom_dc_pred[x > 0][y > 0]."""
     inside = x + S <= width and y + S <= height
     if x > 0 and y > 0 and inside:
-        above = [at(plane, x + i, y - 1) for i in range(S)]
-        left = [at(plane, x - 1, y + i) for i in range(S)]
+        above = [at(plane, x + i, y - 1, pad) for i in range(S)]
+        left = [at(plane, x - 1, y + i, pad) for i in range(S)]
     else:
-        above, left = neighbours_open_loop(plane, x, y, S, S, width, height)
+        above, left = neighbours_open_loop(plane, x, y, S, S, width, height, pad)
     if x > 0 and y > 0:
         return (sum(above[:S]) + sum(left[:S]) + S) // (2 * S)
     if x > 0:
@@ -150,6 +151,7 @@ def generate_padding(buf, width, height, org_x, org_y):
 def restate(case):
     """Returns (tpl_stats grid, tpl_src_stats, padded recon) after one dispense of the case (its arrays are not modified)."""
     S = 16 << case["level"]
+    pad = case.get("pad", PAD)
     sub, step = case["sub"], 1 << case["sub"]
     W, H = case["width"], case["height"]
     cur = case["cur"]
@@ -169,8 +171,8 @@ def restate(case):
         if case["src_pass"]:
             best_inter = best_intra = INT64_MAX
             if not case["disable_intra_pred"]:
-                dc = dc_pred(cur, x, y, S, W, H)
-                best_intra = int(np.abs(block(cur, x, y, S).astype(np.int32) - dc).sum())
+                dc = dc_pred(cur, x, y, S, W, H, pad)
+                best_intra = int(np.abs(block(cur, x, y, S, pad).astype(np.int32) - dc).sum())
             n = 0 if case["slice_is_i"] else int(me["total"][b64 * n_pu + mbo])
             for ci in range(n):
                 cand = int(me["cand"][(b64 * n_pu + mbo) * max_cand + ci])
@@ -192,14 +194,14 @@ def restate(case):
                     my = wrap16((-TPL_PADX - y) << 3)
                 if y + S + (my >> 3) > TPL_PADX + r["max_height"] - 1:
                     my = wrap16(((TPL_PADX + r["max_height"] - 1) - (y + S)) << 3)
-                cost = int(np.abs(block(cur, x, y, S).astype(np.int32) - block(r["src"], x + (mx >> 3), y + (my >> 3), S)).sum())
+                cost = int(np.abs(block(cur, x, y, S, pad).astype(np.int32) - block(r["src"], x + (mx >> 3), y + (my >> 3), S, pad)).sum())
                 if cost < best_inter:
                     best_poc, best_rf, best_inter, best_mv = r["poc"], lst * 4 + ref, cost, (my, mx)
             if best_inter < best_intra:
                 best_mode = NEWMV
             if best_mode == NEWMV:
                 r = case["refs"][(best_rf >> 2, best_rf & 3)]
-                re, _, _ = chain(case, block(cur, x, y, S), block(r["src"], x + (best_mv[1] >> 3), y + (best_mv[0] >> 3), S))
+                re, _, _ = chain(case, block(cur, x, y, S, pad), block(r["src"], x + (best_mv[1] >> 3), y + (best_mv[0] >> 3), S, pad))
                 st["srcrf_dist"] = (re << 4) << sub
             if case["store_src_stats"]:
                 s = srcst[si]
@@ -212,11 +214,11 @@ def restate(case):
         # recon path (:979-1198)
         if best_mode == NEWMV:
             r = case["refs"][(best_rf >> 2, best_rf & 3)]
-            pred = block(r["recon"], x + (best_mv[1] >> 3), y + (best_mv[0] >> 3), S).copy()
+            pred = block(r["recon"], x + (best_mv[1] >> 3), y + (best_mv[0] >> 3), S, pad).copy()
         else:
-            pred = np.full((S, S), dc_pred(rec, x, y, S, W, H), np.uint8)
-        re, eob, out = chain(case, block(cur, x, y, S), pred)
-        dst = block(rec, x, y, S)
+            pred = np.full((S, S), dc_pred(rec, x, y, S, W, H, pad), np.uint8)
+        re, eob, out = chain(case, block(cur, x, y, S, pad), pred)
+        dst = block(rec, x, y, S, pad)
         dst[:] = pred
         if (not case["disable_intra_pred"] or case["is_ref"]) and eob:
             for i in range(0, S, step):
@@ -229,7 +231,7 @@ def restate(case):
         if not case["tpl_slice_is_i"] and best_rf != -1:
             st["mv_row"], st["mv_col"], st["ref_frame_poc"] = best_mv[0], best_mv[1], best_poc
         result_model_store(case, grid, st, x, y, S)
-    generate_padding(rec, case["recon_width"], case["recon_height"], PAD, PAD)
+    generate_padding(rec, case["recon_width"], case["recon_height"], pad, pad)
     return grid, srcst, rec
 
 
@@ -250,7 +252,11 @@ def padded(rng, W, H, base=None, amp=None):
 
 
 def make_case(seed, W, H, level=0, sub=0, pf=2, synth=16, disable_intra_pred=0, is_ref=1, slice_is_i=0, src_pass=1, store_src_stats=1,
-              unusable=(), enable_me_16x16=1, n_refs=(2, 1), amp=6, qstep=(40, 52), max_shrink=(0, 0)):
+              unusable=(), enable_me_16x16=1, n_refs=(2, 1), amp=6, qstep=(40, 52), max_shrink=(0, 0), enable_me_8x8=0, max_cand=23, max_refs=7,
+              max_l0=4):
+    """max_cand / max_refs / max_l0 and enable_me_8x8 (n_pu 85) set the strides of the ME arrays; the defaults are wider than any
+    picture's, api.picture_desc gives 3 / 2 / 1 for one reference per list and 9 / 4 / 2 for two."""
+    assert n_refs[0] <= max_l0 and max_l0 + n_refs[1] <= max_refs
     rng = np.random.default_rng(seed)
     aw, ah = (W + 7) & ~7, (H + 7) & ~7
     cur = padded(rng, W, H)
@@ -261,10 +267,9 @@ def make_case(seed, W, H, level=0, sub=0, pf=2, synth=16, disable_intra_pred=0, 
             src, shift = padded(rng, W, H, base=cur, amp=amp)
             refs[(lst, ref)] = dict(src=src, shift=shift, recon=padded(rng, W, H, base=src, amp=3)[0], poc=poc + (lst * 8 + ref + 1) * (1 if lst else -1),
                                     max_width=W - max_shrink[0], max_height=H - max_shrink[1], usable=int((lst, ref) not in unusable))
-    n_pu = abi.n_pu(enable_me_16x16, 0)
-    max_cand, max_refs, max_l0 = 23, 7, 4
+    n_pu = abi.n_pu(enable_me_16x16, enable_me_8x8)
     n_b64 = ((aw + 63) // 64) * ((ah + 63) // 64)
-    total = rng.integers(0, 6, n_b64 * n_pu).astype(np.uint8)
+    total = np.minimum(rng.integers(0, 6, n_b64 * n_pu), max_cand).astype(np.uint8)  # ME never lists more than max_cand candidates
     cand = np.zeros(n_b64 * n_pu * max_cand, np.uint8)
     for i in range(n_b64 * n_pu):
         for c in range(max_cand):
@@ -318,6 +323,9 @@ def seeded_grid():
         ("pf1_L1_sub0", dict(seed=57, W=128, H=128, level=1, sub=0, pf=1, synth=32)),
         ("max_size_below_picture", dict(seed=58, W=200, H=136, max_shrink=(40, 24), disable_intra_pred=1)),  # the clamp reads max_width / max_height
         ("small_picture", dict(seed=59, W=40, H=24, n_refs=(1, 0))),
+        # the ME arrays at the strides real pictures have (n_pu 85; max_cand / max_refs / max_l0 of one and of two references per list)
+        ("me_layout_85_3_2_1", dict(seed=62, W=200, H=136, n_refs=(1, 1), enable_me_8x8=1, max_cand=3, max_refs=2, max_l0=1)),
+        ("me_layout_85_9_4_2_L1", dict(seed=63, W=232, H=178, level=1, sub=2, synth=32, n_refs=(2, 2), enable_me_8x8=1, max_cand=9, max_refs=4, max_l0=2)),
     ]
     return cases
 

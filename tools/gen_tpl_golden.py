@@ -278,7 +278,7 @@ def run_ref(L, c):
     rec, grid, src = c["recon"].copy(), c["tpl_stats"].copy(), c["tpl_src_stats"].copy()
     refs = {k: (r["src"].ctypes.data, r["recon"].ctypes.data) for k, r in c["refs"].items()}
     me = None if c["slice_is_i"] else tuple(c["me"][k].ctypes.data for k in ("total", "mv", "cand"))
-    d = tpl.make_desc(c, tc.PAD, c["cur"].ctypes.data, rec.ctypes.data, refs, me, grid.ctypes.data, src.ctypes.data)
+    d = tpl.make_desc(c, c.get("pad", tc.PAD), c["cur"].ctypes.data, rec.ctypes.data, refs, me, grid.ctypes.data, src.ctypes.data)
     if L.harness_dispense(C.byref(d)) != 0:
         raise RuntimeError("harness_dispense failed")
     return grid, src, rec
