@@ -34,8 +34,11 @@ extern "C" {
 #define SVT_HIP_DIST_SAD 0
 #define SVT_HIP_DIST_VAR 1
 
-#define SVT_HIP_FP_CENTRE_FROM_CHAIN 1 /* (mvx, mvy) = the best MV job `chain_from` left (its outputs, a job of an EARLIER batch or an earlier index of this one) */
-#define SVT_HIP_FP_BEST_FROM_CHAIN 2   /* *best_cost / *best_mvx / *best_mvy on entry = job `chain_from`'s outputs */
+/* Chaining: `chain_from` is the job's OWN index, and names its slot of best_cost / best_mv as a batch enqueued EARLIER on the stream left it (the
+ * rounds of one block share a slot; every job of a batch writes its slot, so no other slot is stable while the batch runs).  With chain_from
+ * outside [0, n_jobs) both flags are ignored and the job uses its own fields. */
+#define SVT_HIP_FP_CENTRE_FROM_CHAIN 1 /* (mvx, mvy) = the best MV in slot `chain_from` */
+#define SVT_HIP_FP_BEST_FROM_CHAIN 2   /* *best_cost / *best_mvx / *best_mvy on entry = slot `chain_from` */
 #define SVT_HIP_FP_SPRS_LEV0_DONE 4    /* is_sprs_lev0_performed */
 #define SVT_HIP_FP_ENABLE_PSAD 8       /* ctx->enable_psad */
 
@@ -53,7 +56,7 @@ typedef struct SvtHipFullpelJob {
     SvtHipMv ref_mv;               /* ctx->ref_mv: what the MV-rate is measured against */
     uint32_t best_cost;            /* *best_cost on entry (unless BEST_FROM_CHAIN) */
     int16_t  best_mvx, best_mvy;   /* *best_mvx / *best_mvy on entry */
-    int32_t  chain_from;           /* job index whose outputs feed this one (flags), or -1 */
+    int32_t  chain_from;           /* the job's own index when a chain flag is set, else -1 (out of range: the flags are ignored) */
 } SvtHipFullpelJob;
 
 typedef struct SvtHipFullpelBatchDesc {
@@ -70,7 +73,7 @@ typedef struct SvtHipFullpelBatchDesc {
     int16_t  *best_mv;                     /* [n_jobs][2] = (best_mvx, best_mvy) */
 } SvtHipFullpelBatchDesc;
 
-/* Jobs of one batch run concurrently: a job may only chain from a job of a batch enqueued earlier on the stream (same output arrays). */
+/* Jobs of one batch run concurrently: a job chains only from its own slot, as a batch enqueued earlier on the stream (same output arrays) left it. */
 int svt_hip_md_fullpel_batch(SvtHipContext *ctx, const SvtHipFullpelBatchDesc *d);
 
 #define SVT_HIP_USE_2_TAPS 1

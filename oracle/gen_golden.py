@@ -306,7 +306,32 @@ def gen_md_search():
     print("md_search.npz", len(out), "arrays")
 
 
-GENERATORS = {"md": gen_md_search, "pyramid": gen_pyramid, "me": gen_me, "me_mctf": lambda: gen_me(only=["me_vga_m4_mctf"]), "sad": gen_sad_kernels, "presets": gen_presets, "stats": gen_block_stats, "dg": gen_dg_detector, "tpl": gen_tpl_chain, "rd": gen_rd_chain}
+def gen_md_edges():
+    """The reference's md_full_pel_search chains and both sub-pel tree searches on tests/md_search_cases.py's edge / tie / every-cost-mode case lists
+    (FULLPEL_EDGE_GRID with the edge chain and the five-round chain, SUBPEL_TIE_GRID, SUBPEL_FAR_GRID): one row per case."""
+    import md_search_cases as mc
+    ref = pyoracle.load_ref()
+    out = {}
+    for chain, key in (("edge", "fe"), ("std", "fc")):
+        costs, mvs = [], []
+        for ci in range(len(mc.FULLPEL_EDGE_GRID)):
+            src, refp, tables, rounds, ctype, epb = mc.fullpel_edge_case(ci, chain)
+            got = mc.run_fullpel_cpu(ref.ref_md_fullpel_batch, src, refp, rounds, ctype, epb, tables)
+            costs.append(np.stack([c for c, _ in got]))
+            mvs.append(np.stack([m for _, m in got]))
+        out[f"{key}_cost"], out[f"{key}_mv"] = np.stack(costs), np.stack(mvs)
+    for far, key in ((False, "st"), (True, "sf")):
+        rows = []
+        for ci in range(len(mc.SUBPEL_FAR_GRID if far else mc.SUBPEL_TIE_GRID)):
+            src, refp, tables, jobs, setting = mc.subpel_edge_case(ci, far)
+            rows.append(mc.run_subpel_cpu(ref.ref_md_subpel_batch, src, refp, jobs, setting, mc.SUBPEL_EPB, mc.SUBPEL_QP, tables))
+        for k in rows[0]:
+            out[f"{key}_{k}"] = np.stack([r[k] for r in rows])
+    np.savez_compressed(os.path.join(OUT, "md_search_edges.npz"), **out)
+    print("md_search_edges.npz", {k: v.shape for k, v in out.items()})
+
+
+GENERATORS = {"md": gen_md_search, "md_edges": gen_md_edges, "pyramid": gen_pyramid, "me": gen_me, "me_mctf": lambda: gen_me(only=["me_vga_m4_mctf"]), "sad": gen_sad_kernels, "presets": gen_presets, "stats": gen_block_stats, "dg": gen_dg_detector, "tpl": gen_tpl_chain, "rd": gen_rd_chain}
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)

@@ -91,7 +91,12 @@ static void full_pel_search(const SvtHipFullpelBatchDesc *d, const SvtHipFullpel
         }
 }
 
+static int chain_in_range(const SvtHipFullpelBatchDesc *d, const SvtHipFullpelJob *jb) { return jb->chain_from >= 0 && (uint32_t)jb->chain_from < d->n_jobs; }
+
 int orc_md_fullpel_batch(const SvtHipFullpelBatchDesc *d) {
+    /* the jobs of a batch run concurrently on the device: a chain to another index of the same batch is a race there, and an error here */
+    for (uint32_t j = 0; j < d->n_jobs; j++)
+        if ((d->jobs[j].flags & (SVT_HIP_FP_CENTRE_FROM_CHAIN | SVT_HIP_FP_BEST_FROM_CHAIN)) && chain_in_range(d, &d->jobs[j]) && (uint32_t)d->jobs[j].chain_from != j) return 1;
     for (uint32_t j = 0; j < d->n_jobs; j++) {
         const SvtHipFullpelJob *jb = &d->jobs[j];
         SvtHipMvCostParam       p;
@@ -100,8 +105,9 @@ int orc_md_fullpel_batch(const SvtHipFullpelBatchDesc *d) {
         p.error_per_bit = d->error_per_bit;
         int16_t  mvx = jb->mvx, mvy = jb->mvy, bx = jb->best_mvx, by = jb->best_mvy;
         uint32_t best = jb->best_cost;
-        if (jb->flags & SVT_HIP_FP_CENTRE_FROM_CHAIN) { mvx = d->best_mv[2 * jb->chain_from]; mvy = d->best_mv[2 * jb->chain_from + 1]; }
-        if (jb->flags & SVT_HIP_FP_BEST_FROM_CHAIN) { best = d->best_cost[jb->chain_from]; bx = d->best_mv[2 * jb->chain_from]; by = d->best_mv[2 * jb->chain_from + 1]; }
+        const int chained = chain_in_range(d, jb); /* out of range: the chain flags are ignored */
+        if (chained && (jb->flags & SVT_HIP_FP_CENTRE_FROM_CHAIN)) { mvx = d->best_mv[2 * jb->chain_from]; mvy = d->best_mv[2 * jb->chain_from + 1]; }
+        if (chained && (jb->flags & SVT_HIP_FP_BEST_FROM_CHAIN)) { best = d->best_cost[jb->chain_from]; bx = d->best_mv[2 * jb->chain_from]; by = d->best_mv[2 * jb->chain_from + 1]; }
         full_pel_search(d, jb, &p, mvx, mvy, &best, &bx, &by);
         d->best_cost[j] = best; d->best_mv[2 * j] = bx; d->best_mv[2 * j + 1] = by;
     }

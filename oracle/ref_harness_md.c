@@ -75,14 +75,15 @@ int ref_md_full_pel_search(const SvtHipFullpelBatchDesc *d, const SvtHipFullpelJ
     return 0;
 }
 
-/* host-memory mirror of svt_hip_md_fullpel_batch through the reference (jobs in order: a job may chain from an earlier one) */
+/* host-memory mirror of svt_hip_md_fullpel_batch through the reference (a job chains from its own slot) */
 int ref_md_fullpel_batch(const SvtHipFullpelBatchDesc *d) {
     for (uint32_t j = 0; j < d->n_jobs; j++) {
         const SvtHipFullpelJob *jb = &d->jobs[j];
         int16_t  mvx = jb->mvx, mvy = jb->mvy, bx = jb->best_mvx, by = jb->best_mvy;
         uint32_t best = jb->best_cost;
-        if (jb->flags & SVT_HIP_FP_CENTRE_FROM_CHAIN) { mvx = d->best_mv[2 * jb->chain_from]; mvy = d->best_mv[2 * jb->chain_from + 1]; }
-        if (jb->flags & SVT_HIP_FP_BEST_FROM_CHAIN) { best = d->best_cost[jb->chain_from]; bx = d->best_mv[2 * jb->chain_from]; by = d->best_mv[2 * jb->chain_from + 1]; }
+        const int chained = jb->chain_from >= 0 && (uint32_t)jb->chain_from < d->n_jobs; /* the batch's range rule (svt_hip_md_search.h) */
+        if (chained && (jb->flags & SVT_HIP_FP_CENTRE_FROM_CHAIN)) { mvx = d->best_mv[2 * jb->chain_from]; mvy = d->best_mv[2 * jb->chain_from + 1]; }
+        if (chained && (jb->flags & SVT_HIP_FP_BEST_FROM_CHAIN)) { best = d->best_cost[jb->chain_from]; bx = d->best_mv[2 * jb->chain_from]; by = d->best_mv[2 * jb->chain_from + 1]; }
         const int rc = ref_md_full_pel_search(d, jb, mvx, mvy, &best, &bx, &by);
         if (rc) return rc;
         d->best_cost[j] = best; d->best_mv[2 * j] = bx; d->best_mv[2 * j + 1] = by;

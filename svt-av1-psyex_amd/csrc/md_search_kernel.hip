@@ -6,7 +6,7 @@
 //     position's cost = distortion + MV rate (svt_aom_fp_mv_err_cost, Codec/mcomp.c:44-78,776); lane <-> search position, the block's rows
 //     through v_sad_u8 / dot products straight from global memory (L1 / L2: the windows of a job are a few KB); the winner is the wave minimum
 //     of (cost << 32 | visiting order) against the incoming best with the reference's strict `<`.  Jobs chain on the device (centre and / or
-//     incoming best = an earlier job's outputs): the rounds of md_nsq_motion_search (:2260-2375) never come back to the host.
+//     incoming best = what an earlier batch left in the job's own slot): the rounds of md_nsq_motion_search (:2260-2375) never come back to the host.
 //   md_subpel_kernel   = svt_av1_find_best_sub_pixel_tree (Codec/mcomp.c:688-777; search_method 1: every candidate's error is the variance of
 //     svt_aom_upsampled_pred -- separable 2 / 4 / 8-tap interpolation, recomputed per pixel) or
 //     svt_av1_find_best_sub_pixel_tree_pruned (Codec/mcomp.c:606-687) with svt_estimated_pref_error (:147-167): the tree's
@@ -99,8 +99,9 @@ __global__ void __launch_bounds__(64) md_fullpel_kernel(const FullpelParams p) {
     const SvtHipFullpelJob jb = d.jobs[job];
     int16_t  mvx = jb.mvx, mvy = jb.mvy, in_x = jb.best_mvx, in_y = jb.best_mvy;
     uint32_t in_cost = jb.best_cost;
-    if (jb.flags & SVT_HIP_FP_CENTRE_FROM_CHAIN) { mvx = d.best_mv[2 * jb.chain_from]; mvy = d.best_mv[2 * jb.chain_from + 1]; }
-    if (jb.flags & SVT_HIP_FP_BEST_FROM_CHAIN) { in_cost = d.best_cost[jb.chain_from]; in_x = d.best_mv[2 * jb.chain_from]; in_y = d.best_mv[2 * jb.chain_from + 1]; }
+    const bool chained = jb.chain_from >= 0 && (uint32_t)jb.chain_from < d.n_jobs; // out of range: the chain flags are ignored
+    if (chained && (jb.flags & SVT_HIP_FP_CENTRE_FROM_CHAIN)) { mvx = d.best_mv[2 * jb.chain_from]; mvy = d.best_mv[2 * jb.chain_from + 1]; }
+    if (chained && (jb.flags & SVT_HIP_FP_BEST_FROM_CHAIN)) { in_cost = d.best_cost[jb.chain_from]; in_x = d.best_mv[2 * jb.chain_from]; in_y = d.best_mv[2 * jb.chain_from + 1]; }
     // every lane has read the chain inputs before any lane of this wave overwrites them (a job may chain from itself: results in place)
     __builtin_amdgcn_wave_barrier();
     int sx = jb.start_x, ex = jb.end_x, sy = jb.start_y, ey = jb.end_y;

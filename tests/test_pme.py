@@ -69,7 +69,7 @@ def test_garbage_padding_after_mv_cost_type(oracle, ref, cost_type):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("cost_type", [0, 3, 4, 5])
+@pytest.mark.parametrize("cost_type", [0, 1, 2, 3, 4, 5])
 def test_hip_batch_matches_oracle(hip_ctx, oracle, cost_type):
     rng = np.random.default_rng(200 + cost_type)
     tables = cost_tables(rng)
