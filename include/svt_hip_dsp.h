@@ -12,10 +12,12 @@
  *  -> svt_full_distortion_kernel32_bits                     (Codec/pic_operators.c:150-172)
  *  -> svt_av1_inv_txfm2d_add_{WxH}                          (Codec/inv_transforms.c:2459-2716)
  *  -> svt_spatial_full_distortion_kernel / svt_full_distortion_kernel16_bits (picture_operators_c.c:65-83, pic_operators.c:174-197)
- * Decision logic (which tx_type wins, rate estimation, RDOQ) stays on the host.
+ * The rate half of that loop body -- svt_aom_txb_estimate_coeff_bits, RDCOST and the choice of the winning tx_type -- is
+ * svt_hip_coeff_rate_batch below; it reads the qcoeff / eob arrays svt_hip_rd_batch writes, on the device.  RDOQ and the early exits of
+ * the search stay on the host.
  *
  * Also here: the forward and the inverse transform as batches of their own (svt_hip_fwd_txfm_batch, svt_hip_inv_txfm_batch), the
- * batched block statistics incl. the PSYEX psy-RD term and distortion facades (svt_hip_block_stats_batch, svt_hip_spy_rd_bias),
+ * coefficient rate estimation with the RD cost and the winning candidate (svt_hip_coeff_rate_batch), batched block statistics incl. the PSYEX psy-RD term and distortion facades (svt_hip_block_stats_batch, svt_hip_spy_rd_bias),
  * full-pel prediction from ME results (svt_hip_fullpel_pred{,_batch}) and the scan-order / size helpers.
  */
 #ifndef SVT_HIP_DSP_H
@@ -216,6 +218,91 @@ int    svt_hip_ssim_batch(SvtHipContext *ctx, const SvtHipSsimBatchDesc *d);
  * `pyramids` != 0, when a region is not 64x64. */
 int    svt_hip_ssim_check_jobs(const SvtHipBlockJob *jobs, uint32_t n_jobs, int pyramids);
 size_t svt_hip_ssim_desc_size(void); /* sizeof(SvtHipSsimBatchDesc) as compiled */
+
+/* ---- coefficient rate estimation, RD cost and the winning candidate -------------------------------------------------
+ * Per job, svt_aom_txb_estimate_coeff_bits of one plane (Codec/rd_cost.c:1405-1450) behind the two short-cuts of tx_type_search
+ * (Codec/product_coding_loop.c:4947-4952):
+ *   bits     luma, (coeff_rate_est_lvl >= 2 || == 0) && eob < th:  6000 + eob * 1000,  th = (tx_width * tx_height) >> 6 (real dimensions)
+ *            luma, coeff_rate_est_lvl == 0:                        3000 + eob * 100
+ *            eob == 0:                                             av1_cost_skip_txb = txb_skip_cost[txb_skip_ctx][1]
+ *            else svt_av1_cost_coeffs_txb with allow_update_cdf == 0 (rd_cost.c:434-559), luma << mds_subres_step; chroma carries no
+ *            transform-type rate, no shift and no short-cut
+ *   rd_cost  RDCOST(lambda, bits, dist) (Codec/rd_cost.h:37) = ((bits * lambda + 256) >> 9) + (dist << 7); the caller's own shifts of
+ *            the distortion and its three_quad_energy addition stay with the caller
+ * and per group of consecutive jobs (the candidates of one block), the first strict minimum of rd_cost in job order.  That is
+ * tx_type_search's best_tx_type (product_coding_loop.c:4976-4985) exactly when txt_ctrls.early_exit_coeff_th == 0 &&
+ * txt_ctrls.early_exit_dist_th == 0 (no candidate is skipped behind a good one, :4987-5002), ssim_level <= SSIM_LVL_1 (the search
+ * compares SSD costs), and the caller lists a block's candidates in the reference's group order (the tx_type_group loop's).  The
+ * search's early_cost > best_cost skip (:4941-4945) never changes the winner: RDCOST is monotone in the rate.
+ * Bit-exact: integer, table-driven arithmetic whose 32-bit sums are order-free. */
+typedef struct SvtHipLvMapCoeffCost { /* LvMapCoeffCost (Codec/md_rate_estimation.h:41-49) */
+    int32_t txb_skip_cost[13][2];
+    int32_t base_eob_cost[4][3];
+    int32_t base_cost[42][8];
+    int32_t eob_extra_cost[22][2];
+    int32_t dc_sign_cost[3][2];
+    int32_t lps_cost[21][26];
+} SvtHipLvMapCoeffCost;
+typedef struct SvtHipLvMapEobCost { /* LvMapEobCost (:37-39) */
+    int32_t eob_cost[2][11];
+} SvtHipLvMapEobCost;
+/* The four members of MdRateEstimationContext the estimate reads (Codec/md_rate_estimation.h:127-133), same element types and bounds: a
+ * host copies them member by member.  Lives in DEVICE memory, uploaded by the caller; changes once per picture. */
+typedef struct SvtHipRateTables {
+    SvtHipLvMapCoeffCost coeff_fac_bits[5][2];          /* [TX_SIZES][PLANE_TYPES] */
+    SvtHipLvMapEobCost   eob_frac_bits[7][2];
+    int32_t intra_tx_type_fac_bits[3][4][13][17];      /* [EXT_TX_SETS_INTRA][EXT_TX_SIZES][INTRA_MODES][CDF_SIZE(TX_TYPES)] */
+    int32_t inter_tx_type_fac_bits[4][4][17];          /* [EXT_TX_SETS_INTER][EXT_TX_SIZES][CDF_SIZE(TX_TYPES)] */
+} SvtHipRateTables;
+
+typedef struct SvtHipRateJob {
+    uint8_t tx_type;      /* below 16 */
+    uint8_t txb_skip_ctx; /* 0..12: ctx->luma_txb_skip_context / cb_ / cr_ */
+    uint8_t dc_sign_ctx;  /* 0..2:  ctx->luma_dc_sign_context / cb_ / cr_ */
+    uint8_t is_inter;     /* is_inter_mode(cand->pred_mode) */
+    uint8_t intra_dir;    /* 0..12, read for intra luma jobs only: cand->pred_mode, or fimode_to_intradir[cand->filter_intra_mode] when that is set;
+                           * any value on inter and chroma jobs */
+    uint8_t reserved[3];
+} SvtHipRateJob;
+
+typedef struct SvtHipCoeffRateDesc {
+    uint8_t  tx_size;                  /* TxSize shared by every job of this call */
+    uint8_t  plane_type;               /* 0 PLANE_TYPE_Y, 1 PLANE_TYPE_UV, shared */
+    uint8_t  reduced_tx_set;           /* frm_hdr->reduced_tx_set */
+    uint8_t  coeff_rate_est_lvl;       /* ctx->rate_est_ctrls.coeff_rate_est_lvl: selects the short-cuts above (luma); 1 = none */
+    uint8_t  mds_fast_coeff_est_level; /* ctx->mds_fast_coeff_est_level, not 0 */
+    uint8_t  mds_subres_step;          /* ctx->mds_subres_step, 0..2 */
+    uint8_t  reserved[2];
+    uint32_t n_jobs, n_groups;
+    const SvtHipRateJob    *jobs;      /* device pointers */
+    const SvtHipRateTables *tables;
+    const int32_t  *qcoeff;            /* [n_jobs][min(W,32)*min(H,32)]: SvtHipRdBatchDesc.qcoeff; 16-byte aligned where that is 256 coefficients or more */
+    const uint16_t *eob;               /* [n_jobs]: SvtHipRdBatchDesc.eob */
+    uint64_t       *bits;              /* [n_jobs] */
+    /* optional: rd_cost[j] = RDCOST(lambda, bits[j], dist[j * dist_stride]); dist_stride 0 counts as 1, 2 reads the first column of
+     * SvtHipRdBatchDesc.dist_coeff in place */
+    uint32_t        lambda, dist_stride;
+    const uint64_t *dist;
+    uint64_t       *rd_cost;           /* [n_jobs] */
+    /* optional, needs rd_cost: jobs group_start[g] .. group_start[g + 1] - 1 are the candidates of block g (ascending; an end beyond n_jobs is
+     * cut there).  best_job[g] is the job index of the first strict minimum of rd_cost, best_cost[g] its cost; a group that is empty or
+     * whose jobs are all undefined reports 0xFFFFFFFF and UINT64_MAX. */
+    const uint32_t *group_start;       /* [n_groups + 1] */
+    uint32_t       *best_job;          /* [n_groups] */
+    uint64_t       *best_cost;         /* [n_groups] */
+} SvtHipCoeffRateDesc;
+
+/* Enqueues one batch on the context stream (asynchronous).  Returns non-zero and enqueues nothing when the descriptor fails validation: a
+ * null context, descriptor or mandatory pointer (jobs, tables, qcoeff, eob, bits), tx_size >= 19, plane_type > 1, mds_subres_step > 2,
+ * mds_fast_coeff_est_level == 0, a qcoeff that is not 16-byte aligned for a size of 256 coefficients or more, rd_cost without dist, groups without rd_cost (or without one of
+ * group_start, best_job, best_cost).
+ * The jobs live in device memory, where the host cannot refuse them.  Where the reference is undefined -- eob above the coefficient count or
+ * a zero coefficient at scan[eob - 1] (it indexes base_eob_cost[..][-1]), a context or tx_type outside its table, an intra_dir above 12 on an intra luma job (the only jobs that read it) -- a job that
+ * would take the table path reads no table out of range and reports bits = rd_cost = UINT64_MAX (the convention of svt_hip_ssim_batch); its
+ * neighbours are not affected. */
+int    svt_hip_coeff_rate_batch(SvtHipContext *ctx, const SvtHipCoeffRateDesc *d);
+size_t svt_hip_coeff_rate_desc_size(void); /* sizeof(SvtHipCoeffRateDesc) as compiled */
+size_t svt_hip_rate_tables_size(void);     /* sizeof(SvtHipRateTables) as compiled */
 
 /* Full-pel motion-compensated prediction from ME results: every 16x16 PU copies the block of `ref` displaced by its
  * best integer MV (sb_best_mv = SvtHipMeResults.sb_best_mv, device pointer; list / ref_idx select the reference).

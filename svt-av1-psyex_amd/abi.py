@@ -206,6 +206,41 @@ VARIANCE_SIZES = [(4, 4), (4, 8), (4, 16), (8, 4), (8, 8), (8, 16), (8, 32), (16
                   (32, 32), (32, 64), (64, 16), (64, 32), (64, 64), (64, 128), (128, 64), (128, 128)]
 
 
+class LvMapCoeffCost(C.Structure):  # SvtHipLvMapCoeffCost
+    _fields_ = [("txb_skip_cost", (C.c_int32 * 2) * 13), ("base_eob_cost", (C.c_int32 * 3) * 4), ("base_cost", (C.c_int32 * 8) * 42),
+                ("eob_extra_cost", (C.c_int32 * 2) * 22), ("dc_sign_cost", (C.c_int32 * 2) * 3), ("lps_cost", (C.c_int32 * 26) * 21)]
+
+
+class LvMapEobCost(C.Structure):  # SvtHipLvMapEobCost
+    _fields_ = [("eob_cost", (C.c_int32 * 11) * 2)]
+
+
+class RateTables(C.Structure):  # SvtHipRateTables
+    _fields_ = [("coeff_fac_bits", (LvMapCoeffCost * 2) * 5), ("eob_frac_bits", (LvMapEobCost * 2) * 7),
+                ("intra_tx_type_fac_bits", ((((C.c_int32 * 17) * 13) * 4) * 3)), ("inter_tx_type_fac_bits", ((C.c_int32 * 17) * 4) * 4)]
+
+
+class RateJob(C.Structure):  # SvtHipRateJob
+    _fields_ = [("tx_type", C.c_uint8), ("txb_skip_ctx", C.c_uint8), ("dc_sign_ctx", C.c_uint8), ("is_inter", C.c_uint8), ("intra_dir", C.c_uint8),
+                ("reserved", C.c_uint8 * 3)]
+
+
+class CoeffRateDesc(C.Structure):  # SvtHipCoeffRateDesc
+    _fields_ = [("tx_size", C.c_uint8), ("plane_type", C.c_uint8), ("reduced_tx_set", C.c_uint8), ("coeff_rate_est_lvl", C.c_uint8),
+                ("mds_fast_coeff_est_level", C.c_uint8), ("mds_subres_step", C.c_uint8), ("reserved", C.c_uint8 * 2), ("n_jobs", C.c_uint32),
+                ("n_groups", C.c_uint32), ("jobs", C.c_void_p), ("tables", C.c_void_p), ("qcoeff", C.c_void_p), ("eob", C.c_void_p), ("bits", C.c_void_p),
+                ("lambda_", C.c_uint32), ("dist_stride", C.c_uint32), ("dist", C.c_void_p), ("rd_cost", C.c_void_p),
+                ("group_start", C.c_void_p), ("best_job", C.c_void_p), ("best_cost", C.c_void_p)]
+
+
+RATE_JOB_DTYPE = [("tx_type", "u1"), ("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"), ("is_inter", "u1"), ("intra_dir", "u1"), ("reserved", "u1", (3,))]
+# the members of SvtHipRateTables in their order, as int32 arrays (an LvMapCoeffCost is 970 int32, an LvMapEobCost 22)
+RATE_TABLE_SHAPES = [("coeff_fac_bits", (5, 2, 970)), ("eob_frac_bits", (7, 2, 2, 11)), ("intra_tx_type_fac_bits", (3, 4, 13, 17)),
+                     ("inter_tx_type_fac_bits", (4, 4, 17))]
+RATE_UNDEFINED = 0xFFFFFFFFFFFFFFFF  # bits / rd_cost / best_cost of a job (group) the reference leaves undefined
+RATE_NO_JOB = 0xFFFFFFFF             # best_job of such a group
+
+
 # ---- include/svt_hip_pme.h ----
 class Mv(C.Structure):
     _fields_ = [("row", C.c_int16), ("col", C.c_int16)]

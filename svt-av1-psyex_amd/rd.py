@@ -41,12 +41,23 @@ def grid_jobs(width, height, stride, tx_size, tx_type=0, quant_row=0, org=0):
 OPTIONAL_OUTPUTS = ("coeff", "qcoeff", "dqcoeff", "cul_level", "recon")  # eob .. sse are mandatory
 
 
-def run_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, want_recon=True, qmatrix=None, iqmatrix=None, outputs=None,
-            spare_jobs=0, fill=0, recon_init=None):
-    """Runs svt_hip_rd_batch on device copies of the inputs; returns numpy results.
-    outputs: the optional outputs to request, a subset of OPTIONAL_OUTPUTS; None = cul_level plus what want_coeffs / want_recon select.
-    Every per-job output array gets `spare_jobs` slots past n_jobs; all of them start as the byte `fill` and come back whole.
-    recon_init: the recon plane's content before the call (same shape and dtype as pred); None = a copy of pred."""
+class Enqueued:
+    """An RD batch on the context stream: `outs` = the per-job output arrays as device byte tensors by name, `recon` = the recon plane's tensor
+    or None.  The object also holds the uploaded inputs, so keep it until the stream has run."""
+
+    def __init__(self, outs, shapes, recon, slots, inputs):
+        self.outs, self.shapes, self.recon, self.slots, self._inputs = outs, shapes, recon, slots, inputs
+
+    def download(self):
+        """the per-job outputs as numpy arrays [slots, elements per job] (after ctx.sync())"""
+        return {name: self.outs[name].cpu().numpy().view(dt).reshape(self.slots, k) for name, (dt, k) in self.shapes.items()}
+
+
+def enqueue_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, want_recon=True, qmatrix=None, iqmatrix=None, outputs=None,
+                spare_jobs=0, fill=0, recon_init=None):
+    """Uploads the inputs and enqueues svt_hip_rd_batch on the context stream without waiting for it: returns an Enqueued, whose `outs` stay
+    on the device for a following batch on the same stream (rate.run_rate_device reads outs["qcoeff"] / outs["eob"] / outs["dist_coeff"] in
+    place).  Arguments as run_hip's."""
     import torch
     if outputs is None:
         outputs = ("cul_level",) + (("coeff", "qcoeff", "dqcoeff") if want_coeffs else ()) + (("recon",) if want_recon else ())
@@ -68,15 +79,27 @@ def run_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, wan
                         jobs=t_jobs.data_ptr(), quant_rows=t_q.data_ptr(), n_quant_rows=len(quant_rows), **desc_fields)
     for name, t in outs.items():
         setattr(d, name, t.data_ptr())
+    keep = [t_src, t_pred, t_jobs, t_q]
     if qmatrix is not None:
         t_qm, t_iqm = dev(np.asarray(qmatrix, np.uint8)), dev(np.asarray(iqmatrix, np.uint8))
         d.qmatrix, d.iqmatrix = t_qm.data_ptr(), t_iqm.data_ptr()
+        keep += [t_qm, t_iqm]
     torch.cuda.synchronize()
     ctx.check(api.lib().svt_hip_rd_batch(ctx._h, C.byref(d)), "svt_hip_rd_batch")
+    return Enqueued(outs, shapes, t_rec, len(jobs) + spare_jobs, keep)
+
+
+def run_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, want_recon=True, qmatrix=None, iqmatrix=None, outputs=None,
+            spare_jobs=0, fill=0, recon_init=None):
+    """Runs svt_hip_rd_batch on device copies of the inputs; returns numpy results.
+    outputs: the optional outputs to request, a subset of OPTIONAL_OUTPUTS; None = cul_level plus what want_coeffs / want_recon select.
+    Every per-job output array gets `spare_jobs` slots past n_jobs; all of them start as the byte `fill` and come back whole.
+    recon_init: the recon plane's content before the call (same shape and dtype as pred); None = a copy of pred."""
+    run = enqueue_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs, want_recon, qmatrix, iqmatrix, outputs, spare_jobs, fill, recon_init)
     ctx.sync()
-    res = {name: outs[name].cpu().numpy().view(dt).reshape(slots, k) for name, (dt, k) in shapes.items()}
-    if want_recon:
-        res["recon"] = t_rec.cpu().numpy().view(pred.dtype).reshape(pred.shape)
+    res = run.download()
+    if run.recon is not None:
+        res["recon"] = run.recon.cpu().numpy().view(pred.dtype).reshape(pred.shape)
     return res
 
 
