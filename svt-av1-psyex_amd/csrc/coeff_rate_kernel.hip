@@ -26,6 +26,7 @@
 #include <string.h>
 #include "svt_hip_internal.h"
 #include "../../include/svt_hip_dsp.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -49,23 +50,6 @@ struct RateParams {
     uint32_t c_div;           // MAX(1, mds_fast_coeff_est_level - mds_subres_step)
     uint32_t n_packs;
 };
-
-template <int G> __device__ __forceinline__ uint32_t group_sum(uint32_t v) { // over the G lanes of a group, in all of them
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
-template <int G> __device__ __forceinline__ uint32_t group_or(uint32_t v) {
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ void rate_wave_sync() { // the levels array is one wave's own: a wave-level barrier orders it
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // get_golomb_cost (rd_cost.c:90-97) of a level >= 1 + NUM_BASE_LEVELS + COEFF_BASE_RANGE = 15
 __device__ __forceinline__ uint32_t golomb_cost(uint32_t a) { return kCostLiteral * (2u * (32u - (uint32_t)__builtin_clz(a - 14u)) - 1u); }
@@ -172,7 +156,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) coeff_rate_kerne
 
         // svt_av1_txb_init_levels_c: min(|qcoeff|, 127) over the WHOLE block, in a zero frame
         for (int i = gl * 16; i < lev_bytes; i += G * 16) *reinterpret_cast<uint4 *>(lev + i) = make_uint4(0, 0, 0, 0);
-        rate_wave_sync();
+        wave_sync();
 #pragma unroll 1
         for (int it = 0; it < ITER; it++) {
             const int pos = (it * G + gl) * V;
@@ -188,7 +172,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) coeff_rate_kerne
             if constexpr (V == 4) *reinterpret_cast<uint32_t *>(lev + row * stride + col) = packed;
             else lev[row * stride + col] = (uint8_t)packed;
         }
-        rate_wave_sync();
+        wave_sync();
 
         uint32_t cost = 0, bad = 0;
         if (compute) {
@@ -252,7 +236,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) coeff_rate_kerne
                 p.d.rd_cost[job]    = bits == ~0ull ? ~0ull : ((bits * (uint64_t)p.d.lambda + 256ull) >> 9) + (dist << 7);
             }
         }
-        rate_wave_sync(); // the next job's zero fill must not overtake this one's reads
+        wave_sync(); // the next job's zero fill must not overtake this one's reads
     }
 }
 

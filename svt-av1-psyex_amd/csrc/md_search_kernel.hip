@@ -17,52 +17,12 @@
 #include <string.h>
 #include "svt_hip_internal.h"
 #include "../../include/svt_hip_md_search.h"
+#include "mv_cost.h"
+#include "wave_ops.h"
 
 namespace {
 typedef unsigned long long u64;
 typedef long long          i64;
-
-__device__ __forceinline__ int clip3(int lo, int hi, int v) { return v < lo ? lo : (v > hi ? hi : v); }
-
-struct MvCost {
-    SvtHipMv       ref_mv;
-    int            type, error_per_bit;
-    const int32_t *mvjcost, *row, *col;
-};
-
-// svt_mv_err_cost (mcomp.c:44-69)
-__device__ __forceinline__ int mv_err_cost(int16_t row, int16_t col, const MvCost &m) {
-    const int16_t dr = (int16_t)(row - m.ref_mv.row), dc = (int16_t)(col - m.ref_mv.col); // MV fields are int16
-    const int16_t ar = (int16_t)(dr < 0 ? -dr : dr), ac = (int16_t)(dc < 0 ? -dc : dc);
-    switch (m.type) {
-    case SVT_HIP_MV_COST_ENTROPY: {
-        const int joint = dr == 0 ? (dc == 0 ? 0 : 1) : (dc == 0 ? 2 : 3);
-        const int bits  = m.mvjcost[joint] + m.row[clip3(-(1 << 14), 1 << 14, dr)] + m.col[clip3(-(1 << 14), 1 << 14, dc)];
-        return (int)((((i64)bits * m.error_per_bit) + ((i64)1 << 13)) >> 14);
-    }
-    case SVT_HIP_MV_COST_L1_LOWRES: return (2 * (ar + ac)) >> 3;
-    case SVT_HIP_MV_COST_L1_MIDRES: return 0;
-    case SVT_HIP_MV_COST_L1_HDRES: return (ar + ac) >> 3;
-    case SVT_HIP_MV_COST_OPT: return (int)((((i64)((ar + ac) << 8) * m.error_per_bit) + ((i64)1 << 13)) >> 14);
-    default: return 0;
-    }
-}
-
-__device__ __forceinline__ u64 wave_min_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const u64 t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
 
 // one lane: SAD or (sum of differences, sum of squares) of a w x h block, byte by byte in dwords where the width allows
 __device__ __forceinline__ uint32_t lane_sad(const uint8_t *a, uint32_t as, const uint8_t *b, uint32_t bs, int w, int h) {
@@ -160,7 +120,7 @@ __global__ void __launch_bounds__(64) md_fullpel_kernel(const FullpelParams p) {
             best = key < best ? key : best;
         }
     }
-    best = wave_min_u64(best);
+    best = wave_min(best);
     if (lane == 0) {
         uint32_t out_cost = in_cost;
         int16_t  out_x = in_x, out_y = in_y;
@@ -213,8 +173,8 @@ __device__ __forceinline__ uint32_t wave_sub_pixel_variance(const uint8_t *a, ui
         sum += dd;
         sse += (uint32_t)(dd * dd);
     }
-    sum = wave_sum_i32(sum);
-    sse = wave_sum_u32(sse);
+    sum = wave_sum(sum);
+    sse = wave_sum(sse);
     sse_out = sse;
     return sse - (uint32_t)(((i64)sum * sum) / n);
 }
@@ -274,8 +234,8 @@ __device__ __forceinline__ uint32_t wave_upsampled_variance(const uint8_t *a, ui
         sum += dd;
         sse += (uint32_t)(dd * dd);
     }
-    sum = wave_sum_i32(sum);
-    sse = wave_sum_u32(sse);
+    sum = wave_sum(sum);
+    sse = wave_sum(sse);
     sse_out = sse;
     return sse - (uint32_t)(((i64)sum * sum) / n);
 }
@@ -366,8 +326,8 @@ __global__ void __launch_bounds__(64) md_subpel_kernel(const SubpelParams p) {
             sum += dd;
             sse += (uint32_t)(dd * dd);
         }
-        sum = wave_sum_i32(sum);
-        sse = wave_sum_u32(sse);
+        sum = wave_sum(sum);
+        sse = wave_sum(sse);
         const uint32_t var = sse - (uint32_t)(((i64)sum * sum) / n);
         const int block_var = (int)((var + ((1u << s.jb.log2_pels) >> 1)) >> s.jb.log2_pels);
         if (block_var < d.pred_variance_th) done = true;

@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "me_kernel.h"
+#include "wave_ops.h"
 
 // Diagnostic build only (-DSVT_HIP_ME_PROFILE): lane 0 accumulates shader-clock deltas per phase (private array) and adds
 // them to queue_head[16 + 2*i] (u64) when the wave retires.  Never defined in the shipped library.
@@ -199,26 +200,6 @@ struct Shared { // byte offsets into g_lds (pointers kept in a struct would lose
     int       cshift;
 };
 #define LDS(off) (g_lds + (off))
-
-// Orders the wave's own LDS traffic for the compiler: what one lane stored before this point, every lane may load after it.  The
-// hardware executes a wave's LDS instructions in order, so no instruction is needed -- only the compiler must not move memory
-// operations across (a lane reading what another lane wrote is invisible to its single-thread view of the program).
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
-__device__ __forceinline__ u64 wave_sum64(u64 v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += (u64)__shfl_xor((unsigned long long)v, o, 64);
-    return v;
-}
 
 __host__ __device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
 __host__ __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
@@ -432,36 +413,11 @@ __device__ __forceinline__ const uint8_t *uni_ptr(const uint8_t *p) {
     return reinterpret_cast<const uint8_t *>(((uintptr_t)uni((uint32_t)(a >> 32)) << 32) | uni((uint32_t)a));
 }
 
-// minimum over the wave's 64 lanes, in every lane's return value (SGPR): butterfly inside the 16-lane rows by DPP (min is idempotent, so the
-// mirror patterns serve), two row broadcasts, lane 63 holds the result -- no LDS traffic
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#define SVT_MIN_DPP(ctrl, rmask) { const uint32_t t_ = (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, ctrl, rmask, 0xF, false); v = t_ < v ? t_ : v; }
-    SVT_MIN_DPP(0xB1, 0xF)  // quad_perm [1,0,3,2]
-    SVT_MIN_DPP(0x4E, 0xF)  // quad_perm [2,3,0,1]
-    SVT_MIN_DPP(0x141, 0xF) // row_half_mirror
-    SVT_MIN_DPP(0x140, 0xF) // row_mirror
-    SVT_MIN_DPP(0x142, 0xA) // row_bcast:15 -> rows 1, 3
-    SVT_MIN_DPP(0x143, 0xC) // row_bcast:31 -> rows 2, 3
-#undef SVT_MIN_DPP
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-// sum over the wave's 64 lanes (mod 2^32), in every lane's return value (SGPR), by DPP: no LDS traffic
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#define SVT_SUM_DPP(ctrl, rmask, bc) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rmask, 0xF, bc);
-    SVT_SUM_DPP(0x111, 0xF, true)  // row_shr:1 (zero fill)
-    SVT_SUM_DPP(0x112, 0xF, true)  // row_shr:2
-    SVT_SUM_DPP(0x114, 0xF, true)  // row_shr:4
-    SVT_SUM_DPP(0x118, 0xF, true)  // row_shr:8: lane 15 of a row holds the row's sum
-    SVT_SUM_DPP(0x142, 0xA, false) // row_bcast:15 -> rows 1, 3
-    SVT_SUM_DPP(0x143, 0xC, false) // row_bcast:31 -> rows 2, 3
-#undef SVT_SUM_DPP
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
 // the wave's smallest (sad, pos) pair as sad << 32 | pos -- the reference's "first minimum in raster order": the smallest SAD, then among
 // its lanes the smallest position word (y << 16 | x); ~0 when no lane holds a result
 __device__ __forceinline__ u64 wave_min_key(uint32_t sad, uint32_t pos) {
-    const uint32_t smin = wave_min_u32(sad);
-    const uint32_t pmin = wave_min_u32(sad == smin ? pos : 0xFFFFFFFFu);
+    const uint32_t smin = wave_min_dpp(sad);
+    const uint32_t pmin = wave_min_dpp(sad == smin ? pos : 0xFFFFFFFFu);
     return ((u64)smin << 32) | pmin;
 }
 
@@ -831,7 +787,7 @@ __device__ __forceinline__ bool small_direct_ok(const St &st, int *q_total = nul
         per = ((w + 7) >> 3) * h;
     }
     if (!__all(ok) || (bw != 32 && bw != 64) || nreq > kMaxReq || nreq <= 0) return false;
-    const int q = (int)wave_sum_u32((uint32_t)per);
+    const int q = (int)wave_sum_dpp((uint32_t)per);
     if (q_total) *q_total = q;
     return q <= kThreads;
 }
@@ -892,7 +848,7 @@ template <int DEPTH = 1> __device__ __forceinline__ bool run_small_searches_dire
     PROF(23);
     for (int rq = 0; rq < nreq; rq++) { // lane <-> position in raster order: the first minimum is the smallest (sad << 6 | lane) (sad < 2^20)
         const int      wr = (int16_t)uni((uint32_t)st.req[rq].sa_w), hr = (int16_t)uni((uint32_t)st.req[rq].sa_h);
-        const uint32_t k32 = wave_min_u32(lane < wr * hr ? (sad[rq * kNarrowMaxPos + lane] << 6) | (uint32_t)lane : 0xFFFFFFFFu);
+        const uint32_t k32 = wave_min_dpp(lane < wr * hr ? (sad[rq * kNarrowMaxPos + lane] << 6) | (uint32_t)lane : 0xFFFFFFFFu);
         const int      wl = (int)(k32 & 63u), wy = (int)uni(div_by_rcp((uint32_t)wl, rcp_of((uint32_t)wr))), wx = wl - wy * wr;
         if (lane == 0) st.req_key[rq] = ((u64)(k32 >> 6) << 32) | ((uint32_t)wy << 16) | (uint32_t)wx;
     }
@@ -945,18 +901,6 @@ __device__ __forceinline__ void push_hme_req(St &st, CParams &p, int level, CPla
 // ---------------------------------------------------------------------------------------------
 // Integer search: 85 square PUs per position
 // ---------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ uint32_t dpp_quad_sum(uint32_t v) {
-    // sum over the 4 lanes of a quad, result in all 4 lanes
-    uint32_t t = v + (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
-    return t + (uint32_t)__builtin_amdgcn_mov_dpp((int)t, 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, true);
-}
-
-__device__ __forceinline__ uint32_t sum16_of_quads(uint32_t v) {
-    // v is uniform inside each quad; returns the sum of the 4 quads of each 16-lane row, in all 16 lanes
-    uint32_t t = v + (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141 /* row_half_mirror */, 0xF, 0xF, true);
-    return t + (uint32_t)__builtin_amdgcn_mov_dpp((int)t, 0x140 /* row_mirror */, 0xF, 0xF, true);
-}
 
 __device__ __forceinline__ void upd(u64 &best, uint32_t sad, uint32_t ord) {
     const u64 k = ((u64)sad << 32) | ord;
@@ -1083,8 +1027,8 @@ __device__ __forceinline__ void run_me_searches(Shared &sh, CParams &p, const Me
 #pragma unroll
                             for (int j = 0; j < 4; j++) v8[j] = (uint32_t)((acc[j] >> (16 * i)) & 0xFFFF);
                             const uint32_t v16 = (v8[0] + v8[1]) + (v8[2] + v8[3]);
-                            const uint32_t v32 = dpp_quad_sum(v16);
-                            const uint32_t v64 = sum16_of_quads(v32);
+                            const uint32_t v32 = quad_sum(v16);
+                            const uint32_t v64 = row16_sum_of_quads(v32);
                             if (x < w && live) { // x: wave-uniform; live: whole 16-lane rows (the DPP sums above never leave a row)
                                 const uint32_t ord = ord0 + (uint32_t)x;
 #pragma unroll
@@ -1488,7 +1432,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
 #pragma unroll
         for (int k = 0; k < 8; k++)
             if (k < nzz) { // uniform
-                const uint32_t t = wave_sum_u32(zz_sum[k]);
+                const uint32_t t = wave_sum_dpp(zz_sum[k]);
                 if (tid == 0) st.req_key[k] = (u64)t << 32; // where zz_post looks for the result of search k
             }
         wave_sync();
@@ -1519,7 +1463,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 z = (z * 64 * 64) / (st.b64_w * st.b64_h);
                 st.zz_sad[li][ri] = z;
             }
-            const uint32_t best = wave_min_u32(z);
+            const uint32_t best = wave_min_dpp(z);
             if (d.temporal_layer_index > 0 && best < c.zz_sad_th && valid && ri >= 1)
                 if ((uint32_t)((z - best) * 100) > (uint32_t)(c.zz_sad_pct * best)) st.do_ref[li][ri] = 0; // (every list is searched when the layer is above 0)
             if (c.me_safe_limit_zz_th) {
@@ -1600,7 +1544,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                     }
                 }
             }
-            const uint32_t best_sad = wave_min_u32(m);
+            const uint32_t best_sad = wave_min_dpp(m);
             if (d.temporal_layer_index > 0 && best_sad < c.phme_sad_th && valid && ri >= 1 && st.do_ref[li][ri]) // (every list is searched when the layer is above 0)
                 if ((uint32_t)((m - best_sad) * 100) > (uint32_t)(c.phme_sad_pct * best_sad)) st.do_ref[li][ri] = 0;
         };
@@ -1779,7 +1723,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 const u64  hs = slot ? st.hme_sad64[li][ri] : ~0ull;
                 const uint16_t th = c.prune_ref_if_hme_sad_dev_bigger_than_th;
                 if (c.enable_me_hme_ref_pruning && th != 0xFFFF) {
-                    const u64 best = (u64)wave_min_u32((uint32_t)(hs < 0xFFFFFFFFull ? hs : 0xFFFFFFFFull)); // hme_sad is a 32-bit quantity here
+                    const u64 best = (u64)wave_min_dpp((uint32_t)(hs < 0xFFFFFFFFull ? hs : 0xFFFFFFFFull)); // hme_sad is a 32-bit quantity here
                     if (slot && ri >= 1 && (hs - best) * 100 > (u64)th * best) st.do_ref[li][ri] = 0;
                 }
                 if (c.enable_me_sr_adjustment && slot) {
@@ -2042,7 +1986,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                     const int  li = (tid >> 2) & 1, ri = tid & 3;
                     const bool slot = tid < 8;
                     const u64  hs = slot ? st.hme_sad64[li][ri] : ~0ull;
-                    const u64  best = (u64)wave_min_u32((uint32_t)(hs < 0xFFFFFFFFull ? hs : 0xFFFFFFFFull));
+                    const u64  best = (u64)wave_min_dpp((uint32_t)(hs < 0xFFFFFFFFull ? hs : 0xFFFFFFFFull));
                     if (slot && ri >= 1 && (hs - best) * 100 > (u64)th * best) st.do_ref[li][ri] = 0;
                 }
             }
@@ -2168,7 +2112,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 const uint32_t d32 = wave_sum(tid < 4 ? st.me_dist[1 + tid] : 0u);
                 const u64       mean = d8 / 64;
                 const long long dd   = (long long)v8 - (long long)mean;
-                const u64       ssq  = wave_sum64((u64)(dd * dd));
+                const u64       ssq  = wave_sum((u64)(dd * dd));
                 // perform_gm_detection (:2838-2961): lane i classifies PU i of the list; the per-(list, ref, component, sign)
                 // counts of the reference's cnt[] are popcounts of ballots
                 uint8_t stationary = 0, allow_gm = 0;
@@ -2253,7 +2197,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
     if (MODE == SVT_HIP_ME_PROFILE_MODE) PROF_FLUSH(hdr.queue_head + 16);
 #endif
     if ((MODE == kMeFull || MODE == kMeMid1) && has_dense && hdr.count_dense) { // counters of the context's diagnostics entry (svt_hip_me_dense_counters): uniform
-        const uint32_t h = wave_sum_u32(n_hit), m = wave_sum_u32(n_miss);
+        const uint32_t h = wave_sum_dpp(n_hit), m = wave_sum_dpp(n_miss);
         if (tid == 0) {
             atomicAdd(reinterpret_cast<unsigned long long *>(hdr.queue_head + SVT_HIP_ME_COUNTER_WORD), (unsigned long long)h);
             atomicAdd(reinterpret_cast<unsigned long long *>(hdr.queue_head + SVT_HIP_ME_COUNTER_WORD) + 1, (unsigned long long)m);

@@ -1,0 +1,38 @@
+// mv_cost.h -- the MV rate term of the mode-decision motion searches (pme_kernel.hip, md_search_kernel.hip): the reference's
+// svt_mv_err_cost (Codec/mcomp.c:44-69; mcomp.h:135-138, rd_cost.c:55-60) with its six cost modes, the one place it is restated.
+#ifndef SVT_HIP_MV_COST_H
+#define SVT_HIP_MV_COST_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/svt_hip_pme.h"
+
+namespace {
+
+__device__ __forceinline__ int clip3(int lo, int hi, int v) { return v < lo ? lo : (v > hi ? hi : v); }
+
+struct MvCost {
+    SvtHipMv       ref_mv;
+    int            type, error_per_bit; // type: SVT_HIP_MV_COST_*
+    const int32_t *mvjcost, *row, *col; // the joint and the component cost tables, read for SVT_HIP_MV_COST_ENTROPY only
+};
+
+// svt_mv_err_cost of the int16 vector (row, col) against m.ref_mv
+__device__ __forceinline__ int mv_err_cost(int16_t row, int16_t col, const MvCost &m) {
+    const int16_t dr = (int16_t)(row - m.ref_mv.row), dc = (int16_t)(col - m.ref_mv.col); // MV fields are int16
+    const int16_t ar = (int16_t)(dr < 0 ? -dr : dr), ac = (int16_t)(dc < 0 ? -dc : dc);
+    switch (m.type) {
+    case SVT_HIP_MV_COST_ENTROPY: {
+        const int joint = dr == 0 ? (dc == 0 ? 0 : 1) : (dc == 0 ? 2 : 3); // svt_av1_get_mv_joint
+        const int bits  = m.mvjcost[joint] + m.row[clip3(-(1 << 14), 1 << 14, dr)] + m.col[clip3(-(1 << 14), 1 << 14, dc)];
+        return (int)((((long long)bits * m.error_per_bit) + (1ll << 13)) >> 14); // ROUND_POWER_OF_TWO_64(.., RDDIV_BITS + AV1_PROB_COST_SHIFT - RD_EPB_SHIFT + 4)
+    }
+    case SVT_HIP_MV_COST_L1_LOWRES: return (2 * (ar + ac)) >> 3;
+    case SVT_HIP_MV_COST_L1_MIDRES: return 0;
+    case SVT_HIP_MV_COST_L1_HDRES: return (ar + ac) >> 3;
+    case SVT_HIP_MV_COST_OPT: return (int)((((long long)((ar + ac) << 8) * m.error_per_bit) + (1ll << 13)) >> 14);
+    default: return 0;
+    }
+}
+
+} // namespace
+#endif

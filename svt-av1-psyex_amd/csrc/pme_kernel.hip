@@ -12,31 +12,12 @@
 #include "svt_hip_internal.h"
 #include "leaf_guard.h"
 #include "../../include/svt_hip_pme.h"
+#include "mv_cost.h"
+#include "wave_ops.h"
 
 namespace {
 typedef unsigned long long u64;
 typedef long long          i64;
-
-__device__ __forceinline__ int clip3(int lo, int hi, int v) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// svt_mv_err_cost (mcomp.c:44-69) of the int16 vector (row, col) against ref_mv
-__device__ __forceinline__ int mv_err_cost(int16_t row, int16_t col, SvtHipMv ref_mv, int type, int error_per_bit, const int32_t *mvjcost, const int32_t *cost_row,
-                                           const int32_t *cost_col) {
-    const int16_t dr = (int16_t)(row - ref_mv.row), dc = (int16_t)(col - ref_mv.col); // MV fields are int16
-    const int16_t ar = (int16_t)(dr < 0 ? -dr : dr), ac = (int16_t)(dc < 0 ? -dc : dc);
-    switch (type) {
-    case SVT_HIP_MV_COST_ENTROPY: {
-        const int joint = dr == 0 ? (dc == 0 ? 0 : 1) : (dc == 0 ? 2 : 3); // svt_av1_get_mv_joint
-        const int bits  = mvjcost[joint] + cost_row[clip3(-(1 << 14), 1 << 14, dr)] + cost_col[clip3(-(1 << 14), 1 << 14, dc)];
-        return (int)((((i64)bits * error_per_bit) + ((i64)1 << 13)) >> 14); // ROUND_POWER_OF_TWO_64(.., RDDIV_BITS + AV1_PROB_COST_SHIFT - RD_EPB_SHIFT + 4)
-    }
-    case SVT_HIP_MV_COST_L1_LOWRES: return (2 * (ar + ac)) >> 3;
-    case SVT_HIP_MV_COST_L1_MIDRES: return 0;
-    case SVT_HIP_MV_COST_L1_HDRES: return (ar + ac) >> 3;
-    case SVT_HIP_MV_COST_OPT: return (int)((((i64)((ar + ac) << 8) * error_per_bit) + ((i64)1 << 13)) >> 14);
-    default: return 0;
-    }
-}
 
 struct PmeParams { SvtHipPmeBatchDesc d; };
 
@@ -49,6 +30,7 @@ __global__ void __launch_bounds__(64) pme_sad_kernel(const PmeParams p) {
     const int n_rows   = jb.sa_h > 0 ? (jb.sa_h - 1) / step + 1 : 0;
     const int n_items  = n_groups * 2 * n_rows;                               // quads
     const uint8_t *src = p.d.src + jb.src_offset, *ref = p.d.ref + jb.ref_offset;
+    const MvCost mc = {jb.ref_mv, p.d.mv_cost_type, p.d.error_per_bit, p.d.mvjcost, p.d.mvcost[0], p.d.mvcost[1]};
     u64 best = ~0ull;
     for (int it = lane; it < n_items; it += 64) {
         const int yi = it / (n_groups * 2), q = it - yi * (n_groups * 2), g = q >> 1, half = q & 1;
@@ -74,13 +56,12 @@ __global__ void __launch_bounds__(64) pme_sad_kernel(const PmeParams p) {
         for (int i = 0; i < 4; i++) {
             const uint32_t px = (uint32_t)(jb.start_x + xs + i), py = (uint32_t)(jb.start_y + ys); // refinement_pos_x / _y (uint32 in the reference)
             const int16_t  col = (int16_t)(jb.mvx + (px * 8)), row = (int16_t)(jb.mvy + (py * 8));
-            const uint32_t cost = sad[i] + (uint32_t)mv_err_cost(row, col, jb.ref_mv, p.d.mv_cost_type, p.d.error_per_bit, p.d.mvjcost, p.d.mvcost[0], p.d.mvcost[1]);
+            const uint32_t cost = sad[i] + (uint32_t)mv_err_cost(row, col, mc);
             const u64      key  = ((u64)cost << 32) | (uint32_t)((yi * n_groups + g) * 8 + 4 * half + i); // visiting order: rows, then groups, then columns
             best = key < best ? key : best;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const u64 t = __shfl_xor(best, o, 64); best = t < best ? t : best; }
+    best = wave_min(best);
     if (lane == 0) {
         uint32_t out_cost = jb.best_cost;
         int16_t  out_x = jb.best_mvx, out_y = jb.best_mvy;

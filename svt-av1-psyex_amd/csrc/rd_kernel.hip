@@ -30,23 +30,6 @@ struct RdParams {
 
 template <typename T> __device__ __forceinline__ int ldpix(const void *p, size_t i) { return (int)static_cast<const T *>(p)[i]; }
 
-// reductions over the LW lanes (a power of two) that work on one block
-template <int LW> __device__ __forceinline__ u64 seg_sum_u64(u64 v) {
-#pragma unroll
-    for (int o = LW / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <int LW> __device__ __forceinline__ uint32_t seg_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = LW / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <int LW> __device__ __forceinline__ uint32_t seg_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = LW / 2; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
-    return v;
-}
-
 __host__ __device__ constexpr int rd_lanes_per_block(int ts) { return tx_wide(ts) > tx_high(ts) ? tx_wide(ts) : tx_high(ts); }
 __host__ __device__ constexpr int rd_blocks_per_wave(int ts) { return 64 / rd_lanes_per_block(ts); }
 
@@ -139,7 +122,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     // one answer for the wave (all its blocks): every residual small enough for the 24-bit multiplies of the forward passes?
     // one answer for the wave (all its blocks): small enough data for the three-instruction butterflies?  The column pass sees the residual
     // shifted up by fsh[0] (0 or 2)
-    const bool fast_col = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)seg_max_u32<64>(rmax)) << (fsh[0] > 0 ? fsh[0] : 0), H);
+    const bool fast_col = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(rmax)) << (fsh[0] > 0 ? fsh[0] : 0), H);
     __syncthreads();
     // forward columns (av1_tranform_two_d_core_c, transforms.c:2287-2308)
     uint32_t cmax = 0; // largest |column output| of this lane
@@ -154,7 +137,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         for (int r = 0; r < H; r++) A[r * PA + oc] = x[r];
         cmax = vec_max_abs<H>(x);
     }
-    const bool fast_row = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)seg_max_u32<64>(cmax)), W); // the row pass's input
+    const bool fast_row = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(cmax)), W); // the row pass's input
     __syncthreads();
     // forward rows (:2310-2323)
     uint32_t comax = 0; // largest |coefficient| of this lane
@@ -172,7 +155,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         comax = vec_max_abs<W>(x);
     }
     // coefficients below 2^16 in every block of the wave: the quantizer's products fit 24-bit multiplies (see the loop below)
-    const bool q24 = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg_max_u32<64>(comax)) < (1u << 16);
+    const bool q24 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(comax)) < (1u << 16);
     __syncthreads();
     // 64-point sizes keep the top-left 32x32 (svt_handle_transform*_c, transforms.c:2374-2505)
     // partial-frequency shapes (av1_estimate_transform_N2 / _N4 / _ONLY_DC, transforms.c:2633-2948): the pruned 1-D kernels
@@ -186,7 +169,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
             const int r = i / W, c = i - r * W;
             if (r >= HP || c >= WP) { const int32_t v = A[r * PA + c]; tq += (u64)((i64)v * v); }
         }
-        tq = seg_sum_u64<LW>(tq);
+        tq = group_sum<LW>(tq);
     }
     if constexpr (W > 32 || H > 32) __syncthreads(); // the compaction below overwrites discarded coefficients
     // SATD, quantize, coefficient-domain distortion over the kept NP coefficients (packed index rc = r*WP + c).  The
@@ -340,11 +323,11 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         if (q_out) q_out[rc] = qs;
         if (dq_out) dq_out[rc] = dqs;
     }
-    satd  = seg_sum_u32<LW>(satd);
-    qsum  = seg_sum_u32<LW>(qsum);
-    eob   = seg_max_u32<LW>(eob);
-    dres  = seg_sum_u64<LW>(dres);
-    dpred = seg_sum_u64<LW>(dpred);
+    satd  = group_sum<LW>(satd);
+    qsum  = group_sum<LW>(qsum);
+    eob   = group_max<LW>(eob);
+    dres  = group_sum<LW>(dres);
+    dpred = group_sum<LW>(dpred);
     __syncthreads();
     // inverse rows (inv_txfm2d_add_c, inv_transforms.c:2497-2511): discarded frequencies are zero
     int32_t xr[W];
@@ -358,7 +341,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         }
         irmax = vec_max_abs<W>(xr);
     }
-    const bool fast_irow = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)seg_max_u32<64>(irmax)), W); // wave-uniform
+    const bool fast_irow = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(irmax)), W); // wave-uniform
     uint32_t icmax = 0; // largest |row-pass output|: the column pass's input
     if (l < H) {
         if (fast_irow) inv_1d<W, ROW_CLAMP, 2>(xr, ht); else inv_1d<W, ROW_CLAMP, 1>(xr, ht);
@@ -367,7 +350,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         for (int c = 0; c < W; c++) A[l * PA + c] = xr[c];
         icmax = vec_max_abs<W>(xr);
     }
-    const bool fast_icol = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)seg_max_u32<64>(icmax)), H);
+    const bool fast_icol = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(icmax)), H);
     __syncthreads();
     // inverse columns + reconstruction + SSE (:2513-2534; svt_spatial_full_distortion_kernel / 16-bit variant)
     u64 sse = 0;
@@ -416,7 +399,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
             }
         }
     }
-    sse = seg_sum_u64<LW>(sse);
+    sse = group_sum<LW>(sse);
     if (l == 0 && valid) {
         p.d.eob[job]  = (uint16_t)eob;
         p.d.satd[job] = satd;
@@ -468,7 +451,7 @@ template <int TS, int BD, typename Pix> __global__ void __launch_bounds__(64, rd
         }
         irmax = vec_max_abs<W>(xr);
     }
-    const bool fast_irow = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)seg_max_u32<64>(irmax)), W); // wave-uniform
+    const bool fast_irow = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(irmax)), W); // wave-uniform
     uint32_t icmax = 0; // largest |row-pass output|: the column pass's input
     if (l < H) {
         if (fast_irow) inv_1d<W, ROW_CLAMP, 2>(xr, ht); else inv_1d<W, ROW_CLAMP, 1>(xr, ht);
@@ -477,7 +460,7 @@ template <int TS, int BD, typename Pix> __global__ void __launch_bounds__(64, rd
         for (int c = 0; c < W; c++) A[l * PA + c] = xr[c];
         icmax = vec_max_abs<W>(xr);
     }
-    const bool fast_icol = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)seg_max_u32<64>(icmax)), H);
+    const bool fast_icol = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(icmax)), H);
     __syncthreads();
     if (l < W) { // inverse columns (:2513-2534)
         int32_t x[H];
@@ -546,7 +529,7 @@ template <int TS> __global__ void __launch_bounds__(64, rd_waves_per_simd(TS)) f
     }
     // one answer for the wave (all its blocks): small enough data for the three-instruction butterflies?  The column pass sees the residual
     // shifted up by fsh[0] (0 or 2)
-    const bool fast_col = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)seg_max_u32<64>(rmax)) << (fsh[0] > 0 ? fsh[0] : 0), H); // see kFwdMul24MaxResidual
+    const bool fast_col = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(rmax)) << (fsh[0] > 0 ? fsh[0] : 0), H); // see kFwdMul24MaxResidual
     __syncthreads();
     uint32_t cmax = 0;
     if (l < W) { // columns (:2287-2308)
@@ -560,7 +543,7 @@ template <int TS> __global__ void __launch_bounds__(64, rd_waves_per_simd(TS)) f
 #pragma unroll
         for (int r = 0; r < H; r++) { A[r * PA + oc] = x[r]; cmax = max(cmax, (uint32_t)(x[r] < 0 ? -x[r] : x[r])); }
     }
-    const bool fast_row = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)seg_max_u32<64>(cmax)), W); // the row pass's input
+    const bool fast_row = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(cmax)), W); // the row pass's input
     __syncthreads();
     if (l < H) { // rows (:2310-2323)
         int32_t x[W];
@@ -793,10 +776,7 @@ extern "C" int svt_hip_fwd_txfm_batch(SvtHipContext *ctx, const SvtHipFwdTxBatch
 // The cosine table (constant memory of this device's copy of the code object) and the inverse scan orders, made once per
 // context at svt_hip_context_create: no lazily initialised process-global state (several threads, several GPUs per process).
 int svt_hip_rd_tables_init(SvtHipContext *ctx) {
-    int32_t cosp[4][64];
-    for (int b = 0; b < 4; b++)
-        for (int j = 0; j < 64; j++) cosp[b][j] = (int32_t)(cos(3.14159265358979323846 * j / 128.0) * (double)(1 << (10 + b)) + 0.5);
-    SVT_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_cospi), cosp, sizeof(cosp)));
+    SVT_HIP_CHECK(ctx, txfm_upload_cospi());
     const size_t bytes = sizeof(int16_t) * 19 * 3 * 1024;
     int16_t *tab = static_cast<int16_t *>(calloc(1, bytes)), scan[1024];
     if (!tab) return svt_hip_fail(ctx, SVT_HIP_ERR_NO_MEMORY, "iscan tables");

@@ -23,6 +23,7 @@
 #include "svt_hip_internal.h"
 #include "leaf_guard.h"
 #include "psy_energy.h"
+#include "wave_ops.h"
 #include "../../include/svt_hip_dsp.h"
 #include "../../include/svt_hip_leaf.h"
 
@@ -36,21 +37,6 @@ struct SsimParams {
     SvtHipSsimBatchDesc d;
     int unclamped; // the pointer-level tile entries: the raw score of a one-tile job (svt_ssim_*_c return it unclamped)
 };
-
-// sums over the lanes of a quad / of an 8-lane group, in all of them (DPP, no LDS traffic)
-__device__ __forceinline__ uint32_t quad_sum(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
-    return v + (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, true);
-}
-__device__ __forceinline__ uint32_t oct_sum(uint32_t v) {
-    v = quad_sum(v);
-    return v + (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141 /* row_half_mirror: the other quad of the 8 */, 0xF, 0xF, true);
-}
-__device__ __forceinline__ u64 wave_sum64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // C's truncating double -> uint64_t conversion of 0 <= x < 2^64, as two exact 32-bit halves (the compiler's own lowering has an fma in it;
 // this one is exact without: hi * 2^32 is exact and so is x - hi * 2^32, a multiple of x's ulp below 2^32)
@@ -122,12 +108,6 @@ __device__ __forceinline__ bool job_ok(const SvtHipBlockJob &jb) {
     return jb.width >= 4 && jb.width <= 128 && !(jb.width & 3) && jb.height >= 4 && jb.height <= 128 && !(jb.height & 3) && !jb.subpel_x && !jb.subpel_y;
 }
 
-__device__ __forceinline__ void ssim_wave_sync() { // the LDS of these kernels is one wave's own: a wave-level barrier orders it
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // one plain job by one wave
 template <typename Pix> __device__ __forceinline__ void ssim_job(const SsimParams &p, double *sc, uint32_t job, int lane) {
     const SvtHipBlockJob jb = p.d.jobs[job];
@@ -152,10 +132,10 @@ template <typename Pix> __device__ __forceinline__ void ssim_job(const SsimParam
             [[clang::always_inline]] b = psy_tile_energy<Pix>(rv, n);
             e += (u64)(uint32_t)(a > b ? a - b : b - a);
         }
-        e = wave_sum64(e);
+        e = wave_sum(e);
         e = sizeof(Pix) == 1 ? e >> 1 : e << 2;
     }
-    ssim_wave_sync();
+    wave_sync();
     if (lane == 0) { // ssim_{8x8,4x4}_blocks: the ordered sum of the clamped scores, then the division by the tile count
         const int nt = t8 ? (w >> 3) * (h >> 3) : (w >> 2) * (h >> 2);
         double tot = 0;
@@ -187,7 +167,7 @@ template <typename Pix> __device__ __forceinline__ void ssim_pyramid(const SsimP
         [[clang::always_inline]] b = psy_tile_energy<Pix>(rv, 8);
         e8[lane] = (uint32_t)(a > b ? a - b : b - a);
     }
-    ssim_wave_sync();
+    wave_sync();
     for (int z = lane; z < SVT_HIP_PYRAMID_BLOCKS; z += 64) {
         int n, k;
         if (z == 0) { n = 64; k = 0; }

@@ -113,6 +113,8 @@ int    svt_hip_me_launch(SvtHipContext *ctx, SvtHipLane *lane, const MeKernelPar
 int    svt_hip_me_pictures_on_lane(SvtHipContext *ctx, SvtHipLane *lane, uint32_t n_pictures, const SvtHipMeJob *jobs);
 // pictures.hip
 int    svt_hip_scratch(SvtHipContext *ctx, SvtHipLane *lane, size_t bytes, void **out);
+// stats_kernel.hip: launches hadamard_kernel for the pointer-level Hadamard entries (not exported)
+__attribute__((visibility("hidden"))) hipError_t svt_hip_hadamard_launch(SvtHipContext *ctx, const int16_t *src, int stride, int n, int32_t *coeff);
 // rd_kernel.hip: cosine / inverse-scan tables of the context's device
 int    svt_hip_rd_tables_init(SvtHipContext *ctx);
 void   svt_hip_rd_tables_free(SvtHipContext *ctx);

@@ -38,12 +38,6 @@ struct TplParams {
     int             size, k, nbx, nby, nb64x, sub;
 };
 
-__device__ __forceinline__ void wave_sync() { // LDS hand-off between the lanes of ONE wave (other waves of the workgroup carry on)
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-}
-
 __device__ __forceinline__ const uint8_t *pix(const SvtHipPlaneDesc &p, int x, int y) {
     return p.buffer_y + (ptrdiff_t)(p.org_y + y) * p.stride_y + p.org_x + x;
 }
@@ -57,8 +51,8 @@ __device__ int dc_value(const SvtHipPlaneDesc &p, int x, int y, int S, int W, in
         if (y > 0) sa = (x + l < W) ? *pix(p, x + l, y - 1) : 127;
         if (x > 0) sl = (y + l < H) ? *pix(p, x - 1, y + l) : 129;
     }
-    sa = wave_sum_u32(sa);
-    sl = wave_sum_u32(sl);
+    sa = wave_sum(sa);
+    sl = wave_sum(sl);
     if (x > 0 && y > 0) return (int)((sa + sl + S) / (2 * S));
     if (x > 0) return (int)((sl + S / 2) / S);
     if (y > 0) return (int)((sa + S / 2) / S);
@@ -82,7 +76,7 @@ template <int TS> __device__ int64_t tx_chain(int32_t *A, int l, int pf, const S
 #pragma unroll
         for (int r = 0; r < H; r++) A[r * PA + l] = x[r];
     }
-    wave_sync();
+    wave_sync_workgroup_fences();
     if (l < H) { // forward rows
         int32_t x[W];
 #pragma unroll
@@ -96,7 +90,7 @@ template <int TS> __device__ int64_t tx_chain(int32_t *A, int l, int pf, const S
 #pragma unroll
         for (int c = 0; c < W; c++) A[l * PA + c] = x[c];
     }
-    wave_sync();
+    wave_sync_workgroup_fences();
     // svt_av1_quantize_fp (quantize_fp_helper_c, 8-bit, log_scale 0, no matrix) + svt_av1_block_error over the kept coefficients
     const int keep_w = pf == 3 ? 1 : (W >> pf), keep_h = pf == 3 ? 1 : (H >> pf);
     uint32_t eob = 0;
@@ -118,10 +112,10 @@ template <int TS> __device__ int64_t tx_chain(int32_t *A, int l, int pf, const S
         err += (u64)(dd * dd);
         A[r * PA + c] = dqs;
     }
-    eob = wave_max_u32(eob);
-    err = wave_sum_u64(err);
+    eob = wave_max(eob);
+    err = wave_sum(err);
     eob_out = eob;
-    wave_sync();
+    wave_sync_workgroup_fences();
     if (inv && eob) { // inverse DCT_DCT (inv_txfm2d_add_c, inv_transforms.c:2497-2534), 8-bit clamps
         if (l < H) {
             int32_t xr[W];
@@ -136,7 +130,7 @@ template <int TS> __device__ int64_t tx_chain(int32_t *A, int l, int pf, const S
 #pragma unroll
             for (int c = 0; c < W; c++) A[l * PA + c] = xr[c];
         }
-        wave_sync();
+        wave_sync_workgroup_fences();
         if (l < W) {
             int32_t x[H];
 #pragma unroll
@@ -146,7 +140,7 @@ template <int TS> __device__ int64_t tx_chain(int32_t *A, int l, int pf, const S
 #pragma unroll
             for (int r = 0; r < H; r++) A[r * PA + l] = x[r];
         }
-        wave_sync();
+        wave_sync_workgroup_fences();
     }
     const int shift = TS == 3 ? 0 : 2; // TX_32X32 (get_quantize_error, src_ops_process.c:225-249)
     const int64_t re = (int64_t)(err >> shift);
@@ -215,7 +209,7 @@ template <int TS> __global__ void __launch_bounds__(64) tpl_src_kernel(const Tpl
         const int dc = dc_value(d.cur, b.x, b.y, S, cw, ch, l);
         uint32_t sad = 0;
         for (int i = l; i < S * S; i += 64) { const int r = i / S, c = i - r * S; sad += (uint32_t)abs((int)*pix(d.cur, b.x + c, b.y + r) - dc); }
-        best_intra = wave_sum_u32(sad);
+        best_intra = wave_sum(sad);
     }
     st.best_rf_idx = -1;
     const int cnt_raw = d.slice_is_i ? 0 : d.me.total_me_candidate_index[(size_t)b.b64 * d.n_pu + b.mbo];
@@ -234,7 +228,7 @@ template <int TS> __global__ void __launch_bounds__(64) tpl_src_kernel(const Tpl
         const int rx = b.x + (mx >> 3), ry = b.y + (my >> 3);
         uint32_t sad = 0;
         for (int i = l; i < S * S; i += 64) { const int r = i / S, c = i - r * S; sad += (uint32_t)abs((int)*pix(d.cur, b.x + c, b.y + r) - (int)*pix(rf.src, rx + c, ry + r)); }
-        const int64_t cost = wave_sum_u32(sad);
+        const int64_t cost = wave_sum(sad);
         if (cost < best_inter) {
             best_inter = cost;
             st.ref_frame_poc = rf.picture_number;
@@ -250,7 +244,7 @@ template <int TS> __global__ void __launch_bounds__(64) tpl_src_kernel(const Tpl
             const int r = i / W, c = i - r * W;
             A[r * (W + 1) + c] = (int)*pix(d.cur, b.x + c, b.y + r * step) - (int)*pix(rf.src, rx + c, ry + r * step);
         }
-        wave_sync();
+        wave_sync_workgroup_fences();
         uint32_t eob;
         const int64_t re = tx_chain<TS>(A, l, d.pf_shape, d.quant, p.iscan, false, eob);
         st.srcrf_dist = (re << 4) << p.sub; // TPL_DEP_COST_SCALE_LOG2
@@ -273,7 +267,7 @@ template <int TS, typename Pred> __device__ void recon_block(const TplParams &p,
         const int r = i / W, c = i - r * W;
         A[r * (W + 1) + c] = (int)*pix(d.cur, b.x + c, b.y + r * step) - pred(r * step, c);
     }
-    wave_sync();
+    wave_sync_workgroup_fences();
     const bool inv = !d.disable_intra_pred || d.is_ref;
     uint32_t eob;
     const int64_t re = tx_chain<TS>(A, l, d.pf_shape, d.quant, p.iscan, inv, eob);
@@ -431,10 +425,7 @@ template <int TS> int launch_all(SvtHipContext *ctx, const TplParams &p, int n_b
 
 // The cosine table of this translation unit's copy of txfm_core.h (svt_hip_rd_tables_init fills rd_kernel.hip's)
 int svt_hip_tpl_tables_init(SvtHipContext *ctx) {
-    int32_t cosp[4][64];
-    for (int b = 0; b < 4; b++)
-        for (int j = 0; j < 64; j++) cosp[b][j] = (int32_t)(cos(3.14159265358979323846 * j / 128.0) * (double)(1 << (10 + b)) + 0.5);
-    SVT_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_cospi), cosp, sizeof(cosp)));
+    SVT_HIP_CHECK(ctx, txfm_upload_cospi());
     return SVT_HIP_OK;
 }
 

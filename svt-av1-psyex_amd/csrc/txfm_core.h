@@ -1,11 +1,13 @@
 // txfm_core.h -- device code shared by the kernels that run the AV1 integer transforms (rd_kernel.hip, tpl_kernel.hip): the 1-D
-// forward / inverse DCT, ADST and identity kernels of the reference, by structure, the shift / clamp helpers of the 2-D passes and
-// the wave reductions.  Each translation unit that includes it has its own copy of the constant tables; c_cospi is filled at context
-// creation (svt_hip_rd_tables_init, svt_hip_tpl_tables_init).
+// forward / inverse DCT, ADST and identity kernels of the reference, by structure, the shift / clamp helpers of the 2-D passes (the wave
+// reductions: wave_ops.h).  Each translation unit that includes it has its own copy of the constant tables; c_cospi is filled at context
+// creation by txfm_upload_cospi() (svt_hip_rd_tables_init, svt_hip_tpl_tables_init).
 #ifndef SVT_HIP_TXFM_CORE_H
 #define SVT_HIP_TXFM_CORE_H
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include "wave_ops.h"
 
 namespace {
 
@@ -13,6 +15,13 @@ typedef unsigned long long u64;
 typedef long long          i64;
 
 __constant__ int32_t c_cospi[4][64]; // cospi_arr(bit), bit 10..13 (round(cos(j*pi/128) * 2^bit)), filled at init
+// host: computes the table and fills the including translation unit's copy
+inline hipError_t txfm_upload_cospi() {
+    int32_t cosp[4][64];
+    for (int b = 0; b < 4; b++)
+        for (int j = 0; j < 64; j++) cosp[b][j] = (int32_t)(cos(3.14159265358979323846 * j / 128.0) * (double)(1 << (10 + b)) + 0.5);
+    return hipMemcpyToSymbol(HIP_SYMBOL(c_cospi), cosp, sizeof(cosp));
+}
 // svt_aom_eb_av1_sinpi_arr_data rows for cos_bit 10..13 (Codec/inv_transforms.c:3228-3234)
 __constant__ int32_t c_sinpi[4][5] = {{0, 330, 621, 836, 951}, {0, 660, 1241, 1672, 1901}, {0, 1321, 2482, 3344, 3803}, {0, 2642, 4964, 6689, 7606}};
 
@@ -347,22 +356,6 @@ template <int N, bool SAFE32 = false> __device__ __forceinline__ void shift_vec(
 #pragma unroll
         for (int i = 0; i < N; i++) x[i] = (int32_t)((uint32_t)x[i] << sh);
     }
-}
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
-    return v;
 }
 
 } // namespace
