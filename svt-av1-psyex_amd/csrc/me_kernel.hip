@@ -165,6 +165,7 @@ struct LdsLayout { uint32_t src16, src32, src64, bsad, bmv, dense, win, total; }
 //   kMeMid2  level-1 results -> level-2 requests                    (control only)
 //   kMeS2    the level-2 searches (direct form)
 //   kMeTail  level-2 results, search centres, check-00, probe, integer search, pruning, candidates, outputs
+//            (its single-position stages -- check-00, the probe -- without a search stage: c00_sads / probe_sads)
 // A block's state (the head of St) and its search requests / results travel through HBM between them.  A block whose level-1 / level-2
 // searches do not qualify for the direct form (more than 32 positions, an empty area) -- or whose pre-HME / level-0 searches the pre-pass did
 // not make -- is DEFERRED: the one-kernel form makes it from scratch at the end of the launch (list mode).  (Round 3 first gave such blocks
@@ -1079,6 +1080,133 @@ __device__ __forceinline__ void run_me_searches(Shared &sh, CParams &p, const Me
 }
 
 // ---------------------------------------------------------------------------------------------
+// Single-position SADs of the integer-search stages: no window, no search machinery
+// ---------------------------------------------------------------------------------------------
+
+// the wave: check_00_center's SADs (motion_estimation.c:1139-1206) -- the requests st.req[0 .. nreq) c00_pre pushed with push_zz_req: one
+// position each, the even rows of the b64_w x b64_h block -- the way init_zz_sad rides on the block set-up: a lane holds two 16-byte pieces
+// of the even source rows (src64 view) and fetches the same pieces of every request with unaligned 16-byte loads, all of a round in flight
+// before the first is used.  Sums to st.req_key[], where probe_pre looks for them.
+constexpr int kC00Round = 8; // requests of one round (four references): 16 vectors per lane in flight
+__device__ __forceinline__ void c00_sads(Shared &sh) {
+    St &st = sh.st;
+    const int lane = threadIdx.x;
+    const int nreq = (int)uni((uint32_t)st.nreq), bw = (int)uni(st.b64_w), bh = (int)uni(st.b64_h);
+    for (int q0 = 0; q0 < nreq; q0 += kC00Round) { // uniform
+        V4 w[kC00Round][2];
+#pragma unroll
+        for (int j = 0; j < kC00Round; j++)
+            if (q0 + j < nreq) { // uniform
+                const uint8_t *win = uni_ptr(st.req[q0 + j].win);
+                const uint32_t stride = uni(st.req[q0 + j].stride);
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int i = lane + 64 * h, y = (i >> 2) * 2, x = (i & 3) * 16;
+                    w[j][h] = V4{0, 0, 0, 0};
+                    if (y < bh && x < bw) w[j][h] = __builtin_bit_cast(V4, *reinterpret_cast<GV4U *>(reinterpret_cast<uintptr_t>(win + (long long)y * stride + x)));
+                }
+            }
+#pragma unroll
+        for (int j = 0; j < kC00Round; j++)
+            if (q0 + j < nreq) { // uniform
+                uint32_t a = 0;
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int i = lane + 64 * h, y = (i >> 2) * 2, x = (i & 3) * 16;
+                    if (y < bh && x < bw) { // block widths are multiples of 8: a piece is whole or half inside
+                        const V4 v = *reinterpret_cast<const V4 *>(&LDS(sh.src64)[(y >> sh.cshift) * kSrc64Pitch + x]);
+                        a = __builtin_amdgcn_sad_u8(v.x, w[j][h].x, a);
+                        a = __builtin_amdgcn_sad_u8(v.y, w[j][h].y, a);
+                        if (x + 8 < bw) { a = __builtin_amdgcn_sad_u8(v.z, w[j][h].z, a); a = __builtin_amdgcn_sad_u8(v.w, w[j][h].w, a); }
+                    }
+                }
+                const uint32_t t = wave_sum_dpp(a);
+                if (lane == 0) st.req_key[q0 + j] = (u64)t << 32;
+            }
+    }
+    wave_sync();
+}
+
+typedef uint32_t V2 __attribute__((ext_vector_type(2)));
+typedef uint32_t V2U __attribute__((ext_vector_type(2), aligned(1)));
+typedef const __attribute__((address_space(1))) V2U GV2U;
+
+// the wave: the 1-point probes of the 8x8-variance test (motion_estimation.c:1391-1406), st.me_probe[0 .. nprobe), without a window: lane <->
+// 8x8 PU (quad-tree order, the n_idx order of best_sad's rows 21..84), its compared rows (4 when the search is sub-sampled, else 8) of the
+// reference straight from global memory at the request's centre, the source from the src64 view.  The rows of a round of references are all
+// in flight before the first SAD.  16x16 / 32x32 / 64x64 sums by DPP; scale and merge as in run_me_searches (a sub-sampled SAD counts twice;
+// strict `<` against the row's value; MV = the centre).  A centre whose 64x64 window leaves the padded plane -- the uniform test of
+// run_me_searches -- takes its samples clamped to the plane's edge.
+constexpr int kProbeRound = 4; // references of one round: 4 x 8 rows of 8 bytes per lane in flight
+__device__ __forceinline__ void probe_sads(Shared &sh, CParams &p, uint32_t *bsad, uint32_t *bmv, int r0n PROF_PARAM) {
+    St &st = sh.st;
+    const int lane = threadIdx.x;
+    const int sub  = (p.cfg.me_search_method == 0);
+    const int nrow = sub ? 4 : 8, rstep = sub ? 2 : 1;
+    const int px = 8 * ((lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4)), py = 8 * (((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4));
+    const int count = (int)uni((uint32_t)st.nprobe);
+    for (int m0 = 0; m0 < count; m0 += kProbeRound) { // uniform
+        V2 w[kProbeRound][8];
+#pragma unroll
+        for (int j = 0; j < kProbeRound; j++)
+            if (m0 + j < count) { // uniform
+                const MeReq &mm = st.me_probe[m0 + j];
+                const uint8_t *pix0 = uni_ptr(mm.pix0);
+                const uint32_t stride = uni(mm.stride);
+                const int ox = (int16_t)uni((uint32_t)mm.ox), oy = (int16_t)uni((uint32_t)mm.oy);
+                const int min_x = (int16_t)uni((uint32_t)mm.min_x), max_x = (int16_t)uni((uint32_t)mm.max_x);
+                const int min_y = (int16_t)uni((uint32_t)mm.min_y), max_y = (int16_t)uni((uint32_t)mm.max_y);
+                if (ox >= min_x && ox + 63 <= max_x && oy >= min_y && oy + 63 <= max_y) { // uniform
+                    const uint8_t *g = pix0 + (ox + px) + (long long)(oy + py) * stride;
+#pragma unroll
+                    for (int k = 0; k < 8; k++)
+                        if (k < nrow) w[j][k] = __builtin_bit_cast(V2, *reinterpret_cast<GV2U *>(reinterpret_cast<uintptr_t>(g + (long long)(k * rstep) * stride)));
+                }
+            }
+        PROF(17); // (diagnostic build: the probes' reference rows requested)
+#pragma unroll
+        for (int j = 0; j < kProbeRound; j++)
+            if (m0 + j < count) { // uniform
+                const MeReq &mm = st.me_probe[m0 + j];
+                const int ox = (int16_t)uni((uint32_t)mm.ox), oy = (int16_t)uni((uint32_t)mm.oy);
+                const int row = (uni(mm.li) ? r0n : 0) + (int)uni(mm.ri);
+                const int min_x = (int16_t)uni((uint32_t)mm.min_x), max_x = (int16_t)uni((uint32_t)mm.max_x);
+                const int min_y = (int16_t)uni((uint32_t)mm.min_y), max_y = (int16_t)uni((uint32_t)mm.max_y);
+                uint32_t a = 0;
+                if (ox >= min_x && ox + 63 <= max_x && oy >= min_y && oy + 63 <= max_y) { // uniform
+#pragma unroll
+                    for (int k = 0; k < 8; k++)
+                        if (k < nrow) { // uniform
+                            const V2 s = *reinterpret_cast<const V2 *>(&LDS(sh.src64)[((py + k * rstep) >> sh.cshift) * kSrc64Pitch + px]);
+                            a = __builtin_amdgcn_sad_u8(s.x, w[j][k].x, a);
+                            a = __builtin_amdgcn_sad_u8(s.y, w[j][k].y, a);
+                        }
+                } else { // rare: sample by sample, coordinates clamped into the padded plane (a rolled loop: no registers, little code)
+                    const uint8_t *pix0 = uni_ptr(mm.pix0);
+                    const uint32_t stride = uni(mm.stride);
+#pragma nounroll
+                    for (int i = 0; i < nrow * 8; i++) {
+                        const int k = i >> 3, b = i & 7;
+                        const int x = imin(imax(ox + px + b, min_x), max_x), y = imin(imax(oy + py + k * rstep, min_y), max_y);
+                        a += (uint32_t)iabs((int)LDS(sh.src64)[((py + k * rstep) >> sh.cshift) * kSrc64Pitch + px + b] - (int)*reinterpret_cast<const __attribute__((address_space(1))) uint8_t *>(reinterpret_cast<uintptr_t>(pix0 + x + (long long)y * stride)));
+                    }
+                }
+                const uint32_t v8 = a << sub, v16 = quad_sum(v8), v32 = row16_sum_of_quads(v16), v64 = wave_sum_dpp(v8);
+                uint32_t *rs_ = bsad + row * 85, *rm_ = bmv + row * 85;
+                const uint32_t mv = ((uint32_t)oy << 16) | (uint16_t)ox;
+                auto merge = [&](int n, uint32_t sad) {
+                    if (sad < rs_[n]) { rs_[n] = sad; rm_[n] = mv; }
+                };
+                merge(21 + lane, v8);
+                if ((lane & 3) == 0) merge(5 + (lane >> 2), v16);
+                if ((lane & 15) == 0) merge(1 + (lane >> 4), v32);
+                if (lane == 0) merge(0, v64);
+            }
+    }
+    wave_sync();
+}
+
+// ---------------------------------------------------------------------------------------------
 // lane-0 control logic (restates the scalar parts of motion_estimation.c; see per-function citations)
 // ---------------------------------------------------------------------------------------------
 
@@ -1927,7 +2055,19 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 wave_sync();
                 PROF(step == kMain ? 20 : 6 + step);
                 if (step == kC00 && bi == 0 && st.tf_exit) { step = kEnd; continue; } // uniform: LDS value read after the barrier
-                if (step < kProbe) {
+                if constexpr (MODE == kMeTail) {
+                    // The tail enters at kC00: its single-position stages go without a search (c00_sads, probe_sads), so it carries neither form of
+                    // the small searches.  The one-kernel form keeps the search forms for them: it has the code for its HME stages anyway, and the
+                    // inline forms on top of it measured slower there.
+                    if (step == kC00) {
+                        c00_sads(sh);
+                        PROF(18); // (diagnostic build: check-00 SADs)
+                    } else if (step == kProbe) {
+                        probe_sads(sh, p, bsad, bmv, r0n PROF_ARG);
+                    } else {
+                        run_me_searches(sh, p, st.me, st.nme, bsad, bmv, r0n PROF_ARG);
+                    }
+                } else if (step < kProbe) {
                     PROF_STEP(step);
                     if (st.nreq) { // uniform (LDS value read after the barrier)
                         if (!run_small_searches_direct(sh PROF_ARG)) run_searches(sh PROF_ARG);

@@ -42,8 +42,15 @@ PHASES = [
 ] + [(24 + i, f"{n}: plan a round + issue its window loads" if MODE not in (2, 5) else ("search kernel: job flags read", "search kernel: requests + source view into LDS", "direct search: qualification, lane set-up", "direct search: row loop")[i] if i < 4 else "-") for i, n in enumerate(STAGES)] + [(32 + i, f"{n}: window registers -> LDS arena") for i, n in enumerate(STAGES)] + [
     (40 + i, f"{n}: rest of the evaluation (tile entry -> registers, arg-min across the wave, result)") for i, n in enumerate(STAGES)] + [
     (22, "all stages: plan the next round + issue its window loads (inside the evaluation phase)"), (30, "all stages: wide tiles, item loop (8 positions x whole block per lane)"),
-    (23, "all stages: small searches, item loop (8 positions x row slice per lane, LDS atomics)"), (19, "searches: tail"), (3, "8x8-variance probe: folding the bests, merge into best_sad / best_mv"), (4, "integer search: folding the bests, merge into best_sad / best_mv"),
-    (46, "integer search / probe: window staged (global -> registers -> LDS arena)"), (47, "integer search / probe: positions evaluated"),
+    (23, "all stages: small searches, item loop (8 positions x row slice per lane, LDS atomics)"), (19, "searches: tail"),
+    (18, "check-00: the two SADs per reference, inline (no search stage)"),  # 17, 18: the tail kernel only
+    (17, "8x8-variance probe: reference rows of all probes requested (global -> registers)"),
+    # the tail kernel evaluates the probe on its own (probe_sads); every other form sends it through run_me_searches like the integer search, so
+    # there its window and its positions are part of slots 46 / 47 and slot 3 is what follows them
+    (3, "8x8-variance probe: SADs, 16x16 / 32x32 / 64x64 sums, merge into best_sad / best_mv" if MODE == 7 else "8x8-variance probe: folding the bests, merge into best_sad / best_mv"),
+    (4, "integer search: folding the bests, merge into best_sad / best_mv"),
+    (46, "integer search: window staged (global -> registers -> LDS arena)" if MODE == 7 else "probe + integer search: window staged (global -> registers -> LDS arena)"),
+    (47, "integer search: positions evaluated" if MODE == 7 else "probe + integer search: positions evaluated"),
     (5, "control after a stage (fold results, centres, early exits)"),
     (13, "reference pruning"), (14, "candidate lists"), (15, "distortions / variance outputs"), (16, "result rows stored"),
 ]
@@ -77,12 +84,15 @@ tot = col.sum()
 lines = [f"{KERNEL[MODE]}, diagnostic build -DSVT_HIP_ME_PROFILE -DSVT_HIP_ME_PROFILE_MODE={MODE} (tools/build_me_profile_lib.sh): where a block's wall time in this kernel goes.  One wave per block; lane 0 accumulates",
          f"s_memtime deltas per phase; averaged over the {n_b64} blocks of bench.py's launch (16 pictures 3840x2160, preset 6, R = 2, reference distances 8 / 1 / 4 / 2) and {N} launches",
          "on the three picture sets.  The waves of a CU share its issue slots, so a phase's share of wall time includes the cycles its wave waited for the others to issue.", "",
-         f"{'phase':86s} {'clocks/block':>12s} {'%':>5s}"]
-for i, name in PHASES:
-    if col[i] >= 0.5:
-        lines.append(f"{name:86s} {col[i]:12.0f} {100 * col[i] / tot:5.1f}")
-lines.append(f"{'total clocks per block (s_memtime)':86s} {tot:12.0f}")
-grp = {"control (serial, one lane)": (2, 6, 7, 8, 9, 10, 11, 12, 20, 5, 13), "set-up, outputs, fetch": (0, 1, 14, 15, 16), "probe + integer search": (3, 4, 46, 47)}
+         ""]
+shown = [(i, name) for i, name in PHASES if col[i] >= 0.5]
+WID = max([86] + [len(name) for _, name in shown])  # the column is as wide as the widest label shown
+lines[-1] = f"{'phase':{WID}s} {'clocks/block':>12s} {'%':>5s}"
+for i, name in shown:
+    lines.append(f"{name:{WID}s} {col[i]:12.0f} {100 * col[i] / tot:5.1f}")
+lines.append(f"{'total clocks per block (s_memtime)':{WID}s} {tot:12.0f}")
+grp = {"control (serial, one lane)": (2, 6, 7, 8, 9, 10, 11, 12, 20, 5, 13), "set-up, outputs, fetch": (0, 1, 14, 15, 16), "check-00 inline + tails of the searches (18, 19)": (18, 19)}
+grp.update({"probe (17, 3)": (17, 3), "integer search (4, 46, 47)": (4, 46, 47)} if MODE == 7 else {"probe + integer search (3, 4, 46, 47)": (3, 4, 46, 47)})
 if MODE in (2, 5):
     grp = {"per-job prologue / epilogue (flags, requests, source view, lane set-up, arg-min, keys out; slots 0, 24, 25, 26, 23)": (0, 24, 25, 26, 23), "row loop (27)": (27,)}
 elif MODE == 1:
@@ -94,5 +104,8 @@ lines.append("")
 for g, idx in grp.items():
     v = sum(col[i] for i in idx)
     if v >= 0.5:
-        lines.append(f"{g:86s} {v:12.0f} {100 * v / tot:5.1f}")
+        lines.append(f"{g:{WID}s} {v:12.0f} {100 * v / tot:5.1f}")
+rest = tot - sum(col[i] for i in {i for idx in grp.values() for i in idx})
+if grp and rest >= 0.5:  # the groups add up to the total
+    lines.append(f"{'in no group above':{WID}s} {rest:12.0f} {100 * rest / tot:5.1f}")
 print("\n".join(lines))
