@@ -25,6 +25,7 @@
 #include <string.h>
 #include "me_kernel.h"
 #include "wave_ops.h"
+#include "lds_dma.h"
 
 // Diagnostic build only (-DSVT_HIP_ME_PROFILE): lane 0 accumulates shader-clock deltas per phase (private array) and adds
 // them to queue_head[16 + 2*i] (u64) when the wave retires.  Never defined in the shipped library.
@@ -929,8 +930,9 @@ __device__ __attribute__((noinline)) void stage_clamped(uint8_t *win, const uint
 // are packed keys (sad << 12 | position inside the tile, raster order): one v_lshl_or + one v_min per PU size and position -- the first
 // minimum in raster order wins, like the reference's strict `<` -- against three instructions for a compare and two selects.  Measured on
 // the bench launch (one-wave-per-8x8 layout before): ~20 VALU instructions per position and wave -> ~8.
-constexpr int kMeInFlight = 4; // window vectors a lane has in flight while staging a tile (8 measured the same: 35 more spilled registers pay for the saved round trip)
 constexpr int kMeOrdBits = 12; // positions of one tile: at most 4096 (the tile sizing below); 64x64 SADs stay below 2^20
+// The fast path fills a tile's window with direct-to-LDS loads (lds_dma.h): every vector of the tile in flight before the one wait, no staging
+// registers (through registers, 4 vectors per lane in flight took 2-3 round trips per tile, and 8 paid for the saved one with 35 spilled registers).
 __device__ __forceinline__ void run_me_searches(Shared &sh, CParams &p, const MeReq *list, int count, uint32_t *bsad, uint32_t *bmv, int r0n PROF_PARAM) {
     const int lane = threadIdx.x;
     const int sub  = (p.cfg.me_search_method == 0);
@@ -962,8 +964,7 @@ __device__ __forceinline__ void run_me_searches(Shared &sh, CParams &p, const Me
                 const int pitch = me_pitch(0, w); // 16-byte rows (fetched with unaligned 16-byte loads: position x0 sits on LDS byte 0 of its row)
                 const int rows        = h - 1 + 64;
                 const int vec_per_row = pitch >> 4;
-                const float vpr_rcp   = rcp_of((uint32_t)vec_per_row);
-                wave_sync(); // previous tile fully consumed
+                lds_dma_after_stores(); // previous tile fully consumed, and none of the wave's own LDS traffic behind the loads below
                 // The reference's 1-point probe uses the unclipped search centre (motion_estimation.c:1391-1406): a centre far outside
                 // the picture would take these reads past the padded plane (undefined in the reference; a fault here).  Such a tile
                 // -- uniform test -- is staged sample by sample with coordinates clamped to the plane's edge instead.
@@ -971,25 +972,8 @@ __device__ __forceinline__ void run_me_searches(Shared &sh, CParams &p, const Me
                 // carry that much slack around every row, pictures.hip.)
                 const int wx0 = m.ox + x0, wy0 = m.oy + y0;
                 if (m.ox + x0 >= m.min_x && m.ox + x0 + w - 1 + 63 <= m.max_x && wy0 >= m.min_y && wy0 + rows - 1 <= m.max_y) {
-                    const int nvec = vec_per_row * rows;
-                    // kMeInFlight independent loads per lane before the first is waited for
-                    for (int b0 = 0; b0 < nvec; b0 += kMeInFlight * kThreads) { // uniform
-                        const int base = b0 + lane;
-                        int  k[kMeInFlight];
-                        V4   v[kMeInFlight];
-#pragma unroll
-                        for (int j = 0; j < kMeInFlight; j++) {
-                            if (b0 + j * kThreads < nvec) { // uniform: whole instructions beyond the window are skipped (lanes beyond it inside one repeat the last vector)
-                                k[j] = imin(base + j * kThreads, nvec - 1);
-                                const int row = (int)div_by_rcp((uint32_t)k[j], vpr_rcp), c = k[j] - row * vec_per_row;
-                                const V4U q4 = *reinterpret_cast<GV4U *>(reinterpret_cast<uintptr_t>(gwin + (long long)row * m.stride + c * 16));
-                                v[j] = V4{q4.x, q4.y, q4.z, q4.w};
-                            }
-                        }
-#pragma unroll
-                        for (int j = 0; j < kMeInFlight; j++)
-                            if (b0 + j * kThreads < nvec) *reinterpret_cast<V4 *>(&LDS(sh.win)[k[j] * 16]) = v[j];
-                    }
+                    lds_dma_window(gwin, m.stride, vec_per_row, rows, g_lds, sh.win); // vector k -> win + 16 * k; lanes beyond the window are switched off
+                    lds_dma_wait();
                 } else {
                     stage_clamped(LDS(sh.win), m.pix0, m.stride, m.min_x, m.max_x, m.min_y, m.max_y, wx0, wy0, pitch, rows);
                 }
@@ -1337,6 +1321,7 @@ constexpr size_t kPersistBytes = (offsetof(St, req) + 15) & ~(size_t)15; // the 
 template <int MODE>
 __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ ghdr, const MeKernelParams *__restrict__ gparams, const uint32_t launch_flags) {
     St     &st = *reinterpret_cast<St *>(g_lds);
+    constexpr bool kImports = MODE == kMeMid2 || MODE == kMeTail; // the kernels that take a block's state over from the kernel before
     // launch parameters: read-only, uniform addresses -> scalar loads through the constant cache, values in SGPRs
     typedef const SVT_CONST_AS MeBatchHeader CHeader;
     CHeader  &hdr = *(CHeader *)ghdr;
@@ -1410,21 +1395,11 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         const uint4 *src = reinterpret_cast<const uint4 *>(g_lds);
         for (int i = tid; i < (int)(kPersistBytes / 16); i += kThreads) dst[i] = src[i];
     };
-    auto import_state = [&](int gjob) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(stage_base(gjob));
-        uint4 *dst = reinterpret_cast<uint4 *>(g_lds);
-        for (int i = tid; i < (int)(kPersistBytes / 16); i += kThreads) dst[i] = src[i];
-    };
     static_assert(kPersistBytes + kMaxReq * (sizeof(Req) + sizeof(u64)) <= SVT_HIP_ME_STAGE_BYTES, "a block's record holds its state, its requests and their results");
     auto export_reqs = [&](int gjob) { // st.req[0 .. nreq) (nreq travels with the state)
         uint4 *dst = reinterpret_cast<uint4 *>(stage_base(gjob) + kPersistBytes);
         const uint4 *src = reinterpret_cast<const uint4 *>(st.req);
         static_assert(sizeof(Req) == 24 && (kMaxReq * sizeof(Req)) % 16 == 0, "requests are copied as 16-byte words");
-        for (int i = tid; i < (int)(kMaxReq * sizeof(Req) / 16); i += kThreads) dst[i] = src[i];
-    };
-    auto import_reqs = [&](int gjob) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(stage_base(gjob) + kPersistBytes);
-        uint4 *dst = reinterpret_cast<uint4 *>(st.req);
         for (int i = tid; i < (int)(kMaxReq * sizeof(Req) / 16); i += kThreads) dst[i] = src[i];
     };
     auto keys_of = [&](int gjob) { return reinterpret_cast<u64 *>(stage_base(gjob) + kPersistBytes + kMaxReq * sizeof(Req)); };
@@ -1455,30 +1430,48 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
 #define BEST_MV(li, ri) (bmv + (((li) ? r0n : 0) + (ri)) * 85)
         const int n_rows   = r0n + (nl > 1 ? d.num_of_ref_pic_to_search[1] : 0);
         uint32_t *const jflag = hdr.job_flags ? hdr.job_flags + gjob : nullptr; // staged launches: how the block travels
-        if constexpr (MODE != kMeFull && MODE != kMeMid1) {
+        if constexpr (me_is_search(MODE)) {
+            // the search kernels' form of the batch below: the block's requests, the 16 bytes of its record that hold nreq, and the source view
+            constexpr int lvl = MODE == kMeS1 ? 1 : 2, parts = lvl == 1 ? 3 : 5; // pieces of a view row, the last one padding
+            static_assert(offsetof(St, req) == kPersistBytes && offsetof(St, nreq) >= kPersistBytes - 16, "nreq sits in the last 16-byte word of the record's head, the requests behind it");
+            static_assert(kSrc32Pitch == 3 * 16 && kSrc64Pitch == 5 * 16, "a view row is its pieces and one piece of padding");
+            lds_dma_after_stores();
+            lds_dma_copy(stage_base(gjob) + kPersistBytes - 16, g_lds, (uint32_t)(kPersistBytes - 16), 1 + (int)(kMaxReq * sizeof(Req) / 16));
+            const int ox = (int)(bxi * 64) >> (2 - lvl), oy = (int)(byi * 64) >> (2 - lvl), rstep = 1 << cshift, npiece = ((lvl == 1 ? 32 : 64) >> cshift) * parts;
+            for (int b0 = 0; b0 < npiece; b0 += kThreads) { // uniform; piece n = row n / parts, part n % parts
+                const int n = b0 + tid, row = n / parts, cc = n - row * parts;
+                if (n < npiece && cc < parts - 1) lds_dma_load16(plane_at(p.cur.lvl[lvl], ox + cc * 16, oy + row * rstep), g_lds, (lvl == 1 ? lay.src32 : lay.src64) + (uint32_t)b0 * 16);
+            }
             const uint32_t f = __hip_atomic_load(jflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            lds_dma_wait();
+            if (f & SVT_HIP_ME_JOB_DEFERRED) continue; // uniform
+        } else if constexpr (kImports) {
+            // One round trip for all the block brings along: the state as the previous kernel left it, the keys of the searches made in between
+            // and (tail) the source view go straight to LDS while the flag word is on its way; one wait, and only then a look at the flag.  (A
+            // deferred block's copies land in this wave's own slice and are not used.)  Destinations: the head of St, req_key[], the view's rows --
+            // disjoint; the previous block's stores to them have retired.
+            static_assert(offsetof(St, req_key) % 16 == 0 && kPersistBytes <= offsetof(St, req) + 8 && offsetof(St, req) + 8 <= offsetof(St, req_key), "the record's parts land on 16-byte words of their own");
+            static_assert(kSrc64Pitch == 5 * 16, "a view row is four pieces and one piece of padding");
+            lds_dma_after_stores();
+            lds_dma_copy(stage_base(gjob), g_lds, 0, (int)(kPersistBytes / 16));
+            lds_dma_copy(reinterpret_cast<const uint8_t *>(keys_of(gjob)), g_lds, (uint32_t)offsetof(St, req_key), (int)(kMaxReq * sizeof(u64) / 16));
+            if constexpr (MODE == kMeTail) {
+                const int ox = (int)(bxi * 64), oy = (int)(byi * 64), rstep = 1 << cshift, npiece = (64 >> cshift) * 5;
+                for (int b0 = 0; b0 < npiece; b0 += kThreads) { // uniform; piece n = row n / 5, part n % 5: part 4 is the row's padding, its lane switched off
+                    const int n = b0 + tid, row = n / 5, cc = n - row * 5;
+                    if (n < npiece && cc < 4) lds_dma_load16(plane_at(p.cur.lvl[2], ox + cc * 16, oy + row * rstep), g_lds, lay.src64 + (uint32_t)b0 * 16);
+                }
+            }
+            const uint32_t f = __hip_atomic_load(jflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (MODE == kMeTail)
+                for (int i = tid; i < n_rows * 85; i += kThreads) { bmv[i] = 0; bsad[i] = SVT_HIP_MAX_SAD_VALUE; }
+            if (tid == 0) { st.nme = 0; st.nprobe = 0; }
+            lds_dma_wait();
             if (f & SVT_HIP_ME_JOB_DEFERRED) continue; // uniform: the whole-pipeline kernel makes this block at the end of the launch
         }
         if constexpr (me_is_search(MODE)) {
             // ---- search-only kernels: the block's requests in, their keys out ------------------------------------------------
-            constexpr int lvl = MODE == kMeS1 ? 1 : 2;
-            const int ox = (int)(bxi * 64), oy = (int)(byi * 64), rstep = 1 << cshift;
-            PROF(24);
-            import_reqs(gjob);
-            if (tid == 0) st.nreq = *reinterpret_cast<const int *>(stage_base(gjob) + offsetof(St, nreq));
-            if constexpr (lvl == 1) {
-                for (int i = tid; i < (32 >> cshift) * 2; i += kThreads) {
-                    const int row = i >> 1, cc = i & 1;
-                    uint4 v; memcpy(&v, plane_at(p.cur.lvl[1], (ox >> 1) + cc * 16, (oy >> 1) + row * rstep), 16);
-                    *reinterpret_cast<uint4 *>(&LDS(sh.src32)[row * kSrc32Pitch + cc * 16]) = v;
-                }
-            } else {
-                for (int i = tid; i < (64 >> cshift) * 4; i += kThreads) {
-                    const int row = i >> 2, cc = i & 3;
-                    uint4 v; memcpy(&v, plane_at(p.cur.lvl[2], ox + cc * 16, oy + row * rstep), 16);
-                    *reinterpret_cast<uint4 *>(&LDS(sh.src64)[row * kSrc64Pitch + cc * 16]) = v;
-                }
-            }
+            PROF(24); // (diagnostic build: the set-up batch)
             wave_sync();
             PROF(25);
             if (st.nreq) { // uniform
@@ -1492,6 +1485,8 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         }
 
         // ---- block setup (me_process.c:183-214; motion_estimation.c:3090-3105, init_me_hme_data :3010-3071) ---
+        // (mid2 / tail: every field initialised here lies in the head of St, which the batch above has brought in -- nothing to store)
+        if constexpr (!kImports) {
         if (tid == 0) {
             st.b64_index = b;
             st.org_x = bxi * 64; st.org_y = byi * 64;
@@ -1502,7 +1497,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
             st.nreq = 0; st.nme = 0; st.nprobe = 0;
         }
         for (int i = tid; i < 3 * 2 * 4 * 2 * 2; i += kThreads) { (&st.hx[0][0][0][0][0])[i] = 0; (&st.hy[0][0][0][0][0])[i] = 0; (&st.hs[0][0][0][0][0])[i] = 0; }
-        if constexpr (MODE == kMeFull || MODE == kMeTail)
+        if constexpr (MODE == kMeFull)
             for (int i = tid; i < n_rows * 85; i += kThreads) { bmv[i] = 0; bsad[i] = SVT_HIP_MAX_SAD_VALUE; }
         if (tid < 8) {
             const int li = tid >> 2, ri = tid & 3;
@@ -1513,6 +1508,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 ph.valid = 0; ph.col = ph.row = 0; ph.sad = 0; ph.sa_w = ph.sa_h = 0;
                 st.performed_phme[li][ri][sri] = 0;
             }
+        }
         }
         if ((MODE == kMeFull || MODE == kMeMid1) && has_dense && tid < n_rows * kDenseKinds) // this block's slots of the dense pre-pass (read by the pre-HME / level-0 stages)
             reinterpret_cast<uint4 *>(g_lds + lay.dense)[tid] = reinterpret_cast<const uint4 *>(hdr.dense)[((size_t)gjob * hdr.n_slot) * kDenseKinds + tid];
@@ -1525,7 +1521,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         { // source views -> LDS (every row, or the even rows only: cshift)
             const int ox = (int)(bxi * 64), oy = (int)(byi * 64), rstep = 1 << cshift;
             const int bw64 = imin(64, (int)d.aligned_width - ox), bh64 = imin(64, (int)d.aligned_height - oy);
-            if constexpr (MODE != kMeMid2)
+            if constexpr (!kImports) // (the tail's view came with the batch)
             for (int i = tid; i < (64 >> cshift) * 4; i += kThreads) {
                 const int row = i >> 2, cc = i & 3;
                 uint4 v; memcpy(&v, plane_at(p.cur.lvl[2], ox + cc * 16, oy + row * rstep), 16);
@@ -1565,12 +1561,6 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
             }
         wave_sync();
 
-        if constexpr (MODE == kMeMid2 || MODE == kMeTail) { // the block's state as the previous kernel left it, and the keys of the searches made in between
-            import_state(gjob);
-            const u64 *keys = keys_of(gjob);
-            if (tid < kMaxReq) st.req_key[tid] = keys[tid];
-            wave_sync();
-        }
         PROF(1);
         // The stages below run as one loop around a SINGLE inlined copy of run_searches / run_me_searches (the kernel
         // must stay small enough for the instruction cache shared by two CUs): each stage has a "pre" part that

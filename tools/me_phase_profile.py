@@ -36,10 +36,10 @@ MODE = int(sys.argv[2]) if len(sys.argv) == 3 and sys.argv[1] == "--one" else -1
 # index -> phase (PROF(i) in csrc/me_kernel.hip)
 STAGES = ("zero-MV SADs", "pre-HME", "HME level 0", "HME level 1", "HME level 2", "check-00")
 PHASES = [
-    (0, "job fetch (queue atomic)" if MODE == 0 else "end of the previous job (results out) + job fetch" if MODE != 1 else "everything behind the set-up (zero-MV / pre-HME / level-0 results folded, level-1 searches pushed, state out) + job fetch"), (1, "block set-up: source 64x64 / 32x32 / 16x16 views into LDS"), (2, "stage preamble"),
+    (0, "job fetch (queue atomic)" if MODE == 0 else "end of the previous job (results out) + job fetch" if MODE != 1 else "everything behind the set-up (zero-MV / pre-HME / level-0 results folded, level-1 searches pushed, state out) + job fetch"), (1, "block set-up: source 64x64 / 32x32 / 16x16 views into LDS" if MODE not in (4, 7) else "block set-up: job flags, state, keys, source view in one batch of direct-to-LDS loads"), (2, "stage preamble"),
     (6, "control before zero-MV SADs"), (7, "control before pre-HME"), (8, "control before HME level 0"), (9, "control before HME level 1"),
     (10, "control before HME level 2"), (11, "control before check-00"), (12, "control before the 8x8-variance probe"), (20, "control before the integer search"),
-] + [(24 + i, f"{n}: plan a round + issue its window loads" if MODE not in (2, 5) else ("search kernel: job flags read", "search kernel: requests + source view into LDS", "direct search: qualification, lane set-up", "direct search: row loop")[i] if i < 4 else "-") for i, n in enumerate(STAGES)] + [(32 + i, f"{n}: window registers -> LDS arena") for i, n in enumerate(STAGES)] + [
+] + [(24 + i, f"{n}: plan a round + issue its window loads" if MODE not in (2, 5) else ("search kernel: set-up batch (job flags, requests, source view: direct-to-LDS loads, one wait)", "search kernel: after the batch (nothing left to copy)", "direct search: qualification, lane set-up", "direct search: row loop")[i] if i < 4 else "-") for i, n in enumerate(STAGES)] + [(32 + i, f"{n}: window registers -> LDS arena") for i, n in enumerate(STAGES)] + [
     (40 + i, f"{n}: rest of the evaluation (tile entry -> registers, arg-min across the wave, result)") for i, n in enumerate(STAGES)] + [
     (22, "all stages: plan the next round + issue its window loads (inside the evaluation phase)"), (30, "all stages: wide tiles, item loop (8 positions x whole block per lane)"),
     (23, "all stages: small searches, item loop (8 positions x row slice per lane, LDS atomics)"), (19, "searches: tail"),
@@ -49,7 +49,7 @@ PHASES = [
     # there its window and its positions are part of slots 46 / 47 and slot 3 is what follows them
     (3, "8x8-variance probe: SADs, 16x16 / 32x32 / 64x64 sums, merge into best_sad / best_mv" if MODE == 7 else "8x8-variance probe: folding the bests, merge into best_sad / best_mv"),
     (4, "integer search: folding the bests, merge into best_sad / best_mv"),
-    (46, "integer search: window staged (global -> registers -> LDS arena)" if MODE == 7 else "probe + integer search: window staged (global -> registers -> LDS arena)"),
+    (46, "integer search: window staged (global -> LDS arena, direct loads)" if MODE == 7 else "probe + integer search: window staged (global -> LDS arena, direct loads)"),
     (47, "integer search: positions evaluated" if MODE == 7 else "probe + integer search: positions evaluated"),
     (5, "control after a stage (fold results, centres, early exits)"),
     (13, "reference pruning"), (14, "candidate lists"), (15, "distortions / variance outputs"), (16, "result rows stored"),
