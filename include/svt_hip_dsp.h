@@ -13,11 +13,12 @@
  *  -> svt_av1_inv_txfm2d_add_{WxH}                          (Codec/inv_transforms.c:2459-2716)
  *  -> svt_spatial_full_distortion_kernel / svt_full_distortion_kernel16_bits (picture_operators_c.c:65-83, pic_operators.c:174-197)
  * The rate half of that loop body -- svt_aom_txb_estimate_coeff_bits, RDCOST and the choice of the winning tx_type -- is
- * svt_hip_coeff_rate_batch below; it reads the qcoeff / eob arrays svt_hip_rd_batch writes, on the device.  RDOQ and the early exits of
- * the search stay on the host.
+ * svt_hip_coeff_rate_batch below; it reads the qcoeff / eob arrays svt_hip_rd_batch writes, on the device.  Between the two sits RDOQ,
+ * svt_hip_rdoq_batch (svt_av1_optimize_b behind its gates, Codec/full_loop.c:1127-1336,1764-1817): it rewrites the "fp" quantizer's qcoeff /
+ * dqcoeff / eob in place and renews dist_coeff and cul_level.  The early exits of the search stay on the host.
  *
  * Also here: the forward and the inverse transform as batches of their own (svt_hip_fwd_txfm_batch, svt_hip_inv_txfm_batch), the
- * coefficient rate estimation with the RD cost and the winning candidate (svt_hip_coeff_rate_batch), batched block statistics incl. the PSYEX psy-RD term and distortion facades (svt_hip_block_stats_batch, svt_hip_spy_rd_bias),
+ * coefficient rate estimation with the RD cost and the winning candidate (svt_hip_coeff_rate_batch), RDOQ (svt_hip_rdoq_batch), batched block statistics incl. the PSYEX psy-RD term and distortion facades (svt_hip_block_stats_batch, svt_hip_spy_rd_bias),
  * full-pel prediction from ME results (svt_hip_fullpel_pred{,_batch}) and the scan-order / size helpers.
  */
 #ifndef SVT_HIP_DSP_H
@@ -303,6 +304,76 @@ typedef struct SvtHipCoeffRateDesc {
 int    svt_hip_coeff_rate_batch(SvtHipContext *ctx, const SvtHipCoeffRateDesc *d);
 size_t svt_hip_coeff_rate_desc_size(void); /* sizeof(SvtHipCoeffRateDesc) as compiled */
 size_t svt_hip_rate_tables_size(void);     /* sizeof(SvtHipRateTables) as compiled */
+
+/* ---- RDOQ: the trellis pass over quantised coefficients ---------------------------------------------------------------
+ * Per job, the part of svt_aom_quantize_inv_quantize that follows the first ("fp") quantizer call when is_encode_pass == 0
+ * (Codec/full_loop.c:1764-1817, then :1832-1836), on the coeff / qcoeff / dqcoeff / eob arrays svt_hip_rd_batch writes with quant_kind 1:
+ *   eob_perc = eob * 100 / (tx_width * tx_height) on the real dimensions
+ *   eob_perc >= eob_th       RDOQ is off for the job and the reference re-quantizes with the "b" quantizer: status 2.  With the fallback
+ *                            arrays (the same jobs through svt_hip_rd_batch with quant_kind 0) the job's outputs become theirs; without
+ *                            them the job is left untouched
+ *   eob_perc >= eob_fast_th  svt_fast_optimize_b = update_coeff_eob_fast (:1092-1126) first: un-weighted dequant, zbin = dq +
+ *                            ROUND_POWER_OF_TWO(dq * 70, 7)
+ *   eob != 0                 svt_av1_optimize_b (:1127-1336) with rdmult = ((lambda * plane_rd_mult[is_inter][plane_type] * rweight) / 100 + 2)
+ *                            >> MAX(2, sharpness), plane_rd_mult = {17, 13}, {16, 10} (TUNE_CHROMA_SSIM == 1); a job's `sharp` flag sets
+ *                            rweight = 0 and switches eob shortening and update_skip off (:1169-1182); eob_fast_inter / eob_fast_intra are its
+ *                            fast_mode (trims again, skips the update_coeff_eob loop)
+ *   cul_level                svt_av1_compute_cul_level of the result
+ * Bit-exact.  Decided on the host and therefore not carried: rdoq_ctrls.dct_dct_only, skip_uv, ctx->mds_skip_rdoq and lossless segments
+ * are known per job there -- the caller simply does not list those jobs; rdoq_ctrls.satd_factor is 255 and early_exit_th is 0 at every RDOQ
+ * level (set_rdoq_controls, Codec/enc_mode_config.c:3336-3418), and eob_cost < 0 never holds.  The encode-pass branch
+ * (svt_av1_perform_noise_normalization, the 16-bit-pipeline quantizer choice) is not part of this entry. */
+typedef struct SvtHipRdoqJob {
+    uint8_t tx_type;      /* below 16 */
+    uint8_t txb_skip_ctx; /* 0..12 */
+    uint8_t dc_sign_ctx;  /* 0..2 */
+    uint8_t is_inter;     /* pred_mode >= NEARESTMV */
+    uint8_t quant_row;    /* index into quant_rows */
+    uint8_t flags;        /* bit 0 = sharp: use_sharpness && delta_q_present && plane == 0 && (sb qindex - quantizer_to_qindex[picture_qp] < 0 ||
+                           * sharp_tx), evaluated by the host */
+    uint8_t reserved[2];
+} SvtHipRdoqJob;
+
+typedef struct SvtHipRdoqDesc {
+    uint8_t  tx_size;        /* TxSize shared by every job of this call */
+    uint8_t  plane_type;     /* 0 PLANE_TYPE_Y, 1 PLANE_TYPE_UV, shared */
+    uint8_t  sharpness;      /* 0..7: static_config.sharpness */
+    uint8_t  eob_fast_inter; /* rdoq_ctrls.eob_fast_{y,uv}_inter of this plane type */
+    uint8_t  eob_fast_intra; /* rdoq_ctrls.eob_fast_{y,uv}_intra */
+    uint8_t  eob_th;         /* rdoq_ctrls.eob_th, 255 = off (as set_rdoq_controls writes it) */
+    uint8_t  eob_fast_th;    /* rdoq_ctrls.eob_fast_th, 255 = off */
+    uint8_t  reserved;
+    uint32_t n_jobs;
+    uint32_t lambda;
+    const SvtHipRdoqJob    *jobs;        /* device pointers */
+    const SvtHipRateTables *tables;
+    const SvtHipQuantRow   *quant_rows;  /* only `dequant` is read */
+    uint32_t                n_quant_rows, reserved2;
+    const uint8_t          *iqmatrix;    /* optional, as SvtHipRdBatchDesc.iqmatrix: applied to the 2-D tx types only (get_dqv) */
+    const int32_t          *coeff;       /* [n_jobs][min(W,32)*min(H,32)] */
+    int32_t                *qcoeff, *dqcoeff; /* in place */
+    uint16_t               *eob;         /* [n_jobs], in place */
+    /* optional outputs */
+    uint8_t  *status;                    /* [n_jobs] 0 optimised; 1 eob == 0 on entry or after the fast trim (nothing else done); 2 the eob_th gate
+                                          * fired; 0xFF undefined input */
+    uint64_t *dist_coeff;                /* [n_jobs][2] svt_full_distortion_kernel32_bits of the final coeff / dqcoeff, the meaning of
+                                          * SvtHipRdBatchDesc.dist_coeff: svt_hip_coeff_rate_batch reads it with dist_stride 2 */
+    uint8_t  *cul_level;                 /* [n_jobs] */
+    /* optional fallback behind the eob_th gate, all three or none: the arrays svt_hip_rd_batch writes for the same jobs with quant_kind 0 */
+    const int32_t  *qcoeff_b, *dqcoeff_b;
+    const uint16_t *eob_b;
+} SvtHipRdoqDesc;
+
+/* Enqueues one batch on the context stream (asynchronous).  Returns non-zero and enqueues nothing when the descriptor fails validation: a null
+ * context, descriptor or mandatory pointer (jobs, tables, quant_rows, coeff, qcoeff, dqcoeff, eob), tx_size >= 19, plane_type > 1,
+ * sharpness > 7, n_quant_rows == 0, a fallback with one of its three arrays missing.  (The kernel loads single coefficients: no alignment
+ * beyond the element's is asked for.)
+ * The jobs live in device memory, where the host cannot refuse them.  Where the reference is undefined -- eob above the coefficient count, a zero
+ * coefficient at scan[eob - 1], a context or tx_type outside its table, quant_row >= n_quant_rows -- a job writes nothing but status 0xFF; its
+ * neighbours are not affected.  A job behind the eob_th gate without fallback arrays writes nothing but status 2.  dist_coeff and cul_level are
+ * written for status 0 and 1, and for status 2 with fallback arrays. */
+int    svt_hip_rdoq_batch(SvtHipContext *ctx, const SvtHipRdoqDesc *d);
+size_t svt_hip_rdoq_desc_size(void); /* sizeof(SvtHipRdoqDesc) as compiled */
 
 /* Full-pel motion-compensated prediction from ME results: every 16x16 PU copies the block of `ref` displaced by its
  * best integer MV (sb_best_mv = SvtHipMeResults.sb_best_mv, device pointer; list / ref_idx select the reference).

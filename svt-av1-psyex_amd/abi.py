@@ -241,6 +241,27 @@ RATE_UNDEFINED = 0xFFFFFFFFFFFFFFFF  # bits / rd_cost / best_cost of a job (grou
 RATE_NO_JOB = 0xFFFFFFFF             # best_job of such a group
 
 
+
+class RdoqJob(C.Structure):  # SvtHipRdoqJob
+    _fields_ = [("tx_type", C.c_uint8), ("txb_skip_ctx", C.c_uint8), ("dc_sign_ctx", C.c_uint8), ("is_inter", C.c_uint8), ("quant_row", C.c_uint8),
+                ("flags", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class RdoqDesc(C.Structure):  # SvtHipRdoqDesc
+    _fields_ = [("tx_size", C.c_uint8), ("plane_type", C.c_uint8), ("sharpness", C.c_uint8), ("eob_fast_inter", C.c_uint8), ("eob_fast_intra", C.c_uint8),
+                ("eob_th", C.c_uint8), ("eob_fast_th", C.c_uint8), ("reserved", C.c_uint8), ("n_jobs", C.c_uint32), ("lambda_", C.c_uint32),
+                ("jobs", C.c_void_p), ("tables", C.c_void_p), ("quant_rows", C.c_void_p), ("n_quant_rows", C.c_uint32), ("reserved2", C.c_uint32),
+                ("iqmatrix", C.c_void_p), ("coeff", C.c_void_p), ("qcoeff", C.c_void_p), ("dqcoeff", C.c_void_p), ("eob", C.c_void_p),
+                ("status", C.c_void_p), ("dist_coeff", C.c_void_p), ("cul_level", C.c_void_p),
+                ("qcoeff_b", C.c_void_p), ("dqcoeff_b", C.c_void_p), ("eob_b", C.c_void_p)]
+
+
+RDOQ_JOB_DTYPE = [("tx_type", "u1"), ("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"), ("is_inter", "u1"), ("quant_row", "u1"), ("flags", "u1"),
+                  ("reserved", "u1", (2,))]
+RDOQ_FLAG_SHARP = 1
+# SvtHipRdoqDesc.status
+RDOQ_OPTIMISED, RDOQ_EMPTY, RDOQ_GATED, RDOQ_UNDEFINED = 0, 1, 2, 0xFF
+
 # ---- include/svt_hip_pme.h ----
 class Mv(C.Structure):
     _fields_ = [("row", C.c_int16), ("col", C.c_int16)]

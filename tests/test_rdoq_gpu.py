@@ -1,0 +1,212 @@
+"""GPU: svt_hip_rdoq_batch on the MI355X, every comparison exact -- against the reference's own results (golden/rdoq.npz) and the restatement
+(tests/rdoq_cases.py) for every size and control variant, the jobs the reference leaves undefined, the eob_th gate with and without the fallback
+arrays, rejected descriptors, and the device-side chain RD batch -> RDOQ -> rate batch -> inverse transform."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import coeff_rate_cases as cr
+import rdoq_cases as rq
+from svt_av1_psyex_amd import abi, api, rate, rd, rdoq
+
+pytestmark = pytest.mark.gpu
+
+FILL = 0xA5
+CONTROLS = rdoq.CONTROLS
+
+
+@pytest.fixture(scope="module")
+def dev_tables(hip_ctx):
+    return [rate.upload_tables(T) for T in rq.shared()["tables"]]
+
+
+def run(ctx, dev_table, c, inp, n, fallback=True):
+    """the batch on the first n jobs of a case, every array pre-filled with 0xA5 and followed by n spare slots: checks the guards and that coeff is
+    unchanged, returns the rest cut to n jobs"""
+    fb = (inp["qcoeff_b"][:n], inp["dqcoeff_b"][:n], inp["eob_b"][:n]) if fallback else None
+    out = rdoq.run_rdoq_hip(ctx, dev_table, c["tx_size"], c["plane"], c["jobs"][:n], c["quant_rows"], c["coeff"][:n], inp["qcoeff"][:n], inp["dqcoeff"][:n],
+                            inp["eob"][:n], c["lam"], iqmatrix=c["iqmatrix"], fallback=fb, spare_jobs=n, fill=FILL, **{k: c[k] for k in CONTROLS})
+    res = {}
+    for name, a in out.items():
+        assert len(a) == 2 * n, name
+        assert np.all(np.ascontiguousarray(a[n:]).view(np.uint8) == FILL), f"{name}: spare slots written"
+        res[name] = a[:n]
+    assert np.array_equal(res.pop("coeff"), c["coeff"][:n]), "coeff changed"
+    return res
+
+
+def compare(got, want, n, what):
+    """device == expectation on every output; where a job writes no dist_coeff / cul_level the pre-fill must still be there"""
+    for name in ("status", "eob", "qcoeff", "dqcoeff"):
+        bad = [i for i in range(n) if not np.array_equal(got[name][i], want[name][i])]
+        assert not bad, (what, name, bad[:6], [int(want["status"][i]) for i in bad[:6]])
+    w = want["written"][:n]
+    assert np.array_equal(got["dist_coeff"][w], want["dist_coeff"][:n][w]) and np.array_equal(got["cul_level"][w], want["cul_level"][:n][w]), what
+    assert np.all(got["dist_coeff"][~w].view(np.uint8) == FILL) and np.all(got["cul_level"][~w] == FILL), what
+
+
+@pytest.mark.parametrize("tx_size", range(cr.N_TX_SIZES))
+def test_every_size_and_variant_equals_the_fixture_and_the_restatement(hip_ctx, dev_tables, tx_size):
+    """luma and chroma, every class the size admits, inter / intra, 8- and 10-bit rows, flat and with a quantization matrix, the lambdas, and the
+    control variants: plain, sharp jobs mixed in, sharpness 4 and 7, eob_fast_* on, eob_fast_th 30 and 0, eob_th 85 (here with the fallback arrays)"""
+    cases = rq.shared()["cases"]
+    ran = 0
+    for k, c in enumerate(cases):
+        if c["tx_size"] != tx_size:
+            continue
+        inp, want, _ = rq.restated(k)
+        n = len(c["jobs"])
+        assert n % max(1, 64 // c["coeff"].shape[1]) or c["coeff"].shape[1] >= 64  # a wave's last group has no job
+        got = run(hip_ctx, dev_tables[c["table"]], c, inp, n)
+        name = rq.VARIANTS[c["variant"]][0]
+        compare(got, want, n, name)
+        ref = c["ref"]  # the reference's own
+        assert np.array_equal(got["qcoeff"], ref["qcoeff"]) and np.array_equal(got["eob"], ref["eob"]), name
+        assert np.array_equal(got["cul_level"], ref["cul_level"]) and np.array_equal(got["status"], ref["status"]), name
+        assert rq.crc(got["dqcoeff"]) == ref["dqcoeff_crc"], name
+        ran += 1
+    assert ran == len(rq.VARIANTS)
+
+
+@pytest.mark.parametrize("tx_size", [0, 5, 2, 4])  # four, two and one job per wave
+def test_undefined_jobs_report_0xff_write_nothing_else_and_leave_their_neighbours(hip_ctx, dev_tables, tx_size):
+    c, inp, bad = rq.undefined_case(tx_size)
+    assert len(bad) == 7
+    n = len(c["jobs"])
+    want = rq.run_case(rq.shared()["tables"][c["table"]], c, inp, True)
+    assert np.all(want["status"][bad] == rq.ST_UNDEFINED) and np.count_nonzero(want["status"] == rq.ST_UNDEFINED) == len(bad)
+    assert not np.any(want["written"][bad])
+    assert np.array_equal(want["qcoeff"][bad], inp["qcoeff"][bad]) and np.array_equal(want["eob"][bad], inp["eob"][bad])
+    got = run(hip_ctx, dev_tables[c["table"]], c, inp, n)
+    compare(got, want, n, "undefined")
+    assert np.any(want["qcoeff"] != inp["qcoeff"])  # the neighbours are optimised as usual
+
+
+@pytest.mark.parametrize("tx_size", [0, 6, 2, 9, 3])  # no 64-point size: its eob_perc stays below 85 (at most 1024 of 2048 coefficients)
+def test_eob_th_gate_with_and_without_the_fallback_arrays(hip_ctx, dev_tables, tx_size):
+    cases = rq.shared()["cases"]
+    k = next(k for k, c in enumerate(cases) if c["tx_size"] == tx_size and rq.VARIANTS[c["variant"]][0] == "eob_th85")
+    c = cases[k]
+    inp, want_fb, _ = rq.restated(k)
+    n = len(c["jobs"])
+    gated = want_fb["status"] == rq.ST_GATED
+    assert 0 < np.count_nonzero(gated) < n
+    # with them: the reference's re-quantization with the "b" quantizer
+    got = run(hip_ctx, dev_tables[c["table"]], c, inp, n, fallback=True)
+    compare(got, want_fb, n, "with fallback")
+    assert np.array_equal(got["qcoeff"][gated], c["ref"]["qcoeff"][gated]) and np.array_equal(got["eob"][gated], c["ref"]["eob"][gated])
+    assert np.any(inp["qcoeff_b"][gated] != inp["qcoeff"][gated])  # "b" and "fp" differ: the copy is visible
+    # without them: the job is left untouched
+    want = rq.run_case(rq.shared()["tables"][c["table"]], c, inp, False)
+    assert np.array_equal(want["status"], want_fb["status"]) and not np.any(want["written"][gated]) and np.all(want["written"][~gated])
+    got = run(hip_ctx, dev_tables[c["table"]], c, inp, n, fallback=False)
+    compare(got, want, n, "without fallback")
+    assert np.array_equal(got["qcoeff"][gated], inp["qcoeff"][gated]) and np.array_equal(got["dqcoeff"][gated], inp["dqcoeff"][gated])
+    assert np.array_equal(got["eob"][gated], inp["eob"][gated]) and np.all(got["status"][gated] == rq.ST_GATED)
+
+
+@pytest.mark.parametrize("bad", ["tx_size_19", "plane_type_2", "sharpness_8", "no_coeff", "no_tables", "zero_quant_rows", "fallback_without_eob_b"])
+def test_rejected_descriptor_returns_non_zero_and_leaves_the_buffers_as_filled(hip_ctx, dev_tables, bad):
+    import torch
+    n, npk = 6, 256
+    fill = lambda nbytes: torch.full((nbytes,), FILL, dtype=torch.uint8, device="cuda")
+    bufs = {"jobs": fill(8 * n), "quant_rows": fill(28), "coeff": fill(4 * n * npk), "qcoeff": fill(4 * n * npk), "dqcoeff": fill(4 * n * npk), "eob": fill(2 * n),
+            "status": fill(n), "dist_coeff": fill(16 * n), "cul_level": fill(n), "qcoeff_b": fill(4 * n * npk), "dqcoeff_b": fill(4 * n * npk), "eob_b": fill(2 * n)}
+    d = abi.RdoqDesc(tx_size=2, plane_type=0, eob_th=255, eob_fast_th=255, n_jobs=n, lambda_=100, tables=dev_tables[0].data_ptr(), n_quant_rows=1,
+                     **{name: t.data_ptr() for name, t in bufs.items()})
+    if bad == "tx_size_19":
+        d.tx_size = 19
+    elif bad == "plane_type_2":
+        d.plane_type = 2
+    elif bad == "sharpness_8":
+        d.sharpness = 8
+    elif bad == "zero_quant_rows":
+        d.n_quant_rows = 0
+    elif bad.startswith("no_"):
+        setattr(d, bad[3:], None)
+    else:
+        d.eob_b = None
+    torch.cuda.synchronize()
+    assert api.lib().svt_hip_rdoq_batch(hip_ctx._h, C.byref(d)) != 0
+    assert b"svt_hip_rdoq_batch" in api.lib().svt_hip_last_error(None)
+    hip_ctx.sync()
+    for name, t in bufs.items():
+        assert bool(torch.all(t == FILL)), name
+
+
+@pytest.mark.parametrize("tx_size", [0, 2, 17, 4])  # TX_4X4, TX_16X16, TX_16X64, TX_64X64
+def test_chain_rd_batch_rdoq_rate_batch_inverse_on_device(hip_ctx, dev_tables, tx_size):
+    """tx_type_search with RDOQ on the device: svt_hip_rd_batch (quant_kind 1) writes coeff / qcoeff / dqcoeff / eob / dist_coeff, svt_hip_rdoq_batch
+    rewrites them in place, svt_hip_coeff_rate_batch prices them (dist_stride 2 on the renewed dist_coeff) and picks the groups' winners,
+    svt_hip_inv_txfm_batch reconstructs from the optimised dqcoeff -- all on the same stream and buffers, one synchronisation at the end.  The
+    inverse runs on every candidate (choosing the winners' jobs on the host would need a second synchronisation); the winners' blocks are the ones
+    checked.  Equal to the restatements fed with the oracle's RD outputs."""
+    import pyoracle
+    import torch
+    T = rq.shared()["tables"][0]
+    rng = np.random.default_rng(2300 + tx_size)
+    W, H = 192, 128
+    src = rng.integers(0, 1024, (H, W)).astype(np.uint16)
+    pred = np.clip(src.astype(np.int32) + rng.integers(-90, 91, src.shape), 0, 1023).astype(np.uint16)
+    jobs = rd.grid_jobs(W, H, W, tx_size)
+    n = len(jobs)
+    types = [t for t in range(16) if cr.EXT_TX_USED[cr.ext_tx_set_type(tx_size, 1, 0)][t]]
+    jobs["tx_type"] = [types[i % len(types)] for i in range(n)]
+    rows = np.stack([rd.quant_row_from_step(160, 220)])
+    f = dict(bit_depth=10, quant_kind=1, tx_size=tx_size, src_stride=W, pred_stride=W)
+    qjobs = np.zeros(n, abi.RDOQ_JOB_DTYPE)
+    qjobs["tx_type"], qjobs["txb_skip_ctx"], qjobs["dc_sign_ctx"], qjobs["is_inter"] = jobs["tx_type"], np.arange(n) % 13, np.arange(n) % 3, 1
+    rjobs = np.zeros(n, abi.RATE_JOB_DTYPE)
+    for name in ("tx_type", "txb_skip_ctx", "dc_sign_ctx", "is_inter"):
+        rjobs[name] = qjobs[name]
+    if len(types) > 1:
+        group_start = np.arange(0, n + 1, len(types), dtype=np.uint32)
+    else:
+        starts = [0]
+        while starts[-1] < n:
+            starts.append(min(n, starts[-1] + (2, 3, 1)[(len(starts) - 1) % 3]))
+        group_start = np.array(starts, np.uint32)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    t_qjobs, t_rjobs, t_gs, t_rows, t_jobs, t_pred = dev(qjobs), dev(rjobs), dev(group_start), dev(rows), dev(jobs), dev(pred)
+    t_rec = t_pred.clone()
+    lam, ctl = 41000, dict(sharpness=0, eob_fast_inter=0, eob_fast_intra=0, eob_th=255, eob_fast_th=60)
+    rd_run = rd.enqueue_hip(hip_ctx, f, src, pred, jobs, rows, outputs=("coeff", "qcoeff", "dqcoeff"))
+    o = rd_run.outs
+    q_out = rdoq.run_rdoq_device(hip_ctx, dev_tables[0], tx_size, 0, t_qjobs, n, t_rows, 1, o["coeff"], o["qcoeff"], o["dqcoeff"], o["eob"], lam,
+                                 dist_coeff=o["dist_coeff"], outputs=("status", "cul_level"), **ctl)
+    res = rate.run_rate_device(hip_ctx, dev_tables[0], tx_size, 0, t_rjobs, n, o["qcoeff"], o["eob"], lam=lam, dist=o["dist_coeff"], dist_stride=2,
+                               group_start=t_gs, n_groups=len(group_start) - 1)
+    d = abi.InvTxBatchDesc(bit_depth=10, sample_bytes=2, tx_size=tx_size, n_jobs=n, pred_stride=W, recon_stride=W, pred=t_pred.data_ptr(),
+                           recon=t_rec.data_ptr(), jobs=t_jobs.data_ptr(), dqcoeff=o["dqcoeff"].data_ptr())
+    hip_ctx.check(api.lib().svt_hip_inv_txfm_batch(hip_ctx._h, C.byref(d)), "svt_hip_inv_txfm_batch")
+    hip_ctx.sync()  # the one synchronisation
+    got_rd, got_q, got_rate = rd_run.download(), rdoq.download(q_out), rate.download(res)
+    recon = t_rec.cpu().numpy().view(np.uint16).reshape(H, W)
+
+    want_rd = pyoracle.rd_batch(f, src, pred, jobs, rows, want_recon=False)
+    case = dict(tx_size=tx_size, plane=0, jobs=qjobs, coeff=want_rd["coeff"], quant_rows=rows, iqmatrix=None, lam=lam, **ctl)
+    inp = {"qcoeff": want_rd["qcoeff"], "dqcoeff": want_rd["dqcoeff"], "eob": want_rd["eob"].reshape(-1)}
+    want = rq.run_case(T, case, inp, False)
+    assert np.all(want["status"] != rq.ST_UNDEFINED) and np.count_nonzero((want["qcoeff"] != inp["qcoeff"]).any(axis=1)) > n // 10  # RDOQ acts: the chain is sensitive to it
+    assert np.array_equal(got_q["status"], want["status"]) and np.array_equal(got_q["cul_level"], want["cul_level"])
+    assert np.array_equal(got_rd["coeff"], want_rd["coeff"])
+    assert np.array_equal(got_rd["qcoeff"], want["qcoeff"]) and np.array_equal(got_rd["dqcoeff"], want["dqcoeff"])
+    assert np.array_equal(got_rd["eob"].reshape(-1), want["eob"]) and np.array_equal(got_rd["dist_coeff"], want["dist_coeff"])
+    rc = {"tx_size": tx_size, "plane": 0, "reduced": 0, "jobs": rjobs, "qcoeff": want["qcoeff"], "eob": want["eob"]}
+    _, bits = cr.run_case(T, rc, variants=[(1, 0)])
+    assert np.array_equal(got_rate["bits"], bits[0])
+    cost = np.array([cr.rdcost(lam, int(b), int(dd)) for b, dd in zip(bits[0], want["dist_coeff"][:, 0])], np.uint64)
+    assert np.array_equal(got_rate["rd_cost"], cost)
+    want_job, want_cost = cr.group_winners(cost, group_start)
+    assert np.array_equal(got_rate["best_job"], want_job) and np.array_equal(got_rate["best_cost"], want_cost)
+    L = pyoracle.load_oracle()
+    tw, th = abi.TX_W[tx_size], abi.TX_H[tx_size]
+    for j in want_job.tolist():
+        off = int(jobs["pred_offset"][j])
+        y, x = divmod(off, W)
+        blk = np.zeros((th, tw), np.uint16)
+        dq = np.ascontiguousarray(want["dqcoeff"][j])
+        L.orc_inv_txfm2d_add(dq.ctypes.data_as(C.c_void_p), C.c_void_p(pred.ctypes.data + 2 * off), W, blk.ctypes.data_as(C.c_void_p), tw,
+                             int(jobs["tx_type"][j]), tx_size, 10)
+        assert np.array_equal(recon[y:y + th, x:x + tw], blk), j
