@@ -351,3 +351,35 @@ class TplGroupDesc(C.Structure):  # SvtHipTplGroupDesc
     _fields_ = [("width", C.c_uint16), ("height", C.c_uint16), ("aligned_width", C.c_uint16), ("aligned_height", C.c_uint16),
                 ("synth_blk_size", C.c_uint8), ("sb_size", C.c_uint8), ("compute_rate", C.c_uint8), ("superres_denom", C.c_uint8),
                 ("stages", C.c_uint32), ("n_frames", C.c_uint32), ("frames", C.POINTER(TplGroupFrame))]
+
+
+# ---- include/svt_hip_pred.h ----
+INTER_PRED_MAX_REFS = 8
+INTER_PRED_NO_REF = 0xFF
+INTER_PRED_MV0_FROM_ARRAY, INTER_PRED_MV1_FROM_ARRAY = 1, 2
+INTER_PRED_OK, INTER_PRED_UNDEFINED = 0, 0xFF
+
+
+class InterPredRef(C.Structure):  # SvtHipInterPredRef
+    _fields_ = [("plane", C.c_void_p), ("stride", C.c_uint32), ("org_x", C.c_uint16), ("org_y", C.c_uint16), ("width", C.c_uint16), ("height", C.c_uint16),
+                ("reserved", C.c_uint32)]
+
+
+class InterPredJob(C.Structure):  # SvtHipInterPredJob
+    _fields_ = [("dst_offset", C.c_uint32), ("org_x", C.c_int16), ("org_y", C.c_int16), ("width", C.c_uint8), ("height", C.c_uint8), ("filter_x", C.c_uint8),
+                ("filter_y", C.c_uint8), ("ref", C.c_uint8 * 2), ("flags", C.c_uint8), ("comp_mode", C.c_uint8), ("mv", (C.c_int16 * 2) * 2),
+                ("mv_index", C.c_uint32 * 2), ("mb_to_left_edge", C.c_int32), ("mb_to_right_edge", C.c_int32), ("mb_to_top_edge", C.c_int32),
+                ("mb_to_bottom_edge", C.c_int32), ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
+class InterPredDesc(C.Structure):  # SvtHipInterPredDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("ss_x", C.c_uint8), ("ss_y", C.c_uint8), ("n_refs", C.c_uint8), ("n_jobs", C.c_uint32),
+                ("refs", InterPredRef * INTER_PRED_MAX_REFS), ("dst", C.c_void_p), ("dst_stride", C.c_uint32), ("reserved", C.c_uint32),
+                ("dst_samples", C.c_uint64), ("jobs", C.c_void_p), ("mv_array", C.c_void_p), ("n_mvs", C.c_uint32), ("reserved2", C.c_uint32),
+                ("status", C.c_void_p)]
+
+
+INTER_PRED_JOB_DTYPE = [("dst_offset", "<u4"), ("org_x", "<i2"), ("org_y", "<i2"), ("width", "u1"), ("height", "u1"), ("filter_x", "u1"), ("filter_y", "u1"),
+                        ("ref", "u1", (2,)), ("flags", "u1"), ("comp_mode", "u1"), ("mv", "<i2", (2, 2)), ("mv_index", "<u4", (2,)),
+                        ("mb_to_left_edge", "<i4"), ("mb_to_right_edge", "<i4"), ("mb_to_top_edge", "<i4"), ("mb_to_bottom_edge", "<i4"),
+                        ("fwd_offset", "u1"), ("bck_offset", "u1"), ("reserved", "u1", (6,))]
