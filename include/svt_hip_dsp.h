@@ -183,6 +183,11 @@ uint64_t svt_hip_spy_rd_bias(uint64_t sse, uint32_t area_width, uint32_t area_he
 /* Enqueues one batch on the context stream (asynchronous); one wave per job. */
 int svt_hip_block_stats_batch(SvtHipContext *ctx, const SvtHipBlockStatsDesc *d);
 
+/* Flat jobs one wave of that launch works through, one after the other: 4, or 1 for a hadamard_path batch (d->satd set) of too few jobs to
+ * give every compute unit several four-job waves.  The launch itself asks this function; outputs do not depend on the answer.  Reads
+ * d->satd and d->n_jobs only; 0 for a null argument. */
+uint32_t svt_hip_block_stats_jobs_per_wave(SvtHipContext *ctx, const SvtHipBlockStatsDesc *d);
+
 /* ---- batched SSIM distortion (--tune 2 / 3 / 4) -------------------------------------------------------------------
  * Per job, src = input, ref = prediction or reconstruction:
  *   ssim       the block mean ssim() / ssim_hbd() returns (Codec/mode_decision.c:4781-4878): 8x8 tiles when both sides are multiples

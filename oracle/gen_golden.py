@@ -331,7 +331,47 @@ def gen_md_edges():
     print("md_search_edges.npz", {k: v.shape for k, v in out.items()})
 
 
-GENERATORS = {"md": gen_md_search, "md_edges": gen_md_edges, "pyramid": gen_pyramid, "me": gen_me, "me_mctf": lambda: gen_me(only=["me_vga_m4_mctf"]), "sad": gen_sad_kernels, "presets": gen_presets, "stats": gen_block_stats, "dg": gen_dg_detector, "tpl": gen_tpl_chain, "rd": gen_rd_chain}
+def save_npz_fixed(path, arrays):
+    """an .npz whose bytes depend on the arrays alone (np.savez stamps every member with the time of day)"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), version=(1, 0), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type, info.external_attr = zipfile.ZIP_DEFLATED, 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def gen_block_stats_edges():
+    """The reference's `_c` block statistics on tests/stats_edge_cases.py's sets: the Walsh atlas, the range-limit blocks and the first jobs of
+    the packed list.  Stored: the outputs, the mask of the jobs each is defined on, and a CRC of the regenerated inputs (not the planes).
+    Nothing is written unless the packed list meets its coverage conditions and the oracle agrees with the reference on every value."""
+    import stats_edge_cases as ec
+    ref, oracle = pyoracle.load_ref(), pyoracle.load_oracle()
+    for av1_only in (True, False):  # the whole list the tests start from, of which the fixture stores the first jobs
+        src, refp, jobs, kinds = ec.standard_packed(av1_only)
+        val, ok = ec.reference_outputs(ref, src, refp, jobs, 8)
+        got = ec.oracle_outputs(oracle, src, refp, jobs, 8)
+        assert not ec.disagreements(val, ok, got), (av1_only, ec.disagreements(val, ok, got))
+        print("packed list", len(jobs), "jobs:", ec.assert_packed_coverage(jobs, kinds, got["satd"]))
+    out = {}
+    for name, (bd, src, refp, jobs) in ec.fixture_sets().items():
+        val, ok = ec.reference_outputs(ref, src, refp, jobs, bd)
+        bad = ec.disagreements(val, ok, ec.oracle_outputs(oracle, src, refp, jobs, bd))
+        assert not bad, (name, bad)
+        if name == "walsh":
+            assert ok["satd"].all() and np.array_equal(val["satd"], ec.walsh_jobs()[1])
+        out[name + "_crc"] = np.uint32(ec.inputs_crc(src, refp, jobs))
+        for k in ec.COLUMNS:
+            if ok[k].any():
+                out[f"{name}_{k}"], out[f"{name}_ok_{k}"] = val[k], ok[k].astype(np.uint8)
+    save_npz_fixed(ec.GOLDEN, out)
+    print("block_stats_edges.npz", len(out), "arrays,", os.path.getsize(ec.GOLDEN), "bytes")
+
+
+GENERATORS = {"block_stats_edges": gen_block_stats_edges, "md": gen_md_search, "md_edges": gen_md_edges, "pyramid": gen_pyramid, "me": gen_me, "me_mctf": lambda: gen_me(only=["me_vga_m4_mctf"]), "sad": gen_sad_kernels, "presets": gen_presets, "stats": gen_block_stats, "dg": gen_dg_detector, "tpl": gen_tpl_chain, "rd": gen_rd_chain}
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)

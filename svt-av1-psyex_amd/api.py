@@ -44,6 +44,8 @@ def lib():
         for name in ("svt_hip_context_destroy", "svt_hip_context_sync"):
             getattr(L, name).argtypes = [C.c_void_p]
         L.svt_hip_pa_picture_destroy.argtypes = [C.c_void_p, C.c_void_p]
+        L.svt_hip_block_stats_jobs_per_wave.restype = C.c_uint32
+        L.svt_hip_block_stats_jobs_per_wave.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

@@ -614,6 +614,11 @@ __global__ void __launch_bounds__(64) hadamard_kernel(const int16_t *src, int st
 
 extern "C" {
 
+uint32_t svt_hip_block_stats_jobs_per_wave(SvtHipContext *ctx, const SvtHipBlockStatsDesc *d) {
+    if (!ctx || !d) return 0;
+    return (d->satd && d->n_jobs < (uint32_t)ctx->num_cus * 8u * kJobsPerWave) ? 1 : kJobsPerWave;
+}
+
 int svt_hip_block_stats_batch(SvtHipContext *ctx, const SvtHipBlockStatsDesc *d) {
     if (!ctx || !d) return SVT_HIP_ERR_BAD_PARAM;
     if (d->n_jobs == 0 && d->n_pyramids == 0) return SVT_HIP_OK;
@@ -631,7 +636,7 @@ int svt_hip_block_stats_batch(SvtHipContext *ctx, const SvtHipBlockStatsDesc *d)
     // still gives every CU several waves -- a one-picture batch's edge jobs are otherwise the launch's critical path
     // (hadamard_path batches only: the psy / facade batches finish a wave's four jobs side by side, one tile per lane -- measured 32 us with four
     // jobs per wave, 42 us with one, on the 2160p batch's 3,720 edge jobs)
-    p.jpw = (d->satd && d->n_jobs < (uint32_t)ctx->num_cus * 8u * kJobsPerWave) ? 1 : kJobsPerWave;
+    p.jpw = svt_hip_block_stats_jobs_per_wave(ctx, d);
     const uint32_t flat = (d->n_jobs + p.jpw - 1) / p.jpw; // waves of the flat list
     p.n_front = d->n_pyramids;
     if (d->satd && d->n_pyramids) // (8-bit planes: checked above)

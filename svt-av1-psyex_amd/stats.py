@@ -37,44 +37,63 @@ def expand_pyramid(region, src_stride, ref_stride):
     return out
 
 
-def run_hip(ctx, src, ref, jobs, bit_depth, satd=True, psy_rd=None, facade=None, pyramids=None):
+def jobs_per_wave(ctx, n_jobs, satd=True):
+    """svt_hip_block_stats_jobs_per_wave: the flat jobs one wave of a batch of n_jobs works through (the launch asks the same function)"""
+    from . import api
+    d = abi.BlockStatsDesc(bit_depth=8, n_jobs=n_jobs, satd=1 if satd else 0)  # only the pointer's presence is read
+    return int(api.lib().svt_hip_block_stats_jobs_per_wave(ctx._h, C.byref(d)))
+
+
+def run_hip(ctx, src, ref, jobs, bit_depth, satd=True, psy_rd=None, facade=None, pyramids=None, spare_jobs=0, fill=None, outputs=None):
     """facade: dict(pred_mode=u8[n], compound_type=u8[n], temporal_layer_index=int, spy_rd=int) -> also `facade_dist`.
     pyramids: optional array of 64x64 region jobs; their 85 outputs each follow the plain jobs' (slots len(jobs) + 85 k ...; the facade
-    arrays then cover those slots too)."""
+    arrays then cover those slots too).
+    fill: a byte every output array is pre-filled with (default: zeros); the arrays are then n + spare_jobs slots long, and the spare
+    slots and the source, reference and job buffers are asserted to read back unchanged.
+    outputs: the names of the output pointers to set (the others stay null; `satd` is then read from this list); the arrays of the
+    others are returned as well, as they were filled."""
     import torch
     from . import api
     L = api.lib()
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
     n_plain = len(jobs)
     n = n_plain + (abi.PYRAMID_BLOCKS * len(pyramids) if pyramids is not None else 0)
-    t_src, t_ref, t_jobs = dev(src), dev(ref), dev(jobs if n_plain else np.zeros(1, abi.BLOCK_JOB_DTYPE))
+    inputs = [src, ref, jobs if n_plain else np.zeros(1, abi.BLOCK_JOB_DTYPE)]
+    t_src, t_ref, t_jobs = (dev(a) for a in inputs)
     fields = list(abi.STATS_OUT_FIELDS) + (list(abi.PSY_OUT_FIELDS) if psy_rd is not None else []) + (list(abi.FACADE_OUT_FIELDS) if facade else []) + (list(abi.VAR10_OUT_FIELDS) if bit_depth == 10 else [])
-    outs = {name: torch.zeros(n * np.dtype(dt).itemsize, dtype=torch.uint8, device="cuda") for name, dt in fields}
+    if outputs is not None:
+        assert set(outputs) <= {name for name, _ in fields}, outputs
+        satd = "satd" in outputs
+    wanted = lambda name: (name in outputs) if outputs is not None else (satd or name != "satd")
+    n_alloc = n + (spare_jobs if fill is not None else 0)
+    outs = {name: torch.full((n_alloc * np.dtype(dt).itemsize,), fill or 0, dtype=torch.uint8, device="cuda") for name, dt in fields}
     d = abi.BlockStatsDesc(bit_depth=bit_depth, n_jobs=n_plain, src_stride=src.shape[1], ref_stride=ref.shape[1])
     if pyramids is not None and len(pyramids):
+        inputs.append(pyramids)
         t_pyr = dev(pyramids)
         d.n_pyramids, d.pyramid_out_base, d.pyramids = len(pyramids), n_plain, t_pyr.data_ptr()
     if psy_rd is not None:
         d.psy_rd = psy_rd
-        for name, _ in abi.PSY_OUT_FIELDS:
-            setattr(d, name, outs[name].data_ptr())
-    if bit_depth == 10:
-        d.variance10, d.var_sse10 = outs["variance10"].data_ptr(), outs["var_sse10"].data_ptr()
     if facade:
         t_mode, t_comp = dev(np.asarray(facade["pred_mode"], np.uint8)), dev(np.asarray(facade["compound_type"], np.uint8))
-        d.pred_mode, d.compound_type, d.facade_dist = t_mode.data_ptr(), t_comp.data_ptr(), outs["facade_dist"].data_ptr()
+        d.pred_mode, d.compound_type = t_mode.data_ptr(), t_comp.data_ptr()
         d.temporal_layer_index, d.spy_rd = facade["temporal_layer_index"], facade["spy_rd"]
     d.src, d.ref, d.jobs = t_src.data_ptr(), t_ref.data_ptr(), t_jobs.data_ptr()
-    for name, _ in abi.STATS_OUT_FIELDS:
-        if name == "satd" and not satd:
-            continue
-        setattr(d, name, outs[name].data_ptr())
+    for name, _ in fields:
+        if wanted(name):
+            setattr(d, name, outs[name].data_ptr())
     torch.cuda.synchronize()
     rc = L.svt_hip_block_stats_batch(ctx._h, C.byref(d))
     ctx.check(rc, "svt_hip_block_stats_batch")
     ctx.sync()
     res = {name: outs[name].cpu().numpy().view(dt) for name, dt in fields}
-    if not satd:
+    if fill is not None:
+        for name in res:
+            assert (res[name][n:].view(np.uint8) == fill).all(), f"{name}: a slot past the batch's {n} was written"
+            res[name] = res[name][:n]
+        for a, t in zip(inputs, [t_src, t_ref, t_jobs] + ([t_pyr] if len(inputs) == 4 else [])):
+            assert np.array_equal(t.cpu().numpy(), np.ascontiguousarray(a).view(np.uint8).reshape(-1)), "an input buffer of the batch was written"
+    if outputs is None and not satd:
         res.pop("satd")
     return res
 
