@@ -57,7 +57,12 @@ typedef struct SvtHipPmeJob {
 typedef struct SvtHipPmeBatchDesc {
     uint32_t n_jobs;
     uint32_t src_stride, ref_stride; /* in samples */
-    const uint8_t      *src, *ref;   /* device pointers, 8-bit planes */
+    const uint8_t      *src, *ref;   /* device pointers, 8-bit planes.  `ref` must be readable for ONE byte behind the last reference sample
+                                      * any job's search reads (its last visited row of positions, last block row, last group's eighth
+                                      * position + width - 1): each position quad loads its reference row as dwords, width + 4 bytes from
+                                      * the quad's first position, of which the last byte belongs to no position.  It is loaded, never
+                                      * used.  A window that ends at the plane's last sample thus needs a plane buffer one byte longer;
+                                      * inside a row the byte is the next sample of the plane.  `src` is read exactly. */
     const SvtHipPmeJob *jobs;        /* device pointer */
     int32_t  mv_cost_type, error_per_bit; /* mv_cost_params->mv_cost_type / error_per_bit */
     const int32_t *mvjcost;          /* device pointer, 4 entries */

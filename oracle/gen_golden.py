@@ -371,7 +371,25 @@ def gen_block_stats_edges():
     print("block_stats_edges.npz", len(out), "arrays,", os.path.getsize(ec.GOLDEN), "bytes")
 
 
-GENERATORS = {"block_stats_edges": gen_block_stats_edges, "md": gen_md_search, "md_edges": gen_md_edges, "pyramid": gen_pyramid, "me": gen_me, "me_mctf": lambda: gen_me(only=["me_vga_m4_mctf"]), "sad": gen_sad_kernels, "presets": gen_presets, "stats": gen_block_stats, "dg": gen_dg_detector, "tpl": gen_tpl_chain, "rd": gen_rd_chain}
+def gen_pme_edges():
+    """The reference's svt_pme_sad_loop_kernel_c on tests/pme_cases.py's edge sets in all six cost types: per set the best costs and vectors
+    [6][n] and a CRC of the regenerated inputs (not the planes).  Nothing is written unless the oracle agrees with the reference on every value."""
+    import zlib
+    import pme_cases as pc
+    ref, oracle = pyoracle.load_ref(), pyoracle.load_oracle()
+    out = {}
+    for name, (src, refp, jobs, tables) in pc.edge_sets().items():
+        got = [pc.run_ref(ref, src, refp, jobs, ct, pc.EDGE_EPB, tables) for ct in range(6)]
+        for ct in range(6):
+            orc = pc.run_oracle(oracle, src, refp, jobs, ct, pc.EDGE_EPB, tables)
+            assert np.array_equal(got[ct][0], orc[0]) and np.array_equal(got[ct][1], orc[1]), (name, ct)
+        out[name + "_crc"] = np.uint32(zlib.crc32(b"".join(np.ascontiguousarray(a).tobytes() for a in (src, refp, jobs) + tuple(tables))))
+        out[name + "_cost"], out[name + "_mv"] = np.stack([c for c, _ in got]), np.stack([m for _, m in got])
+    save_npz_fixed(pc.GOLDEN_EDGES, out)
+    print("pme_edges.npz", {k: v.shape for k, v in out.items()}, os.path.getsize(pc.GOLDEN_EDGES), "bytes")
+
+
+GENERATORS = {"pme_edges": gen_pme_edges, "block_stats_edges": gen_block_stats_edges, "md": gen_md_search, "md_edges": gen_md_edges, "pyramid": gen_pyramid, "me": gen_me, "me_mctf": lambda: gen_me(only=["me_vga_m4_mctf"]), "sad": gen_sad_kernels, "presets": gen_presets, "stats": gen_block_stats, "dg": gen_dg_detector, "tpl": gen_tpl_chain, "rd": gen_rd_chain}
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)

@@ -3,7 +3,8 @@
 //
 // One wave per job.  The positions the reference visits (rows `step` apart; along a row groups of 8 consecutive columns, the groups
 // 7 + step apart) are cut into quads; lane <-> quad: v_qsad_pk_u16_u8 evaluates its 4 positions x 4 pixels per instruction over the
-// block (source and reference dwords straight from global memory / L1: the windows of one job are small, many jobs are in flight).
+// block (source and reference dwords straight from global memory / L1: the windows of one job are small, many jobs are in flight).  A quad's
+// last reference dword of a row holds one byte beyond the quad's last sample: the one-byte slack of svt_hip_pme.h.
 // Then each position's cost = SAD + MV rate; the job's first strict minimum in visiting order -- a 64-bit key (cost, visit number) reduced
 // over the wave -- replaces the incoming best when it beats it.
 #include <hip/hip_runtime.h>
@@ -109,7 +110,10 @@ extern "C" void svt_pme_sad_loop_kernel_hip(const SvtHipMvCostParam *mp, uint8_t
     hipSetDevice(ctx->device);
     const int    st = step < 1 ? 1 : step;
     const size_t src_bytes = ((size_t)block_height - 1) * src_stride + block_width;
-    const size_t ref_bytes = ((size_t)((sa_h - 1) / st) * st + block_height - 1) * ref_stride + block_width + sa_w + 4;
+    // the reference's reads end with the last row of the last visited row of positions: the last group's eighth position plus the block
+    // width.  One byte more is room for the kernel's last load of that row (svt_hip_pme.h); the host array is not read for it.
+    const size_t ref_read  = ((size_t)((sa_h - 1) / st) * st + block_height - 1) * ref_stride + (size_t)((sa_w - 8) / (7 + st)) * (7 + st) + 7 + block_width;
+    const size_t ref_bytes = ref_read + 1;
     const int    mv_max = (1 << 14) - 1, r_lo = -(1 << 14), r_hi = 1 << 14; // the table's index range on the device: [r_lo, r_hi]; the host's: [-mv_max, mv_max]
     const bool   entropy = mp->mv_cost_type == SVT_HIP_MV_COST_ENTROPY;
     const size_t tab = entropy ? (size_t)(r_hi - r_lo + 1) * sizeof(int32_t) : 0;
@@ -117,7 +121,7 @@ extern "C" void svt_pme_sad_loop_kernel_hip(const SvtHipMvCostParam *mp, uint8_t
                  a_t0 = a_j + 256, a_t1 = a_t0 + ((tab + 255) & ~(size_t)255), total = a_t1 + ((tab + 255) & ~(size_t)255);
     uint8_t *d_all = leaf_scratch(ctx, total);
     leaf_check(ctx, hipMemcpyAsync(d_all + a_src, src, src_bytes, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
-    leaf_check(ctx, hipMemcpyAsync(d_all + a_ref, ref, ref_bytes - 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync"); // the last 4 bytes are the kernel's dword over-read
+    leaf_check(ctx, hipMemcpyAsync(d_all + a_ref, ref, ref_read, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
     SvtHipPmeJob jb;
     memset(&jb, 0, sizeof(jb));
     jb.width = (uint8_t)block_width; jb.height = (uint8_t)block_height; jb.start_x = start_x; jb.start_y = start_y; jb.sa_w = sa_w; jb.sa_h = sa_h; jb.step = step;

@@ -108,27 +108,52 @@ def check_ssim_jobs(jobs, pyramids=False):
         raise api.SvtHipError(f"svt_hip_ssim_check_jobs: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
 
 
-def run_ssim_hip(ctx, src, ref, jobs, bit_depth, psy_rd=None, pyramids=None):
+def run_ssim_hip(ctx, src, ref, jobs, bit_depth, psy_rd=None, pyramids=None, spare_jobs=0, fill=None, outputs=None, out_base=None, check=True):
     """svt_hip_ssim_batch on host planes: {"ssim": float64[n], "ssim_dist": uint64[n]} with n = len(jobs) + 85 * len(pyramids), the regions'
-    outputs behind the plain jobs' (slots len(jobs) + 85 k ...).  psy_rd None: no psy term."""
+    outputs behind the plain jobs' (slots len(jobs) + 85 k ...).  psy_rd None: no psy term.
+    src / ref: 2-D arrays (the width is the stride) or (array, stride) views; the two strides may differ.  Both device planes are as long
+    as the larger of the two, and every offset a job names must lie inside them: a kernel that takes one stride for the other, or reads
+    for a job it should refuse, then reads wrong samples, never unmapped memory.
+    fill: a byte both output arrays are pre-filled with (default: zeros); the arrays are then n + spare_jobs slots long, and the spare
+    slots and the source, reference, job and region buffers are asserted to read back unchanged.
+    outputs: the names of the output pointers to set (default: both); the array of the other is returned as well, as it was filled.
+    out_base: pyramid_out_base (default len(jobs)); the arrays then cover the slots in between, n = out_base + 85 * len(pyramids).
+    check: False skips svt_hip_ssim_check_jobs, so that the kernel itself meets the jobs the host check refuses."""
     import torch
     from . import api
     L = api.lib()
-    check_ssim_jobs(jobs)
-    if pyramids is not None:
-        check_ssim_jobs(pyramids, pyramids=True)
+    if check:
+        check_ssim_jobs(jobs)
+        if pyramids is not None:
+            check_ssim_jobs(pyramids, pyramids=True)
+    (src, src_stride), (ref, ref_stride) = (a if isinstance(a, tuple) else (a, a.shape[1]) for a in (src, ref))
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
-    n_plain = len(jobs)
-    n = n_plain + (abi.PYRAMID_BLOCKS * len(pyramids) if pyramids is not None else 0)
-    t_src, t_ref, t_jobs = dev(src), dev(ref), dev(jobs if n_plain else np.zeros(1, abi.BLOCK_JOB_DTYPE))
-    outs = {name: torch.zeros(max(n, 1) * np.dtype(dt).itemsize, dtype=torch.uint8, device="cuda") for name, dt in abi.SSIM_OUT_FIELDS}
-    d = abi.SsimBatchDesc(bit_depth=bit_depth, n_jobs=n_plain, src_stride=src.shape[1], ref_stride=ref.shape[1], psy_rd=psy_rd or 0.0)
-    if pyramids is not None and len(pyramids):
-        t_pyr = dev(pyramids)
-        d.n_pyramids, d.pyramid_out_base, d.pyramids = len(pyramids), n_plain, t_pyr.data_ptr()
-    d.src, d.ref, d.jobs = t_src.data_ptr(), t_ref.data_ptr(), t_jobs.data_ptr()
-    d.ssim, d.ssim_dist = outs["ssim"].data_ptr(), outs["ssim_dist"].data_ptr()
+    n_plain, n_pyr = len(jobs), (len(pyramids) if pyramids is not None else 0)
+    out_base = n_plain if out_base is None else out_base
+    assert out_base >= n_plain
+    n = out_base + abi.PYRAMID_BLOCKS * n_pyr if n_pyr else n_plain
+    size = max(src.size, ref.size)
+    for jb in (jobs, pyramids if n_pyr else jobs[:0]):
+        assert (jb["src_offset"] < size).all() and (jb["ref_offset"] < size).all(), "a job names an offset outside the device planes"
+    padded = lambda a: np.concatenate([np.ascontiguousarray(a).reshape(-1), np.zeros(size - a.size, a.dtype)])
+    inputs = [padded(src), padded(ref), jobs if n_plain else np.zeros(1, abi.BLOCK_JOB_DTYPE)] + ([pyramids] if n_pyr else [])
+    t_in = [dev(a) for a in inputs]
+    n_alloc = max(n + (spare_jobs if fill is not None else 0), 1)
+    outs = {name: torch.full((n_alloc * np.dtype(dt).itemsize,), fill or 0, dtype=torch.uint8, device="cuda") for name, dt in abi.SSIM_OUT_FIELDS}
+    d = abi.SsimBatchDesc(bit_depth=bit_depth, n_jobs=n_plain, src_stride=src_stride, ref_stride=ref_stride, psy_rd=psy_rd or 0.0)
+    if n_pyr:
+        d.n_pyramids, d.pyramid_out_base, d.pyramids = n_pyr, out_base, t_in[3].data_ptr()
+    d.src, d.ref, d.jobs = t_in[0].data_ptr(), t_in[1].data_ptr(), t_in[2].data_ptr()
+    for name, _ in abi.SSIM_OUT_FIELDS:
+        if outputs is None or name in outputs:
+            setattr(d, name, outs[name].data_ptr())
     torch.cuda.synchronize()
     ctx.check(L.svt_hip_ssim_batch(ctx._h, C.byref(d)), "svt_hip_ssim_batch")
     ctx.sync()
-    return {name: outs[name].cpu().numpy().view(dt)[:n] for name, dt in abi.SSIM_OUT_FIELDS}
+    res = {name: outs[name].cpu().numpy().view(dt) for name, dt in abi.SSIM_OUT_FIELDS}
+    if fill is not None:
+        for name in res:
+            assert (res[name][n:].view(np.uint8) == fill).all(), f"{name}: a slot past the batch's {n} was written"
+        for a, t in zip(inputs, t_in):
+            assert np.array_equal(t.cpu().numpy(), np.ascontiguousarray(a).view(np.uint8).reshape(-1)), "an input buffer of the batch was written"
+    return {name: res[name][:n] for name in res}

@@ -1,5 +1,6 @@
 """The SSIM distortion of the SSIM tunes, restated in numpy and Python floats (IEEE doubles, one rounding per operation, no contraction), and
-the job generators of its tests.  Reference (Source/Lib):
+the job generators of its tests (the grids of the first fixture, and edge_case: planes of different widths, the smallest sizes that separate the
+kernel's paths, a psy strength that reaches the distortion's high 32 bits).  Reference (Source/Lib):
   svt_ssim_{8x8,4x4}{,_hbd}_c                      Codec/mode_decision.c:4682-4780   the five uint32_t moments of a tile
   similarity                                      Codec/enc_dec_process.c:709-735   the tile score
   ssim, ssim_{8x8,4x4}_blocks{,_hbd}              Codec/mode_decision.c:4781-4878   clamped scores, summed in raster order, / tile count
@@ -11,6 +12,7 @@ import os
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ssim.npz")
+GOLDEN_EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ssim_edges.npz")
 
 CC = {8: (26634, 239708), 10: (428658, 3857925)}  # (64^2 (.01 * max)^2, 64^2 (.03 * max)^2), enc_dec_process.c:700-703
 MASK32 = np.uint64(0xFFFFFFFF)
@@ -58,6 +60,74 @@ def region_jobs(rng, sizes, pairs, per_size=1, stride=REGION * N_REGIONS):
 
 
 ALL_PAIRS = [(0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (2, 3), (3, 0), (2, 2)]
+
+
+# ---- edge cases: source and reference planes of different widths, the block on different rows and columns of the two -----------------------
+EDGE_STRIDES = {8: (151, 237), 10: (149, 203)}  # (source, reference) plane widths in samples
+EDGE_H = 176                                    # both planes' height
+# the smallest sizes that separate the kernel's paths: one 4x4 / 8x8 tile; 4x4 tiling; 4x4 tiling whose psy term reads 8x8 tiles past the block
+# (12x8 -> 16x8); nine 8x8 tiles (more than one pass of 8 groups); seventeen 4x4 tiles (more than one pass of 16); 64x64; and one 128x124
+EDGE_SIZES = [(4, 4), (8, 8), (4, 8), (12, 8), (8, 72), (72, 8), (68, 4), (64, 64)]
+EDGE_KINDS = ("noise", "copy", "inverted", "extremes")
+PSY_LARGE = 73000000.37  # energy * psy_rd in [2^32, 2^53) for a good part of the jobs: the high half of the distortion's 64 bits
+EDGE_PSY_RDS = PSY_RDS + (PSY_LARGE,)
+
+
+def read_extent(w, h):
+    """(columns, rows) svt_spatial_full_distortion_ssim_kernel reads for a w x h block with the psy term on: whole 8x8 tiles when both
+    sides are 8 or more (psy_rd.c:142-151), else the block"""
+    return (-(-w // 8) * 8, -(-h // 8) * 8) if (w >= 8 and h >= 8) else (w, h)
+
+
+def edge_case(bd):
+    """(src, ref, jobs, kinds, regions) for one bit depth, seeded: 2-D planes EDGE_STRIDES[bd] wide, plain jobs of EDGE_SIZES x EDGE_KINDS x 2
+    and one 128x124, three 64x64 pyramid regions (noise, copy, inverted).  Every job's block lies at unrelated places of the two planes;
+    the content is put there: 0 / max samples into both planes for `extremes`, then the source block (or its inversion) into the reference
+    for `copy` / `inverted`, large blocks first (a later paste may cut into an earlier one; the small blocks stay exact).  Every read, with
+    either stride taken for the other, stays inside the larger plane's length."""
+    from svt_av1_psyex_amd import abi
+    rng = np.random.default_rng(5100 + bd)
+    mx, dt = (1 << bd) - 1, (np.uint8 if bd == 8 else np.uint16)
+    sw, rw = EDGE_STRIDES[bd]
+    src = rng.integers(0, mx + 1, (EDGE_H, sw)).astype(dt)
+    ref = rng.integers(0, mx + 1, (EDGE_H, rw)).astype(dt)
+    size = rw * EDGE_H
+
+    def place(w, h):
+        cw, ch = read_extent(w, h)
+        while True:
+            sx, sy, rx, ry = (int(rng.integers(0, lim + 1)) for lim in (sw - cw, EDGE_H - ch, rw - cw, EDGE_H - ch))
+            if (sx, sy) != (rx, ry) and max(sy * sw + sx, ry * rw + rx) + (ch - 1) * rw + cw <= size:
+                return sx, sy, rx, ry
+
+    todo = [(w, h, k) for (w, h) in EDGE_SIZES for k in EDGE_KINDS for _ in range(2)] + [(128, 124, "noise")]
+    placed = [(w, h, k) + place(w, h) for (w, h, k) in todo]
+    regions = [(64, 64, k) + place(64, 64) for k in ("noise", "copy", "inverted")]
+    everything = sorted(placed + regions, key=lambda t: -t[0] * t[1])
+    for (w, h, k, sx, sy, rx, ry) in everything:
+        if k == "extremes":
+            cw, ch = read_extent(w, h)
+            src[sy:sy + ch, sx:sx + cw] = rng.integers(0, 2, (ch, cw)) * mx
+            ref[ry:ry + ch, rx:rx + cw] = rng.integers(0, 2, (ch, cw)) * mx
+    for (w, h, k, sx, sy, rx, ry) in everything:
+        cw, ch = read_extent(w, h)
+        if k == "noise" and (w, h) != (128, 124):  # the source perturbed: scores inside (0, 1)
+            ref[ry:ry + ch, rx:rx + cw] = np.clip(src[sy:sy + ch, sx:sx + cw].astype(np.int32) + rng.integers(-mx // 20, mx // 20 + 1, (ch, cw)), 0, mx)
+        elif k == "copy":
+            ref[ry:ry + ch, rx:rx + cw] = src[sy:sy + ch, sx:sx + cw]
+        elif k == "inverted":
+            ref[ry:ry + ch, rx:rx + cw] = mx - src[sy:sy + ch, sx:sx + cw]
+    as_jobs = lambda rows: np.array([(sy * sw + sx, ry * rw + rx, w, h, 0, 0) for (w, h, k, sx, sy, rx, ry) in rows], dtype=abi.BLOCK_JOB_DTYPE)
+    return src, ref, as_jobs(placed), [k for (_, _, k, *_) in placed], as_jobs(regions)
+
+
+def edge_tiles(jobs):
+    """(kind of tile: 8 or 4, source offset, reference offset) of the first tile of a sample of the edge jobs, for the tile leaves"""
+    out = []
+    for j in jobs[::3]:
+        n = 8 if (j["width"] % 8 == 0 and j["height"] % 8 == 0) else 4
+        out.append((n, int(j["src_offset"]), int(j["ref_offset"])))
+    return out
 
 
 def tile_moments(s, r, n):
@@ -134,3 +204,26 @@ def run_jobs(oracle, src, ref, jobs, bd, psy_rd=0.0):
 def bits(a):
     """float64 values as their uint64 bit patterns (exact comparisons)"""
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+_edge_cache = {}
+
+
+def edge_expected(oracle, bd):
+    """the edge case of one bit depth with its restated results, computed once per process and shared (read-only): dict(src, ref, jobs,
+    kinds, regions, every = the plain jobs followed by the 85 blocks of each region, ssim[len(every)], energy[len(every)],
+    dist = {psy_rd: uint64[len(every)]} for EDGE_PSY_RDS)"""
+    if bd not in _edge_cache:
+        from svt_av1_psyex_amd import stats
+        src, ref, jobs, kinds, regions = edge_case(bd)
+        sp, rp = EDGE_STRIDES[bd]
+        every = np.concatenate([jobs] + [stats.expand_pyramid(r, sp, rp) for r in regions])
+        ssim = run_jobs(oracle, src, ref, every, bd)["ssim"]
+        fs, fr = src.reshape(-1), ref.reshape(-1)
+        energy = [psy_energy(oracle, fs, int(j["src_offset"]), sp, fr, int(j["ref_offset"]), rp, int(j["width"]), int(j["height"]), bd) for j in every]
+        dist = {psy: np.array([ssim_distortion(v, int(j["width"]), int(j["height"]), bd, psy, e) for v, j, e in zip(ssim, every, energy)], np.uint64)
+                for psy in EDGE_PSY_RDS}
+        for a in (src, ref, jobs, regions, every, ssim):
+            a.setflags(write=False)
+        _edge_cache[bd] = dict(src=src, ref=ref, jobs=jobs, kinds=kinds, regions=regions, every=every, ssim=ssim, energy=np.array(energy, np.uint64), dist=dist)
+    return _edge_cache[bd]

@@ -44,6 +44,56 @@ def test_restated_distortion_equals_the_reference(golden, oracle, bd):
     assert (golden[f"dist{bd}"][0] == 0).any()  # src == ref: ssim exactly 1
 
 
+@pytest.fixture(scope="module")
+def golden_edges():
+    return np.load(sc.GOLDEN_EDGES)
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_restatement_equals_the_reference_on_the_edge_cases(golden_edges, oracle, bd):
+    """source and reference planes of different widths, the blocks at unrelated places of the two (golden/ssim_edges.npz)"""
+    import zlib
+    e = sc.edge_expected(oracle, bd)
+    assert zlib.crc32(b"".join(np.ascontiguousarray(e[k]).tobytes() for k in ("src", "ref", "jobs", "regions"))) == int(golden_edges[f"crc{bd}"])
+    assert tuple(golden_edges["psy_rds"]) == sc.EDGE_PSY_RDS
+    for k, psy in enumerate(sc.EDGE_PSY_RDS):
+        bad = np.nonzero(e["dist"][psy] != golden_edges[f"dist{bd}"][k])[0]
+        assert not len(bad), (psy, bad[:5].tolist())
+    src, ref = e["src"], e["ref"]
+    got = []
+    for (n, so, ro) in sc.edge_tiles(e["jobs"]):
+        (sy, sx), (ry, rx) = divmod(so, src.shape[1]), divmod(ro, ref.shape[1])
+        got.append(sc.tile_score(src[sy:sy + n, sx:sx + n], ref[ry:ry + n, rx:rx + n], bd))
+    assert np.array_equal(sc.bits(got), golden_edges[f"tile_bits{bd}"])
+    assert set(golden_edges[f"tile_kind{bd}"].tolist()) == ({0, 1} if bd == 8 else {2, 3})
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_edge_cases_cover_what_they_are_for(golden_edges, oracle, bd):
+    e = sc.edge_expected(oracle, bd)
+    src, ref, jobs = e["src"], e["ref"], e["jobs"]
+    sp, rp = src.shape[1], ref.shape[1]
+    assert sp != rp and src.shape[0] <= 256 and max(sp, rp) <= 256
+    assert {(int(j["width"]), int(j["height"])) for j in jobs} == set(sc.EDGE_SIZES) | {(128, 124)}
+    for kind in sc.EDGE_KINDS:
+        assert {(int(j["width"]), int(j["height"])) for j, k in zip(jobs, e["kinds"]) if k == kind} >= set(sc.EDGE_SIZES)
+    for j in e["every"]:  # different rows and columns of the two planes, and every read inside the common length whichever stride is taken
+        (sy, sx), (ry, rx) = divmod(int(j["src_offset"]), sp), divmod(int(j["ref_offset"]), rp)
+        cw, ch = sc.read_extent(int(j["width"]), int(j["height"]))
+        assert sx + cw <= sp and rx + cw <= rp and max(sy, ry) + ch <= src.shape[0]
+        assert max(int(j["src_offset"]), int(j["ref_offset"])) + (ch - 1) * max(sp, rp) + cw <= max(src.size, ref.size)
+    rows = [(divmod(int(j["src_offset"]), sp), divmod(int(j["ref_offset"]), rp)) for j in jobs]
+    assert sum(a[0] != b[0] and a[1] != b[1] for a, b in rows) >= len(jobs) * 3 // 4
+    n = len(jobs)
+    assert (e["ssim"][:n] == 1.0).sum() >= 4 and (e["ssim"][:n] == 0.0).sum() >= 4  # src == ref scores exactly 1; the inverted content clamps to 0
+    assert (golden_edges[f"dist{bd}"][0] == 0).any()
+    assert (golden_edges[f"tile_bits{bd}"].view(np.float64) < 0).any() and (golden_edges[f"tile_bits{bd}"].view(np.float64) == 1.0).any()
+    # the large strength: energy * psy_rd below 2^53 (exact in a double) everywhere and at or above 2^32 on at least a quarter of the jobs
+    prod = [int(x) * sc.PSY_LARGE for x in e["energy"]]
+    assert max(prod) < 2.0 ** 53 and sum(p >= 2.0 ** 32 for p in prod) * 4 >= len(prod) and sum(p >= 2.0 ** 32 for p in prod[:n]) * 4 >= n
+    assert all(int(x) * max(sc.PSY_RDS) < 2.0 ** 32 for x in e["energy"])  # what the other strengths leave untested
+
+
 def test_descriptor_size_matches_ctypes():
     L = api.lib()
     L.svt_hip_ssim_desc_size.restype = C.c_size_t
