@@ -155,7 +155,8 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         comax = vec_max_abs<W>(x);
     }
     // coefficients below 2^16 in every block of the wave: the quantizer's products fit 24-bit multiplies (see the loop below)
-    const bool q24 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(comax)) < (1u << 16);
+    const uint32_t comax_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(comax));
+    const bool q24 = comax_w < (1u << 16);
     __syncthreads();
     // 64-point sizes keep the top-left 32x32 (svt_handle_transform*_c, transforms.c:2374-2505)
     // partial-frequency shapes (av1_estimate_transform_N2 / _N4 / _ONLY_DC, transforms.c:2633-2948): the pruned 1-D kernels
@@ -195,7 +196,90 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     // Not always wave-uniform: in a partial last wave with coeff or dqcoeff requested, the lanes of the missing blocks (null co_out / dq_out)
     // take this loop while the wave's real blocks take the general one.  Both loops are exact and the missing blocks store nothing.
     const bool fast_q = q24 && !qm && p.d.quant_kind == 0 && !co_out && !dq_out && __all(pf == 0);
-    if (fast_q) {
+    // The same loop with unsigned 32-bit products, signs by multiplication, 32-bit distortion sums and unpredicated qcoeff stores, taken
+    // when EVERY lane of the wave passes the tests below (wave-uniform; a partial last wave has null q_out lanes and keeps the loop below).
+    //   t = |coeff| + round (8 bits: clamped to 32767) <= tmax = comax_w + max(round) (8 bits: min(.., 32767)), round >= 0.
+    //   The reference's tmp = ((32 t * quant) >> 16) + 32 t equals floor(t * Q / 2^11) with Q = quant + 65536 in [2^15, 2^17) for any int16
+    //   quant (the shift is arithmetic, so the identity holds for negative quant as well).  tmax < 2^(18 - KT) <= 2^15 gives t * Q < 2^32:
+    //   one v_mul_u32_u24, and tmp < 2^(24 - KT).
+    //   qv = (tmp * S) >> (21 - LS) is bits 32.. of (tmp << KT) * (S << (11 + LS - KT)); with 0 <= S < 2^15 (int16) and 11 + LS - KT <= 9
+    //   both factors are below 2^24 and the product below 2^48: one v_mul_hi_u32_u24.  KT = 3, or 4 at log-scale 2 (where S << 10 would not fit).
+    //   Signs: sg = +-1, |coeff| = coeff * sg, qcoeff = qv * sg; at log-scale 0 dqcoeff = qcoeff * dequant, else the shift stays on the magnitude.
+    //   Distortions: |coeff - dqcoeff| = |a - dq| <= max(a, dq) <= M = max(comax_w, dqmax), where dqmax is the quantizer applied to tmax with the
+    //   lane's larger quant, quant_shift and dequant (every step is monotonic in each of them, all >= 0).  (NP / LW) * M^2 < 2^32: a lane's
+    //   NP / LW squares sum without overflow in 32 bits, one v_mad_*24 each; M < 2^16 keeps dq * sg and qv * dequant within 24 x 24 -> 32 bits.
+    constexpr int LS = tx_log_scale(TS), KT = LS == 2 ? 4 : 3;
+    bool lane_lean = fast_q && q_out != nullptr && log_scale == LS;
+    {
+        const int32_t  rndm = rnd_c[0] > rnd_c[1] ? rnd_c[0] : rnd_c[1], sm = q.quant_shift[0] > q.quant_shift[1] ? q.quant_shift[0] : q.quant_shift[1];
+        const int32_t  dm = q.dequant[0] > q.dequant[1] ? q.dequant[0] : q.dequant[1], qm2 = (q.quant[0] > q.quant[1] ? q.quant[0] : q.quant[1]) + 65536;
+        const bool     nonneg = (rnd_c[0] | rnd_c[1] | q.quant_shift[0] | q.quant_shift[1] | q.dequant[0] | q.dequant[1]) >= 0;
+        uint32_t       tmax = comax_w + (uint32_t)(nonneg ? rndm : 0);
+        if (BD == 8) tmax = tmax > 32767u ? 32767u : tmax;
+        const u64 qvmax = ((((u64)tmax * (uint32_t)qm2) >> 11) * (u64)(uint32_t)(nonneg ? sm : 0)) >> (21 - LS);
+        const u64 dqmax = (qvmax * (u64)(uint32_t)(nonneg ? dm : 0)) >> LS;
+        const u64 M = dqmax > comax_w ? dqmax : (u64)comax_w;
+        lane_lean = lane_lean && nonneg && tmax < (1u << (18 - KT)) && M < (1u << 16) && M * M * (NP / LW) < (1ull << 32);
+    }
+    const bool lean_q = __all(lane_lean);
+    if (lean_q) {
+        static_assert(NP % LW == 0, "every lane of a block walks the same number of coefficients");
+        constexpr int kScanAhead = NP / LW < SVT_RD_SCAN_AHEAD ? ((NP / LW) & ~1) : SVT_RD_SCAN_AHEAD; // as in the loop below
+        static_assert(kScanAhead >= 2 && kScanAhead % 2 == 0 && NP / LW >= kScanAhead, "ahead of the loop");
+        uint32_t scan2[kScanAhead / 2];
+#pragma unroll
+        for (int k = 0; k < kScanAhead; k += 2) scan2[k / 2] = (uint32_t)(uint16_t)iscan[l + LW * k] | ((uint32_t)(uint16_t)iscan[l + LW * (k + 1)] << 16);
+        uint32_t dres32 = 0, dpred32 = 0;
+        int32_t  last = -1; // largest scan position of a non-zero level
+        // |coeff| itself is never formed: t = coeff * sg + round, the zero-bin test is t >= zbin + round (zbr), SATD is the sum of the t less the
+        // rounds added (below), coeff^2 and (coeff - dqcoeff)^2 take the signed values.  The cul_level sum is clamped once: min(sum of
+        // min(|q|, 63), 63) == min(sum of |q|, 63), and the sum of a wave's |q| < 2^16 fits 32 bits.
+        auto one = [&](int rc, int32_t zbr, int32_t rnd, uint32_t qq, uint32_t qshift, int32_t deq, int ahead = -1) {
+            const int r = rc / WP, c = rc - r * WP; // WP is a power of two
+            const int32_t co = A[r * PA + c], sg = (co >> 31) | 1, tu = __mul24(co, sg) + rnd;
+            satd += (uint32_t)tu;
+            uint32_t t = (uint32_t)tu;
+            if (BD == 8) t = t > 32767u ? 32767u : t;
+            const uint32_t tmp = umul24_lo(t, qq) >> 11;
+            uint32_t qv = umul24_hi(tmp << KT, qshift);
+            qv = tu >= zbr ? qv : 0u;
+            const int32_t qs = __mul24((int32_t)qv, sg);
+            int32_t dqs;
+            if constexpr (LS == 0) dqs = __mul24(qs, deq);
+            else dqs = __mul24(__mul24((int32_t)qv, deq) >> LS, sg);
+            const int32_t dd = co - dqs;
+            int32_t e; // the scan position itself, -1 for a zero level: the + 1 is added once behind the loop
+            if (ahead >= 0) e = qv ? (int32_t)((scan2[ahead >> 1] >> (16 * (ahead & 1))) & 0xFFFFu) : -1; // (compile-time `ahead`)
+            else e = qv ? (int32_t)iscan[rc] : -1;
+            last = e > last ? e : last;
+            qsum += qv;
+            dres32 += (uint32_t)__mul24(dd, dd);
+            dpred32 += (uint32_t)__mul24(co, co);
+            A[r * PB + c] = dqs;
+            q_out[rc] = qs;
+            return qs;
+        };
+        const int ac0 = l != 0;
+        dc_q = one(l, zb_c[ac0] + rnd_c[ac0], rnd_c[ac0], (uint32_t)(q.quant[ac0] + 65536), (uint32_t)q.quant_shift[ac0] << (11 + LS - KT), q.dequant[ac0], 0);
+        const int32_t  zb1 = zb_c[1] + rnd_c[1], rnd1 = rnd_c[1], deq1 = q.dequant[1];
+        const uint32_t qq1 = (uint32_t)(q.quant[1] + 65536), qshift1 = (uint32_t)q.quant_shift[1] << (11 + LS - KT);
+#pragma unroll
+        for (int k = 1; k < kScanAhead; k++) one(l + LW * k, zb1, rnd1, qq1, qshift1, deq1, k);
+        if constexpr (LW >= 32) {
+            static_assert((NP / LW - kScanAhead) % 2 == 0, "pairs");
+            for (int rc = l + kScanAhead * LW; rc < NP; rc += 2 * LW) {
+                one(rc, zb1, rnd1, qq1, qshift1, deq1);
+                one(rc + LW, zb1, rnd1, qq1, qshift1, deq1);
+            }
+        } else {
+#pragma unroll 4
+            for (int rc = l + kScanAhead * LW; rc < NP; rc += LW) one(rc, zb1, rnd1, qq1, qshift1, deq1);
+        }
+        satd -= (uint32_t)(rnd_c[ac0] + (NP / LW - 1) * rnd1);
+        eob   = (uint32_t)(last + 1);
+        dres  = dres32;
+        dpred = dpred32;
+    } else if (fast_q) {
         static_assert(NP % LW == 0, "every lane of a block walks the same number of coefficients");
         // The scan positions of a lane's first kScanAhead coefficients (the low frequencies: where the non-zero levels are) are fetched ahead,
         // unconditionally, two to a register.  A load behind the `qv != 0` branch waits with s_waitcnt vmcnt(0) -- which on this ISA also

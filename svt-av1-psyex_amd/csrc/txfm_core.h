@@ -50,6 +50,20 @@ __device__ __forceinline__ int32_t mul24_shr(int32_t a, int32_t b, int sh) {
     asm("v_mul_hi_i32_i24 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
     return (int32_t)__builtin_amdgcn_alignbit((uint32_t)hi, (uint32_t)__mul24(a, b), (uint32_t)sh);
 }
+// low 32 bits / bits 32..47 of a * b for operands below 2^24: one full-rate instruction each (the compiler picks the quarter-rate v_mul_lo_u32
+// for a masked product it cannot prove to be 24-bit)
+__device__ __forceinline__ uint32_t umul24_lo(uint32_t a, uint32_t b) {
+    uint32_t lo;
+    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(lo) : "v"(a), "v"(b));
+    return lo;
+}
+__device__ __forceinline__ uint32_t umul24_hi(uint32_t a, uint32_t b) {
+    uint32_t hi;
+    asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
+    return hi;
+}
+// c_log_scale as a compile-time constant (av1_get_tx_scale: by the block's pixel count)
+__host__ __device__ constexpr int tx_log_scale(int s) { return tx_wide(s) * tx_high(s) > 1024 ? 2 : tx_wide(s) * tx_high(s) > 256 ? 1 : 0; }
 __device__ __forceinline__ int32_t rshift64(i64 v, int bit) { return (int32_t)((v + ((i64)1 << (bit - 1))) >> bit); }
 // half_btf of the reference (Codec/transforms.h / inv_transforms.h): two 32-bit wrapping products, summed and rounded in
 // 64 bits.  MUL == 1 (inverse transforms): both operands of every product fit 24 signed bits -- cos weights < 2^13, data
