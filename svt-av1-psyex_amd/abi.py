@@ -383,3 +383,25 @@ INTER_PRED_JOB_DTYPE = [("dst_offset", "<u4"), ("org_x", "<i2"), ("org_y", "<i2"
                         ("ref", "u1", (2,)), ("flags", "u1"), ("comp_mode", "u1"), ("mv", "<i2", (2, 2)), ("mv_index", "<u4", (2,)),
                         ("mb_to_left_edge", "<i4"), ("mb_to_right_edge", "<i4"), ("mb_to_top_edge", "<i4"), ("mb_to_bottom_edge", "<i4"),
                         ("fwd_offset", "u1"), ("bck_offset", "u1"), ("reserved", "u1", (6,))]
+
+
+# ---- include/svt_hip_intra.h ----
+INTRA_PRED_NO_FILTER_INTRA = 5
+INTRA_PRED_OK, INTRA_PRED_UNDEFINED = 0, 0xFF
+
+
+class IntraPredJob(C.Structure):  # SvtHipIntraPredJob
+    _fields_ = [("dst_offset", C.c_uint32), ("nbr_x", C.c_int32), ("nbr_y", C.c_int32), ("tx_size", C.c_uint8), ("mode", C.c_uint8), ("angle_delta", C.c_int8),
+                ("filter_intra_mode", C.c_uint8), ("n_top_px", C.c_uint8), ("n_topright_px", C.c_uint8), ("n_left_px", C.c_uint8), ("n_bottomleft_px", C.c_uint8),
+                ("filt_type", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class IntraPredDesc(C.Structure):  # SvtHipIntraPredDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("disable_edge_filter", C.c_uint8), ("reserved", C.c_uint8 * 2), ("n_jobs", C.c_uint32), ("nbr", C.c_void_p),
+                ("nbr_stride", C.c_uint32), ("nbr_width", C.c_uint32), ("nbr_height", C.c_uint32), ("reserved2", C.c_uint32), ("dst", C.c_void_p),
+                ("dst_stride", C.c_uint32), ("reserved3", C.c_uint32), ("dst_samples", C.c_uint64), ("jobs", C.c_void_p), ("status", C.c_void_p)]
+
+
+INTRA_PRED_JOB_DTYPE = [("dst_offset", "<u4"), ("nbr_x", "<i4"), ("nbr_y", "<i4"), ("tx_size", "u1"), ("mode", "u1"), ("angle_delta", "i1"),
+                        ("filter_intra_mode", "u1"), ("n_top_px", "u1"), ("n_topright_px", "u1"), ("n_left_px", "u1"), ("n_bottomleft_px", "u1"),
+                        ("filt_type", "u1"), ("reserved", "u1", (3,))]

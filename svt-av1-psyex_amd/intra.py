@@ -1,0 +1,54 @@
+"""Host-side helpers of the intra prediction entry (svt_hip_intra_pred_batch): a runner on device buffers (it writes the prediction plane
+rd.enqueue_hip reads) and one on host arrays.  torch is plumbing here; the compute is in libsvthip.so."""
+import ctypes as C
+
+import numpy as np
+
+from . import abi, api
+
+
+def check_desc(d):
+    """svt_hip_intra_pred_check_desc: raises api.SvtHipError when the descriptor is refused."""
+    L = api.lib()
+    rc = L.svt_hip_intra_pred_check_desc(C.byref(d))
+    if rc:
+        raise api.SvtHipError(f"svt_hip_intra_pred_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+
+
+def run_intra_pred_device(ctx, bit_depth, disable_edge_filter, nbr, nbr_stride, nbr_width, nbr_height, dst, dst_stride, jobs, n_jobs, status, dst_samples=None):
+    """Enqueues svt_hip_intra_pred_batch on the context stream, without waiting.  nbr / dst / jobs / status are device tensors: nbr the neighbour
+    plane and dst the prediction plane (uint8, or uint16 at 10 bits, as bytes or samples), jobs abi.INTRA_PRED_JOB_DTYPE records, status one byte
+    per job.  dst_samples: the samples dst holds (default: all of the tensor)."""
+    sample_bytes = 2 if bit_depth > 8 else 1
+    if dst_samples is None:
+        dst_samples = dst.numel() * dst.element_size() // sample_bytes
+    d = abi.IntraPredDesc(bit_depth=bit_depth, disable_edge_filter=int(bool(disable_edge_filter)), n_jobs=n_jobs, nbr=nbr.data_ptr(), nbr_stride=nbr_stride,
+                          nbr_width=nbr_width, nbr_height=nbr_height, dst=dst.data_ptr(), dst_stride=dst_stride, dst_samples=dst_samples,
+                          jobs=jobs.data_ptr(), status=status.data_ptr())
+    ctx.check(api.lib().svt_hip_intra_pred_batch(ctx._h, C.byref(d)), "svt_hip_intra_pred_batch")
+    return d
+
+
+def run_intra_pred_hip(ctx, bit_depth, disable_edge_filter, nbr, jobs, dst_shape, dst_stride=None, spare_jobs=0, fill=0, nbr_size=None):
+    """svt_hip_intra_pred_batch on host arrays.  nbr: the neighbour plane [H][stride] uint8 / uint16; nbr_size: (width, height) the kernel may read
+    (default: the whole array); jobs: abi.INTRA_PRED_JOB_DTYPE; dst_shape: (rows, columns) of the destination plane, dst_stride its pitch in
+    samples (default: columns).  Returns {"dst": [rows][dst_stride] as it is after the call (it starts as the byte `fill`), "status":
+    [n + spare_jobs] (the spare slots start as `fill`), "nbr": the neighbour plane read back}."""
+    import torch
+    dt = np.uint16 if bit_depth > 8 else np.uint8
+    n = len(jobs)
+    rows, cols = dst_shape
+    dst_stride = cols if dst_stride is None else dst_stride
+    nbr = np.ascontiguousarray(nbr, dtype=dt)
+    width, height = (nbr.shape[1], nbr.shape[0]) if nbr_size is None else nbr_size
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    t_nbr = dev(nbr)
+    t_dst = torch.full((rows * dst_stride * np.dtype(dt).itemsize,), fill, dtype=torch.uint8, device="cuda")
+    t_status = torch.full((max(1, n + spare_jobs),), fill, dtype=torch.uint8, device="cuda")
+    t_jobs = dev(np.ascontiguousarray(jobs, dtype=abi.INTRA_PRED_JOB_DTYPE) if n else np.zeros(1, abi.INTRA_PRED_JOB_DTYPE))
+    torch.cuda.current_stream().synchronize()  # the fills and copies above ran on torch's stream; the context stream is not waited for
+    run_intra_pred_device(ctx, bit_depth, disable_edge_filter, t_nbr, nbr.shape[1], width, height, t_dst, dst_stride, t_jobs, n, t_status,
+                          dst_samples=rows * dst_stride)
+    ctx.sync()
+    return {"dst": t_dst.cpu().numpy().view(dt).reshape(rows, dst_stride), "status": t_status.cpu().numpy()[:n + spare_jobs],
+            "nbr": t_nbr.cpu().numpy().view(dt).reshape(nbr.shape)}
