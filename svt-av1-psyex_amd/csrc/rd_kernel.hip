@@ -58,6 +58,15 @@ __host__ __device__ constexpr int rd_blocks_per_wave(int ts) { return 64 / rd_la
 #ifndef SVT_RD_WAVES_16
 #define SVT_RD_WAVES_16 4
 #endif
+#ifndef SVT_RD_FOLD_INV_32LANE
+#define SVT_RD_FOLD_INV_32LANE 1 /* the 32-lane layout folds the inverse DCT's round-shift as well (0: it keeps its 64-bit shift loop) */
+#endif
+// The bounded butterflies of a size's passes: 2 = hbtf2 (two v_mad_i32_i24 and a shift, the passes' round-shifts folded in), 3 = the same
+// arithmetic left to the compiler, with the shift loops behind the passes.  The rectangular 32-lane layouts and 64x16 are at their register
+// limit (128 / 256 VGPRs), and with the opaque instructions their allocation spills more than without: they keep the compiler's form.
+__host__ __device__ constexpr int rd_bounded_btf(int ts) {
+    return ((rd_lanes_per_block(ts) == 32 && tx_wide(ts) != tx_high(ts)) || (tx_wide(ts) == 64 && tx_high(ts) == 16)) ? 3 : 2;
+}
 __host__ __device__ constexpr int rd_waves_per_simd(int ts) {
     return rd_lanes_per_block(ts) == 64 ? SVT_RD_WAVES_64 : rd_lanes_per_block(ts) == 32 ? SVT_RD_WAVES_32 : SVT_RD_WAVES_16;
 }
@@ -65,6 +74,8 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     constexpr int W = tx_wide(TS), H = tx_high(TS), WP = W > 32 ? 32 : W, HP = H > 32 ? 32 : H, NP = WP * HP;
     constexpr int LW = rd_lanes_per_block(TS), BPW = rd_blocks_per_wave(TS);
     constexpr bool kShift32 = LW != 32; // bounded passes round-shift in 32 bits (measured: 64x64 -4 %; the 32-lane layout, at its 128-register limit, spills on it: +12 %)
+    constexpr bool kFoldInv = LW != 32 || SVT_RD_FOLD_INV_32LANE; // the inverse DCT's last stage round-shifts (in 32 bits, in every layout)
+    constexpr int kBtf = rd_bounded_btf(TS);
     constexpr int PA = W + 1, PB = WP + 1; // row pitches (dwords) of the full block and of the packed coefficients
     constexpr int ROW_CLAMP = BD == 8 ? 16 : 18, COL_CLAMP = 16; // svt_av1_gen_inv_stage_range, inv_transforms.c:42-80
     constexpr bool RECT = (W == 2 * H || H == 2 * W);
@@ -131,7 +142,13 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
 #pragma unroll
         for (int r = 0; r < H; r++) x[r] = A[(ud ? H - 1 - r : r) * PA + l];
         shift_vec<H>(x, fsh[0]);
-        if (fast_col) { fwd_1d<H, 2>(x, vt, bit_col); shift_vec<H, kShift32>(x, fsh[1]); } else { fwd_1d<H, 0>(x, vt, bit_col); shift_vec<H>(x, fsh[1]); } // wave-uniform
+        // the shifted values are all the passes below may start from: left to itself the compiler forms the identity pass's x << 4 from the unshifted
+        // samples and keeps both sets alive across the type switch, which the 32-lane layouts (at their 128-register limit) pay for in scratch
+        if constexpr (kBtf == 2) {
+#pragma unroll
+            for (int r = 0; r < H; r++) x[r] = held_in_vgpr(x[r]);
+        }
+        if (fast_col) fwd_1d_bounded<H, kShift32, kBtf>(x, vt, bit_col, fsh[1]); else { fwd_1d<H, 0>(x, vt, bit_col); shift_vec<H>(x, fsh[1]); } // wave-uniform
         const int oc = lr ? W - 1 - l : l;
 #pragma unroll
         for (int r = 0; r < H; r++) A[r * PA + oc] = x[r];
@@ -145,7 +162,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         int32_t x[W];
 #pragma unroll
         for (int c = 0; c < W; c++) x[c] = A[l * PA + c];
-        if (fast_row) { fwd_1d<W, 2>(x, ht, bit_row); shift_vec<W, kShift32>(x, fsh[2]); } else { fwd_1d<W, 0>(x, ht, bit_row); shift_vec<W>(x, fsh[2]); }
+        if (fast_row) fwd_1d_bounded<W, kShift32, kBtf>(x, ht, bit_row, fsh[2]); else { fwd_1d<W, 0>(x, ht, bit_row); shift_vec<W>(x, fsh[2]); }
         if constexpr (RECT) {
 #pragma unroll
             for (int c = 0; c < W; c++) x[c] = rshift64((i64)x[c] * 5793, 12);
@@ -428,8 +445,8 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     const bool fast_irow = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(irmax)), W); // wave-uniform
     uint32_t icmax = 0; // largest |row-pass output|: the column pass's input
     if (l < H) {
-        if (fast_irow) inv_1d<W, ROW_CLAMP, 2>(xr, ht); else inv_1d<W, ROW_CLAMP, 1>(xr, ht);
-        shift_vec<W, kShift32>(xr, c_inv_shift0[TS]);
+        if (fast_irow) inv_1d_bounded<W, ROW_CLAMP, kShift32, kFoldInv, kBtf>(xr, ht, c_inv_shift0[TS]);
+        else { inv_1d<W, ROW_CLAMP, 1>(xr, ht); shift_vec<W, kShift32>(xr, c_inv_shift0[TS]); }
 #pragma unroll
         for (int c = 0; c < W; c++) A[l * PA + c] = xr[c];
         icmax = vec_max_abs<W>(xr);
@@ -443,8 +460,8 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         const int ic = lr ? W - 1 - l : l;
 #pragma unroll
         for (int r = 0; r < H; r++) x[r] = (r < HP) ? clampv(A[r * PA + ic], BD + 6 > 16 ? BD + 6 : 16) : 0; // rows >= 32 of a 64-row block are exactly zero after the row pass: constants, so the network prunes itself
-        if (fast_icol) inv_1d<H, COL_CLAMP, 2>(x, vt); else inv_1d<H, COL_CLAMP, 1>(x, vt);
-        shift_vec<H, kShift32>(x, -4);
+        if (fast_icol) inv_1d_bounded<H, COL_CLAMP, kShift32, kFoldInv, kBtf>(x, vt, -4);
+        else { inv_1d<H, COL_CLAMP, 1>(x, vt); shift_vec<H, kShift32>(x, -4); }
         // residual (with the vertical flip undone) back to LDS, row-major: the reconstruction below moves whole runs
 #pragma unroll
         for (int r = 0; r < H; r++) A[r * PA + l] = x[ud ? H - 1 - r : r];
@@ -508,7 +525,8 @@ struct InvParams {
 template <int TS, int BD, typename Pix> __global__ void __launch_bounds__(64, rd_waves_per_simd(TS)) inv_tx_kernel(const InvParams p) {
     constexpr int W = tx_wide(TS), H = tx_high(TS), WP = W > 32 ? 32 : W, HP = H > 32 ? 32 : H, NP = WP * HP;
     constexpr int LW = rd_lanes_per_block(TS), BPW = rd_blocks_per_wave(TS);
-    constexpr bool kShift32 = LW != 32;
+    constexpr bool kShift32 = LW != 32, kFoldInv = LW != 32 || SVT_RD_FOLD_INV_32LANE;
+    constexpr int kBtf = rd_bounded_btf(TS);
     constexpr int PA = W + 1, PB = WP + 1;
     constexpr int ROW_CLAMP = BD == 8 ? 16 : 18, COL_CLAMP = 16;
     constexpr bool RECT = (W == 2 * H || H == 2 * W);
@@ -538,8 +556,8 @@ template <int TS, int BD, typename Pix> __global__ void __launch_bounds__(64, rd
     const bool fast_irow = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(irmax)), W); // wave-uniform
     uint32_t icmax = 0; // largest |row-pass output|: the column pass's input
     if (l < H) {
-        if (fast_irow) inv_1d<W, ROW_CLAMP, 2>(xr, ht); else inv_1d<W, ROW_CLAMP, 1>(xr, ht);
-        shift_vec<W, kShift32>(xr, c_inv_shift0[TS]);
+        if (fast_irow) inv_1d_bounded<W, ROW_CLAMP, kShift32, kFoldInv, kBtf>(xr, ht, c_inv_shift0[TS]);
+        else { inv_1d<W, ROW_CLAMP, 1>(xr, ht); shift_vec<W, kShift32>(xr, c_inv_shift0[TS]); }
 #pragma unroll
         for (int c = 0; c < W; c++) A[l * PA + c] = xr[c];
         icmax = vec_max_abs<W>(xr);
@@ -551,8 +569,8 @@ template <int TS, int BD, typename Pix> __global__ void __launch_bounds__(64, rd
         const int ic = lr ? W - 1 - l : l;
 #pragma unroll
         for (int r = 0; r < H; r++) x[r] = (r < HP) ? clampv(A[r * PA + ic], BD + 6 > 16 ? BD + 6 : 16) : 0;
-        if (fast_icol) inv_1d<H, COL_CLAMP, 2>(x, vt); else inv_1d<H, COL_CLAMP, 1>(x, vt);
-        shift_vec<H, kShift32>(x, -4);
+        if (fast_icol) inv_1d_bounded<H, COL_CLAMP, kShift32, kFoldInv, kBtf>(x, vt, -4);
+        else { inv_1d<H, COL_CLAMP, 1>(x, vt); shift_vec<H, kShift32>(x, -4); }
 #pragma unroll
         for (int r = 0; r < H; r++) A[r * PA + l] = x[ud ? H - 1 - r : r];
     }

@@ -71,13 +71,79 @@ __device__ __forceinline__ int32_t rshift64(i64 v, int bit) { return (int32_t)((
 // returns the same low 32 bits as the quarter-rate v_mul_lo_u32.  Forward transforms keep the 32-bit multiply: their
 // data range depends on the caller's samples.
 // MUL == 2: the caller has bounded the data so that |a| + |b| < 2^18 (weights <= 2^13): neither product wraps and their sum with the rounding
-// term stays below 2^31, so the whole butterfly is three full-rate 32-bit instructions with the reference's exact result.
-template <int MUL> __device__ __forceinline__ int32_t hbtf(int32_t w0, int32_t a, int32_t w1, int32_t b, int bit) {
-    if constexpr (MUL == 2) return (__mul24(w1, b) + (__mul24(w0, a) + (1 << (bit - 1)))) >> bit; // two v_mad_i32_i24 + a shift
+// term stays below 2^31, so the whole butterfly is three full-rate 32-bit instructions with the reference's exact result (hbtf2 below).
+#ifndef SVT_TX_FOLD_FWD
+#define SVT_TX_FOLD_FWD 1 /* bounded forward passes: the round-shift behind the pass lives in the final butterflies (see fwd_1d) */
+#endif
+#ifndef SVT_TX_FOLD_INV
+#define SVT_TX_FOLD_INV 1 /* bounded inverse DCT passes: the round-shift behind the pass lives in the last butterfly stage (see idct_core) */
+#endif
+// What the butterflies of one 1-D pass round with.  MUL 0 / 1 read `bit` alone.  The bounded butterflies (MUL == 2) add `rnd` = 2^(bit - 1), which
+// the whole pass keeps in ONE VGPR (v_mad_i32_i24 takes the wave-uniform weight as its only scalar operand and no literal).  obit / ornd are
+// what the butterflies that produce a forward pass's OUTPUTS use: the same, or with the pass's round-shift folded in (btf_folded).
+struct Btf {
+    int     bit;
+    int32_t rnd;
+    int     obit;
+    int32_t ornd;
+};
+// a value the compiler has to keep in a vector register: it can neither fold it into an operand nor form it again at every use
+__device__ __forceinline__ int32_t held_in_vgpr(int32_t v) {
+    asm("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ Btf btf_plain(int bit) { return Btf{bit, 0, bit, 0}; } // MUL 0 / 1
+__device__ __forceinline__ Btf btf_bounded(int bit) {
+    const int32_t r = held_in_vgpr(1 << (bit - 1));
+    return Btf{bit, r, bit, r};
+}
+// A bounded FORWARD pass followed by svt_av1_round_shift_array_c(.., s), s > 0.  Every output y of a forward DCT or ADST 8 / 16 is the result of
+// a final half_btf, y = (S + 2^(bit-1)) >> bit with S = w0 a + w1 b, and floor of floor is floor:
+//   (y + 2^(s-1)) >> s == (S + 2^(bit-1) + 2^(s-1+bit)) >> (bit + s).
+// No overflow: the two weights are a cosine and a sine scaled by 2^bit <= 2^13, so |S| <= 2^13 sqrt(2) max(|a|, |b|) (+ 2^17 for the weights'
+// own rounding), and under pass_fits_17_bits max(|a|, |b|) < 2^17: |S| < 1.42 * 2^30.  The rounding term is at most 2^12 + 2^16 (bit <= 13,
+// s <= 4): the sum stays below 2^31.
+__device__ __forceinline__ Btf btf_folded(int bit, int s) {
+    const int32_t r = held_in_vgpr(1 << (bit - 1));
+    if (s <= 0) return Btf{bit, r, bit, r};
+    return Btf{bit, r, bit + s, held_in_vgpr((1 << (bit - 1)) + (1 << (s - 1 + bit)))};
+}
+// acc + w * a for 24-bit w and a, low 32 bits: one v_mad_i32_i24 with the weight as its scalar operand (c_cospi at a wave-uniform index).  Written
+// out because the compiler re-associates the C++ form into two multiplies and a v_add3_u32, and, where the two weights are equal, into
+// w * (a + b) with a quarter-rate v_mul_lo_u32 (it no longer knows the sum to be a 24-bit number).
+__device__ __forceinline__ int32_t mad24_sv(int32_t w, int32_t a, int32_t acc) {
+    int32_t r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "s"(w), "v"(a), "v"(acc));
+    return r;
+}
+// the bounded butterfly: exactly two v_mad_i32_i24 and one shift.  An operand that is a literal zero (rows and columns >= 32 of the 64-point
+// inverse passes) is seen on the C++ side, so that such a butterfly is one multiply-add or nothing and the dead half of the network still
+// disappears: the asm statement itself is opaque to the optimizer.
+__device__ __forceinline__ int32_t hbtf2(int32_t w0, int32_t a, int32_t w1, int32_t b, int32_t rnd, int bit) {
+    bool za = false, zb = false; // (not const: a constant's initializer is folded by the front end, where nothing is known to be constant yet)
+    if (__builtin_constant_p(a) && a == 0) za = true;
+    if (__builtin_constant_p(b) && b == 0) zb = true;
+    if (za && zb) return 0; // rnd < 2^bit
+    int32_t acc = rnd;
+    if (!za) acc = mad24_sv(w0, a, acc);
+    if (!zb) acc = mad24_sv(w1, b, acc);
+    return acc >> bit;
+}
+// MUL == 3: the same bound as MUL == 2 with the expression left to the compiler (two multiplies, a three-operand add, a shift; a quarter-rate
+// multiply where the weights are equal).  For the layouts whose register allocation the opaque instructions cost scratch (see rd_tx_kernel).
+template <int MUL> __device__ __forceinline__ int32_t hbtf(int32_t w0, int32_t a, int32_t w1, int32_t b, const Btf &P) {
+    if constexpr (MUL == 2) return hbtf2(w0, a, w1, b, P.rnd, P.bit);
+    const int bit = P.bit;
+    if constexpr (MUL == 3) return (__mul24(w1, b) + (__mul24(w0, a) + (1 << (bit - 1)))) >> bit;
     i64 s;
     if constexpr (MUL == 1) s = (i64)__mul24(w0, a) + (i64)__mul24(w1, b);
     else s = (i64)(int32_t)((uint32_t)w0 * (uint32_t)a) + (i64)(int32_t)((uint32_t)w1 * (uint32_t)b);
     return (int32_t)((s + ((i64)1 << (bit - 1))) >> bit);
+}
+// a butterfly that produces an output of a forward pass
+template <int MUL> __device__ __forceinline__ int32_t hbtf_out(int32_t w0, int32_t a, int32_t w1, int32_t b, const Btf &P) {
+    if constexpr (MUL == 2) return hbtf2(w0, a, w1, b, P.ornd, P.obit);
+    else return hbtf<MUL>(w0, a, w1, b, P);
 }
 // clamp_value of a SUM or DIFFERENCE inside an inverse pass.  The reference widens to 64 bits before it clamps; here the operands are at most
 // 20-bit numbers -- the pass inputs are clamped to bd + 8 / 16 bits on entry, every butterfly output is clamped again, and a half_btf output is
@@ -103,7 +169,7 @@ __device__ __forceinline__ int32_t wsub(int32_t a, int32_t b) { return (int32_t)
 //   final stage: lane M+i with 2M-1-i, angle 64 - (2*brev(i)+1)*(32/M).
 // CLAMP < 0: forward transform (no clamps); otherwise the reference's clamp_value(stage_range) of the inverse.
 // ---------------------------------------------------------------------------------------------------------
-template <int M, int K, int MUL> __device__ __forceinline__ void odd_rot(int32_t *x, const int32_t *c, int bit) {
+template <int M, int K, int MUL> __device__ __forceinline__ void odd_rot(int32_t *x, const int32_t *c, const Btf &bit) {
     constexpr int t = M >> K;
     if constexpr (K == 1) {
 #pragma unroll
@@ -150,17 +216,17 @@ template <int M, int K, int CLAMP> __device__ __forceinline__ void odd_bfly(int3
         }
     }
 }
-template <int M, bool INV, int MUL = INV ? 1 : 0> __device__ __forceinline__ void odd_final(int32_t *x, const int32_t *c, int bit) {
+template <int M, bool INV, int MUL = INV ? 1 : 0> __device__ __forceinline__ void odd_final(int32_t *x, const int32_t *c, const Btf &bit) {
 #pragma unroll
     for (int i = 0; i < M / 2; i++) {
         const int A = 64 - (2 * brevc(i, ilog2c(M)) + 1) * (32 / M), B = 64 - A, p = M + i, m = 2 * M - 1 - i;
         const int32_t a = x[p], b = x[m];
-        if constexpr (!INV) { x[p] = hbtf<MUL>(c[A], a, c[B], b, bit); x[m] = hbtf<MUL>(c[A], b, -c[B], a, bit); }
+        if constexpr (!INV) { x[p] = hbtf_out<MUL>(c[A], a, c[B], b, bit); x[m] = hbtf_out<MUL>(c[A], b, -c[B], a, bit); } // outputs of the forward DCT
         else { x[p] = hbtf<MUL>(c[A], a, -c[B], b, bit); x[m] = hbtf<MUL>(c[B], a, c[A], b, bit); }
     }
 }
 template <int M, int K, int FM> struct OddFwd {
-    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, int bit) {
+    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, const Btf &bit) {
         if constexpr (K < ilog2c(M)) {
             odd_rot<M, K, FM>(x, c, bit);
             odd_bfly<M, K, -1>(x);
@@ -169,7 +235,7 @@ template <int M, int K, int FM> struct OddFwd {
     }
 };
 template <int M, int K, int CLAMP, int IM> struct OddInv {
-    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, int bit) {
+    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, const Btf &bit) {
         if constexpr (K >= 1) {
             odd_bfly<M, K, CLAMP>(x);
             odd_rot<M, K, IM>(x, c, bit);
@@ -179,11 +245,11 @@ template <int M, int K, int CLAMP, int IM> struct OddInv {
 };
 // FM (forward multiply mode): 0 = 32-bit wrapping products (any input), 1 = full-rate 24-bit multiplies -- exact whenever every node of the
 // pass fits 24 signed bits, which the callers establish from the block's largest residual (see fwd_mul24_safe)
-template <int N, int FM> __device__ __forceinline__ void fdct_core(int32_t *x, const int32_t *c, int bit) {
+template <int N, int FM> __device__ __forceinline__ void fdct_core(int32_t *x, const int32_t *c, const Btf &bit) {
     if constexpr (N == 2) {
         const int32_t a = x[0], b = x[1];
-        x[0] = hbtf<FM>(c[32], a, c[32], b, bit);
-        x[1] = hbtf<FM>(-c[32], b, c[32], a, bit);
+        x[0] = hbtf_out<FM>(c[32], a, c[32], b, bit); // outputs of the forward DCT, as are odd_final's at every level of the recursion
+        x[1] = hbtf_out<FM>(-c[32], b, c[32], a, bit);
     } else {
         constexpr int M = N / 2;
 #pragma unroll
@@ -195,7 +261,10 @@ template <int N, int FM> __device__ __forceinline__ void fdct_core(int32_t *x, c
 }
 // IM (inverse multiply mode): 1 = 24-bit products summed in 64 bits (any clamped input), 2 = the three-instruction butterflies, exact while
 // every node of the pass is below 2^18 (weights <= 2^12): the callers measure the pass input
-template <int N, int CLAMP, int IM> __device__ __forceinline__ void idct_core(int32_t *x, const int32_t *c, int bit) {
+// out_s > 0 (the outermost call of a bounded pass): the pass is followed by svt_av1_round_shift_array_c(.., out_s), and the last stage does it.
+// With r = 2^(out_s-1): (clamp(a +- b, lo, hi) + r) >> out_s == clamp(a + r +- b, lo + r, hi + r) >> out_s -- adding r commutes with the clamp --
+// so t = a + r is shared by the pair: seven instructions for two outputs instead of eight.  |a|, |b| < 2^18 behind the stage clamps.
+template <int N, int CLAMP, int IM> __device__ __forceinline__ void idct_core(int32_t *x, const int32_t *c, const Btf &bit, int out_s = 0) {
     if constexpr (N == 2) {
         const int32_t a = x[0], b = x[1];
         x[0] = hbtf<IM>(c[32], a, c[32], b, bit);
@@ -206,7 +275,14 @@ template <int N, int CLAMP, int IM> __device__ __forceinline__ void idct_core(in
         OddInv<M, ilog2c(M) - 1, CLAMP, IM>::run(x, c, bit);
         idct_core<M, CLAMP, IM>(x, c, bit);
 #pragma unroll
-        for (int i = 0; i < M; i++) { const int32_t a = x[i], b = x[N - 1 - i]; x[i] = clamp32(a + b, CLAMP); x[N - 1 - i] = clamp32(a - b, CLAMP); }
+        for (int i = 0; i < M; i++) {
+            const int32_t a = x[i], b = x[N - 1 - i];
+            if (out_s > 0) {
+                const int32_t r = 1 << (out_s - 1), lo = -(1 << (CLAMP - 1)) + r, hi = (1 << (CLAMP - 1)) - 1 + r, t = a + r;
+                x[i]         = max(min(t + b, hi), lo) >> out_s;
+                x[N - 1 - i] = max(min(t - b, hi), lo) >> out_s;
+            } else { x[i] = clamp32(a + b, CLAMP); x[N - 1 - i] = clamp32(a - b, CLAMP); }
+        }
     }
 }
 template <int N> __device__ __forceinline__ void permute_brev(int32_t *x) { // out[k] = in[brev(k)]: an involution, swap pairs
@@ -222,7 +298,7 @@ template <int N> __host__ __device__ constexpr int adst_perm(int k) { // P_N[2j]
     if constexpr (N == 2) return k;
     else return (k & 1) ? N - 1 - adst_perm<N / 2>(k >> 1) : adst_perm<N / 2>(k >> 1);
 }
-template <int N, int HH, int MUL> __device__ __forceinline__ void adst_rot(int32_t *x, const int32_t *c, int bit) {
+template <int N, int HH, int MUL> __device__ __forceinline__ void adst_rot(int32_t *x, const int32_t *c, const Btf &bit) {
 #pragma unroll
     for (int b = 0; b < N; b += 2 * HH) {
         if constexpr (HH == 2) {
@@ -253,39 +329,39 @@ template <int N, int HH, int CLAMP> __device__ __forceinline__ void adst_bfly(in
             else { x[b + j] = clamp32(a + d, CLAMP); x[b + j + HH] = clamp32(a - d, CLAMP); }
         }
 }
-template <int N, int MUL> __device__ __forceinline__ void adst_last(int32_t *x, const int32_t *c, int bit) {
+template <int N, int MUL, bool OUT> __device__ __forceinline__ void adst_last(int32_t *x, const int32_t *c, const Btf &bit) { // OUT: the forward ADST's outputs
 #pragma unroll
     for (int j = 0; j < N / 2; j++) {
         const int A = (4 * j + 1) * (64 / (2 * N)), B = 64 - A;
         const int32_t a = x[2 * j], d = x[2 * j + 1];
-        x[2 * j]     = hbtf<MUL>(c[A], a, c[B], d, bit);
-        x[2 * j + 1] = hbtf<MUL>(c[B], a, -c[A], d, bit);
+        if constexpr (OUT) { x[2 * j] = hbtf_out<MUL>(c[A], a, c[B], d, bit); x[2 * j + 1] = hbtf_out<MUL>(c[B], a, -c[A], d, bit); }
+        else { x[2 * j] = hbtf<MUL>(c[A], a, c[B], d, bit); x[2 * j + 1] = hbtf<MUL>(c[B], a, -c[A], d, bit); }
     }
 }
 template <int N, int HH, int FM> struct AdstFwd {
-    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, int bit) {
+    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, const Btf &bit) {
         if constexpr (HH < N) { adst_rot<N, HH, FM>(x, c, bit); adst_bfly<N, HH, -1>(x); AdstFwd<N, HH * 2, FM>::run(x, c, bit); }
     }
 };
 template <int N, int HH, int CLAMP, int IM> struct AdstInv {
-    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, int bit) {
+    static __device__ __forceinline__ void run(int32_t *x, const int32_t *c, const Btf &bit) {
         if constexpr (HH >= 2) { adst_bfly<N, HH, CLAMP>(x); adst_rot<N, HH, IM>(x, c, bit); AdstInv<N, HH / 2, CLAMP, IM>::run(x, c, bit); }
     }
 };
-template <int N, int FM> __device__ __forceinline__ void fadst(int32_t *x, const int32_t *c, int bit) {
+template <int N, int FM> __device__ __forceinline__ void fadst(int32_t *x, const int32_t *c, const Btf &bit) {
     int32_t y[N];
 #pragma unroll
     for (int k = 0; k < N; k++) { const int32_t v = x[adst_perm<N>(k)]; y[k] = (__builtin_popcount(k) & 1) ? (int32_t)(0u - (uint32_t)v) : v; }
     AdstFwd<N, 2, FM>::run(y, c, bit);
-    adst_last<N, FM>(y, c, bit);
+    adst_last<N, FM, true>(y, c, bit);
 #pragma unroll
     for (int j = 0; j < N / 2; j++) { x[2 * j] = y[2 * j + 1]; x[2 * j + 1] = y[N - 2 - 2 * j]; }
 }
-template <int N, int CLAMP, int IM> __device__ __forceinline__ void iadst(int32_t *x, const int32_t *c, int bit) {
+template <int N, int CLAMP, int IM> __device__ __forceinline__ void iadst(int32_t *x, const int32_t *c, const Btf &bit) {
     int32_t y[N];
 #pragma unroll
     for (int j = 0; j < N / 2; j++) { y[2 * j + 1] = x[2 * j]; y[N - 2 - 2 * j] = x[2 * j + 1]; }
-    adst_last<N, IM>(y, c, bit);
+    adst_last<N, IM, false>(y, c, bit);
     AdstInv<N, N / 2, CLAMP, IM>::run(y, c, bit);
 #pragma unroll
     for (int k = 0; k < N; k++) x[adst_perm<N>(k)] = (__builtin_popcount(k) & 1) ? (int32_t)(0u - (uint32_t)y[k]) : y[k];
@@ -320,10 +396,11 @@ template <int N> __device__ __forceinline__ void identity(int32_t *x) { // trans
 // 1-D dispatch: type 0 DCT, 1/2 ADST (flips are applied by the 2-D passes), 3 identity.  Wave-uniform switch.
 template <int N, int FM> __device__ __forceinline__ void fwd_1d(int32_t *x, int type, int bit) {
     const int32_t *c = c_cospi[bit - 10];
+    const Btf P = FM == 2 ? btf_bounded(bit) : btf_plain(bit);
     if (type == 3) identity<N>(x);
-    else if (type == 0) { fdct_core<N, FM>(x, c, bit); permute_brev<N>(x); }
+    else if (type == 0) { fdct_core<N, FM>(x, c, P); permute_brev<N>(x); }
     else if constexpr (N == 4) adst4(x, bit, false);
-    else if constexpr (N <= 16) fadst<N, FM>(x, c, bit);
+    else if constexpr (N <= 16) fadst<N, FM>(x, c, P);
 }
 // A block's forward transform may use the 24-bit multiplies when |residual| <= 4095: a node of a 1-D pass is a sum of at most N inputs of that
 // pass with weights of magnitude <= 1, so with the up-shift of at most 2 in front of the column pass and the down-shifts between the passes
@@ -333,10 +410,11 @@ template <int N, int FM> __device__ __forceinline__ void fwd_1d(int32_t *x, int 
 __device__ __forceinline__ bool pass_fits_17_bits(uint32_t wave_max_abs_input, int n) { return (unsigned long long)wave_max_abs_input * (unsigned)n < (1u << 17); }
 template <int N, int CLAMP, int IM> __device__ __forceinline__ void inv_1d(int32_t *x, int type) {
     const int32_t *c = c_cospi[2]; // INV_COS_BIT = 12
+    const Btf P = IM == 2 ? btf_bounded(12) : btf_plain(12);
     if (type == 3) identity<N>(x);
-    else if (type == 0) { permute_brev<N>(x); idct_core<N, CLAMP, IM>(x, c, 12); }
+    else if (type == 0) { permute_brev<N>(x); idct_core<N, CLAMP, IM>(x, c, P); }
     else if constexpr (N == 4) adst4(x, 12, true);
-    else if constexpr (N <= 16) iadst<N, CLAMP, IM>(x, c, 12);
+    else if constexpr (N <= 16) iadst<N, CLAMP, IM>(x, c, P);
 }
 // every node of an inverse pass is a sum of at most N pass inputs with weights of magnitude <= 1 (the stage clamps only shrink it): below 2^18
 // when N x the largest |input| is
@@ -369,6 +447,50 @@ template <int N, bool SAFE32 = false> __device__ __forceinline__ void shift_vec(
     } else if (sh > 0) {
 #pragma unroll
         for (int i = 0; i < N; i++) x[i] = (int32_t)((uint32_t)x[i] << sh);
+    }
+}
+
+// the bounded pass (pass_fits_17_bits) together with the shift_vec<N, SAFE32>(x, sh) behind it, sh <= 0: the DCT and the ADST 8 / 16 round-shift
+// in their final butterflies (btf_folded); identity and ADST4 keep the loop
+template <int N, bool SAFE32, int BM = 2> __device__ __forceinline__ void fwd_1d_bounded(int32_t *x, int type, int bit, int sh) {
+    if constexpr (BM != 2) {
+        fwd_1d<N, BM>(x, type, bit);
+        shift_vec<N, SAFE32>(x, sh);
+        return;
+    }
+#if SVT_TX_FOLD_FWD
+    const int32_t *c = c_cospi[bit - 10];
+    const Btf P = btf_folded(bit, -sh);
+    if (type == 3) { identity<N>(x); shift_vec<N, SAFE32>(x, sh); }
+    else if (type == 0) { fdct_core<N, 2>(x, c, P); permute_brev<N>(x); }
+    else if constexpr (N == 4) { adst4(x, bit, false); shift_vec<N, SAFE32>(x, sh); }
+    else if constexpr (N <= 16) fadst<N, 2>(x, c, P);
+#else
+    fwd_1d<N, 2>(x, type, bit);
+    shift_vec<N, SAFE32>(x, sh);
+#endif
+}
+// the bounded inverse pass (ipass_fits_18_bits) together with the shift_vec<N, SAFE32>(x, sh) behind it, sh <= 0.  FOLD: the DCT round-shifts in its
+// last butterfly stage (idct_core), in 32 bits whatever SAFE32 says (the stage's clamp bounds its operand); the inverse ADST ends in negations
+// and keeps the loop, as do identity and ADST4.  With SAFE32 only passes that clamp to more than 16 bits fold (the row pass at 10 bits): a 16-bit
+// clamp of a sum is the saturating v_add_i16 / v_sub_i16 itself, three instructions per output with the 32-bit shift loop against three and a
+// half folded.  Without SAFE32 the loop is the 64-bit one, and every pass folds.
+template <int N, int CLAMP, bool SAFE32, bool FOLD, int BM = 2> __device__ __forceinline__ void inv_1d_bounded(int32_t *x, int type, int sh) {
+    const int32_t *c = c_cospi[2]; // INV_COS_BIT = 12
+    if constexpr (BM != 2) {
+        inv_1d<N, CLAMP, BM>(x, type);
+        shift_vec<N, SAFE32>(x, sh);
+        return;
+    }
+    if (type == 3) { identity<N>(x); shift_vec<N, SAFE32>(x, sh); }
+    else if (type == 0) {
+        permute_brev<N>(x);
+        if constexpr (FOLD && SVT_TX_FOLD_INV && (CLAMP > 16 || !SAFE32)) idct_core<N, CLAMP, 2>(x, c, btf_bounded(12), -sh);
+        else { idct_core<N, CLAMP, 2>(x, c, btf_bounded(12)); shift_vec<N, SAFE32>(x, sh); }
+    } else {
+        if constexpr (N == 4) adst4(x, 12, true);
+        else if constexpr (N <= 16) iadst<N, CLAMP, 2>(x, c, btf_bounded(12));
+        shift_vec<N, SAFE32>(x, sh);
     }
 }
 
