@@ -77,7 +77,8 @@ typedef struct SvtHipTplDesc {
     /* controls (pcs->tpl_ctrls and friends) */
     uint8_t dispenser_search_level; /* 0: 16x16 blocks, 1: 32x32 blocks */
     uint8_t subsample_tx;           /* 0, 1, 2: rows of the transform taken every 1 / 2 / 4 rows */
-    uint8_t pf_shape;               /* EB_TRANS_COEFF_SHAPE 0..3 of the forward transform */
+    uint8_t pf_shape;               /* EB_TRANS_COEFF_SHAPE 0..3 of the forward transform; 3 (ONLY_DC) keeps every coefficient, as
+                                     * svt_av1_wht_fwd_txfm does (it has cases for N2 and N4 alone) */
     uint8_t synth_blk_size;         /* 16 or 32: the TplStats grid */
     uint8_t disable_intra_pred;     /* disable_intra_pred_nref && temporal_layer_index == hierarchical_levels */
     uint8_t is_ref;                 /* tpl_data.is_ref */

@@ -92,7 +92,9 @@ template <int TS> __device__ int64_t tx_chain(int32_t *A, int l, int pf, const S
     }
     wave_sync_workgroup_fences();
     // svt_av1_quantize_fp (quantize_fp_helper_c, 8-bit, log_scale 0, no matrix) + svt_av1_block_error over the kept coefficients
-    const int keep_w = pf == 3 ? 1 : (W >> pf), keep_h = pf == 3 ? 1 : (H >> pf);
+    // svt_av1_wht_fwd_txfm (Codec/transforms.c) switches on N2 and N4 alone: ONLY_DC_SHAPE (3) runs the whole transform
+    if (pf == 3) pf = 0;
+    const int keep_w = W >> pf, keep_h = H >> pf;
     uint32_t eob = 0;
     u64 err = 0;
     for (int rc = l; rc < W * H; rc += 64) {

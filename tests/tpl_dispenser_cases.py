@@ -108,20 +108,35 @@ def dc_pred(plane, x, y, S, width, height, pad=PAD):
     return 128
 
 
-def chain(case, src_tile, pred_tile):
+def chain(case, src_tile, pred_tile, stats=None):
     """subtract -> svt_av1_wht_fwd_txfm (pf_shape, rows every 1 << subsample_tx) -> get_quantize_error -> inverse: (recon_error, eob,
-    the reconstruction of the transformed rows over pred_tile) as pyoracle.rd_batch computes them."""
+    the reconstruction of the transformed rows over pred_tile) as pyoracle.rd_batch computes them.  With stats, the chain's counters
+    (re == 1; t_clamped: a coefficient whose |coeff| + round_fp leaves int16, the clamp of quantize_fp's t; t_clamp_changes_q: the clamp
+    also changes the quantized value) are taken from the oracle's outputs."""
     S, sub, level = src_tile.shape[0], case["sub"], case["level"]
     ts = TPL_TX_SIZE[level][sub]
     fields = dict(bit_depth=8, quant_kind=2, tx_size=ts, src_stride=S << sub, pred_stride=S << sub)
     jobs = np.zeros(1, dtype=abi.JOB_DTYPE)
-    jobs["pf_shape"] = case["pf"]
-    out = pyoracle.rd_batch(fields, np.ascontiguousarray(src_tile), np.ascontiguousarray(pred_tile), jobs, case["quant"][None], want_coeffs=False)
+    jobs["pf_shape"] = 0 if case["pf"] == 3 else case["pf"]  # svt_av1_wht_fwd_txfm (Codec/transforms.c) has no ONLY_DC case: the whole transform
+    out = pyoracle.rd_batch(fields, np.ascontiguousarray(src_tile), np.ascontiguousarray(pred_tile), jobs, case["quant"][None],
+                            want_coeffs=stats is not None)
     shift = 0 if ts == 3 else 2
-    return max(int(out["dist_coeff"][0, 0]) >> shift, 1), int(out["eob"][0, 0]), out["recon"]
+    re = max(int(out["dist_coeff"][0, 0]) >> shift, 1)
+    if stats is not None:
+        co = np.abs(out["coeff"][0].astype(np.int64))
+        rnd = case["quant"]["round_fp"].astype(np.int64).reshape(-1)
+        stats["chains"] += 1
+        stats["re_is_1"] += re == 1
+        qfp = case["quant"]["quant_fp"].astype(np.int64).reshape(-1)
+        t = co + np.where(np.arange(co.size) == 0, rnd[0], rnd[1])
+        stats["t_clamped"] += bool((t > 32767).any())
+        stats["t_clamp_changes_q"] += bool((((np.minimum(t, 32767) * np.where(np.arange(co.size) == 0, qfp[0], qfp[1])) >> 16)
+                                            != ((t * np.where(np.arange(co.size) == 0, qfp[0], qfp[1])) >> 16)).any())
+        stats["max_abs_coeff"] = max(stats["max_abs_coeff"], int(co.max()))
+    return re, int(out["eob"][0, 0]), out["recon"]
 
 
-def result_model_store(case, grid, st, x, y, S):
+def result_model_store(case, grid, st, x, y, S, stats=None):
     st = dict(st)
     for k in ("srcrf_dist", "recrf_dist", "srcrf_rate", "recrf_rate"):
         st[k] = max(1, st[k])
@@ -133,8 +148,13 @@ def result_model_store(case, grid, st, x, y, S):
         for k in ("srcrf_dist", "recrf_dist", "srcrf_rate", "recrf_rate"):
             st[k] = max(1, st[k] // 4)
         cells = [base, base + 1, base + stride, base + stride + 1]
+        if stats is not None:
+            rows = (case["aligned_height"] + G - 1) // G
+            stats["grid_wrap_row"] += x // G + 1 == stride  # base + 1 is the next grid row's first cell
+            stats["grid_below_last_row"] += y // G + 1 == rows  # base + stride lies below the grid
+            stats["grid_cells_past_grid"] = max(stats["grid_cells_past_grid"], base + stride + 1 - (stride * rows - 1))
     for c in cells:
-        if c < len(grid):  # the grid's allocation ends here (the reference would write on)
+        if c < case.get("n_tpl_stats", len(grid)):  # the cells the descriptor names end here (the reference would write on)
             for k, v in st.items():
                 grid[c][k] = v
 
@@ -148,8 +168,26 @@ def generate_padding(buf, width, height, org_x, org_y):
         buf[org_y + height + k, :] = buf[org_y + height - 1, :]
 
 
-def restate(case):
-    """Returns (tpl_stats grid, tpl_src_stats, padded recon) after one dispense of the case (its arrays are not modified)."""
+STAT_KEYS = ("chains", "re_is_1", "t_clamped", "t_clamp_changes_q", "max_abs_coeff", "blocks", "newmv_blocks", "dc_blocks", "src_eob0", "src_eob_pos",
+             "rec_eob0_newmv", "rec_eob_pos_newmv", "rec_eob0_dc", "rec_eob_pos_dc", "eob0_newmv_rows_differ", "max_eob", "cand_ties",
+             "cand_ties_rf", "inter_intra_ties", "clamp_x_lo", "clamp_x_hi", "clamp_y_lo", "clamp_y_hi", "winner_clamped_y",
+             "stored_mv_clamped", "stored_skipped", "recon_clamp_samples", "recon_clamp_blocks", "grid_wrap_row", "grid_below_last_row",
+             "grid_cells_past_grid", "longest_dc_diagonal", "dc_blocks_past_16_on_diagonal")
+
+
+def restate(case, stats=None):
+    """Returns (tpl_stats grid, tpl_src_stats, padded recon) after one dispense of the case (its arrays are not modified).
+
+    stats: an optional dict that is filled with counters of the paths the dispense took (STAT_KEYS), the conditions the edge cases are
+    built for.  cand_ties: blocks whose LAST candidate of minimal cost differs (best_rf_idx or MV) from the first one, the winner
+    (cand_ties_rf: in best_rf_idx); recon_clamp_*: a proxy -- reconstructed samples that are 0 or 255 where the prediction is not (the
+    oracle returns the sample after the clamp only); dc_blocks_past_16_on_diagonal: DC blocks that are the 17th or a later block of
+    their anti-diagonal of the block grid (b64-aligned), longest_dc_diagonal: the most DC blocks on one anti-diagonal.
+
+    Stored stats (src_pass 0) that the reference's source pass never produces follow the project's own definition
+    (include/svt_hip_tpl.h, SvtHipTplDesc.refs): the recon-path block of a stored MV is taken at the position clamped into the search's
+    window [-32, 32 + max - 1 - S]; a stored NEWMV whose best_rf_idx is outside 0..7 or names a reference without planes skips the block
+    as a whole (recon samples and grid cells untouched)."""
     S = 16 << case["level"]
     pad = case.get("pad", PAD)
     sub, step = case["sub"], 1 << case["sub"]
@@ -161,6 +199,10 @@ def restate(case):
     a16w = (case["aligned_width"] + 15) >> 4
     me = case["me"]
     n_pu, max_cand, max_refs, max_l0 = case["n_pu"], case["max_cand"], case["max_refs"], case["max_l0"]
+    if stats is not None:
+        stats.update({k: 0 for k in STAT_KEYS})
+    dc_diag = {}
+    nbx = ((case["aligned_width"] + 63) // 64) * (64 // S)
     for x, y, b64, me_idx in blocks_in_order(case):
         if x + S // 2 > W or y + S // 2 > H:
             continue
@@ -174,6 +216,7 @@ def restate(case):
                 dc = dc_pred(cur, x, y, S, W, H, pad)
                 best_intra = int(np.abs(block(cur, x, y, S, pad).astype(np.int32) - dc).sum())
             n = 0 if case["slice_is_i"] else int(me["total"][b64 * n_pu + mbo])
+            seen = []  # (cost, best_rf_idx, mv, clamped vertically) of every candidate searched
             for ci in range(n):
                 cand = int(me["cand"][(b64 * n_pu + mbo) * max_cand + ci])
                 direction = cand & 3
@@ -186,23 +229,36 @@ def restate(case):
                     continue
                 mv = int(me["mv"][(b64 * n_pu + mbo) * max_refs + (max_l0 if lst else 0) + ref])
                 mx, my = wrap16(wrap16(mv & 0xFFFF) << 3), wrap16(wrap16(mv >> 16) << 3)
+                hit = [0, 0, 0, 0]
                 if x + (mx >> 3) < -TPL_PADX:
-                    mx = wrap16((-TPL_PADX - x) << 3)
+                    mx, hit[0] = wrap16((-TPL_PADX - x) << 3), 1
                 if x + S + (mx >> 3) > TPL_PADX + r["max_width"] - 1:
-                    mx = wrap16(((TPL_PADX + r["max_width"] - 1) - (x + S)) << 3)
+                    mx, hit[1] = wrap16(((TPL_PADX + r["max_width"] - 1) - (x + S)) << 3), 1
                 if y + (my >> 3) < -TPL_PADX:
-                    my = wrap16((-TPL_PADX - y) << 3)
+                    my, hit[2] = wrap16((-TPL_PADX - y) << 3), 1
                 if y + S + (my >> 3) > TPL_PADX + r["max_height"] - 1:
-                    my = wrap16(((TPL_PADX + r["max_height"] - 1) - (y + S)) << 3)
+                    my, hit[3] = wrap16(((TPL_PADX + r["max_height"] - 1) - (y + S)) << 3), 1
                 cost = int(np.abs(block(cur, x, y, S, pad).astype(np.int32) - block(r["src"], x + (mx >> 3), y + (my >> 3), S, pad)).sum())
+                seen.append((cost, lst * 4 + ref, (my, mx), hit[2] or hit[3]))
+                if stats is not None:
+                    for k, h in zip(("clamp_x_lo", "clamp_x_hi", "clamp_y_lo", "clamp_y_hi"), hit):
+                        stats[k] += h
                 if cost < best_inter:
                     best_poc, best_rf, best_inter, best_mv = r["poc"], lst * 4 + ref, cost, (my, mx)
             if best_inter < best_intra:
                 best_mode = NEWMV
+            if stats is not None and seen:
+                low = [e for e in seen if e[0] == best_inter]
+                stats["cand_ties"] += low[-1][1:3] != low[0][1:3]
+                stats["cand_ties_rf"] += low[-1][1] != low[0][1]
+                stats["inter_intra_ties"] += best_inter == best_intra
+                stats["winner_clamped_y"] += best_mode == NEWMV and low[0][3]
             if best_mode == NEWMV:
                 r = case["refs"][(best_rf >> 2, best_rf & 3)]
-                re, _, _ = chain(case, block(cur, x, y, S, pad), block(r["src"], x + (best_mv[1] >> 3), y + (best_mv[0] >> 3), S, pad))
+                re, eob, _ = chain(case, block(cur, x, y, S, pad), block(r["src"], x + (best_mv[1] >> 3), y + (best_mv[0] >> 3), S, pad), stats)
                 st["srcrf_dist"] = (re << 4) << sub
+                if stats is not None:
+                    stats["src_eob0" if eob == 0 else "src_eob_pos"] += 1
             if case["store_src_stats"]:
                 s = srcst[si]
                 s["srcrf_dist"], s["srcrf_rate"], s["mv_row"], s["mv_col"] = st["srcrf_dist"], 0, best_mv[0], best_mv[1]
@@ -211,18 +267,42 @@ def restate(case):
             s = srcst[si]
             st["srcrf_dist"], st["srcrf_rate"] = int(s["srcrf_dist"]), int(s["srcrf_rate"])
             best_mv, best_rf, best_poc, best_mode = (int(s["mv_row"]), int(s["mv_col"])), int(s["best_rf_idx"]), int(s["ref_frame_poc"]), int(s["best_mode"])
+            if best_mode == NEWMV and not (0 <= best_rf <= 7 and (best_rf >> 2, best_rf & 3) in case["refs"]):
+                if stats is not None:
+                    stats["stored_skipped"] += 1
+                continue  # the project's definition: the block is skipped as a whole
         # recon path (:979-1198)
         if best_mode == NEWMV:
             r = case["refs"][(best_rf >> 2, best_rf & 3)]
-            pred = block(r["recon"], x + (best_mv[1] >> 3), y + (best_mv[0] >> 3), S, pad).copy()
+            rx, ry = x + (best_mv[1] >> 3), y + (best_mv[0] >> 3)
+            if not case["src_pass"]:  # the project's definition: a stored MV is kept inside the clamp window of the search
+                cx = min(max(rx, -TPL_PADX), TPL_PADX + r["max_width"] - 1 - S)
+                cy = min(max(ry, -TPL_PADX), TPL_PADX + r["max_height"] - 1 - S)
+                if stats is not None:
+                    stats["stored_mv_clamped"] += (cx, cy) != (rx, ry)
+                rx, ry = cx, cy
+            pred = block(r["recon"], rx, ry, S, pad).copy()
         else:
             pred = np.full((S, S), dc_pred(rec, x, y, S, W, H, pad), np.uint8)
-        re, eob, out = chain(case, block(cur, x, y, S, pad), pred)
+        re, eob, out = chain(case, block(cur, x, y, S, pad), pred, stats)
         dst = block(rec, x, y, S, pad)
         dst[:] = pred
         if (not case["disable_intra_pred"] or case["is_ref"]) and eob:
             for i in range(0, S, step):
                 dst[i:i + step] = out[i]
+        if stats is not None:
+            kind = "newmv" if best_mode == NEWMV else "dc"
+            stats["blocks"] += 1
+            stats[kind + "_blocks"] += 1
+            stats[("rec_eob0_" if eob == 0 else "rec_eob_pos_") + kind] += 1
+            stats["max_eob"] = max(stats["max_eob"], eob)
+            if eob == 0 and best_mode == NEWMV and step > 1:
+                stats["eob0_newmv_rows_differ"] += any((pred[i:i + step] != pred[i]).any() for i in range(0, S, step))
+            hit = int((((dst == 0) | (dst == 255)) & (dst != pred)).sum())
+            stats["recon_clamp_samples"] += hit
+            stats["recon_clamp_blocks"] += hit > 0
+            if best_mode != NEWMV:
+                dc_diag.setdefault(x // S + y // S, []).append(y // S)
         st["recrf_dist"] = (re << 4) << sub
         if best_mode != NEWMV:
             st["srcrf_dist"], st["srcrf_rate"] = st["recrf_dist"], 0
@@ -230,7 +310,14 @@ def restate(case):
         st["recrf_rate"] = max(st["srcrf_rate"], st["recrf_rate"])
         if not case["tpl_slice_is_i"] and best_rf != -1:
             st["mv_row"], st["mv_col"], st["ref_frame_poc"] = best_mv[0], best_mv[1], best_poc
-        result_model_store(case, grid, st, x, y, S)
+        result_model_store(case, grid, st, x, y, S, stats)
+    if stats is not None:
+        for t, bys in dc_diag.items():
+            by0 = max(t - (nbx - 1), 0)  # the diagonal's first block row on the b64-aligned block grid
+            stats["longest_dc_diagonal"] = max(stats["longest_dc_diagonal"], len(bys))
+            stats["dc_blocks_past_16_on_diagonal"] += sum(by - by0 >= 16 for by in bys)
+        for k in stats:
+            stats[k] = int(stats[k])
     generate_padding(rec, case["recon_width"], case["recon_height"], pad, pad)
     return grid, srcst, rec
 
@@ -253,9 +340,10 @@ def padded(rng, W, H, base=None, amp=None):
 
 def make_case(seed, W, H, level=0, sub=0, pf=2, synth=16, disable_intra_pred=0, is_ref=1, slice_is_i=0, src_pass=1, store_src_stats=1,
               unusable=(), enable_me_16x16=1, n_refs=(2, 1), amp=6, qstep=(40, 52), max_shrink=(0, 0), enable_me_8x8=0, max_cand=23, max_refs=7,
-              max_l0=4):
+              max_l0=4, spare_cells=8):
     """max_cand / max_refs / max_l0 and enable_me_8x8 (n_pu 85) set the strides of the ME arrays; the defaults are wider than any
-    picture's, api.picture_desc gives 3 / 2 / 1 for one reference per list and 9 / 4 / 2 for two."""
+    picture's, api.picture_desc gives 3 / 2 / 1 for one reference per list and 9 / 4 / 2 for two.  spare_cells: cells of the tpl_stats
+    buffer past the grid (32x32 blocks on the 16 grid write up to stride + 1 cells past it)."""
     assert n_refs[0] <= max_l0 and max_l0 + n_refs[1] <= max_refs
     rng = np.random.default_rng(seed)
     aw, ah = (W + 7) & ~7, (H + 7) & ~7
@@ -287,7 +375,7 @@ def make_case(seed, W, H, level=0, sub=0, pf=2, synth=16, disable_intra_pred=0, 
     far = rng.random(mvx.shape) < 0.1  # some MVs far outside the picture: the clamp
     mvx = np.where(far, rng.integers(-400, 400, mvx.shape), mvx)
     mv = ((mvx & 0xFFFF) | ((mvy & 0xFFFF) << 16)).astype(np.uint32)
-    synth_cells = ((aw + synth - 1) // synth) * ((ah + synth - 1) // synth) + 8  # a few cells past the grid: writes there are dropped
+    synth_cells = ((aw + synth - 1) // synth) * ((ah + synth - 1) // synth) + spare_cells  # cells past the grid
     tpl_stats = np.zeros(synth_cells, abi.TPL_STATS_DTYPE)
     tpl_stats.view(np.uint8)[:] = 0xA5  # untouched cells keep this
     a16 = ((aw + 15) // 16) * ((ah + 15) // 16)
@@ -373,6 +461,10 @@ def input_checksum(c):
     return np.frombuffer(h.digest(), np.uint8).copy()
 
 
+def plane_checksum(plane):
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(plane).tobytes()).digest(), np.uint8).copy()
+
+
 def fixture_cases(recon_of):
     """(name, kwargs, case) of the fixture in order.  The stored-stats case reuses the TplSrcStats of the first case's picture; the
     sliding-window pair's second picture takes the first one's TPL recon (recon_of(case): the fixture's, or the reference's while the
@@ -390,3 +482,203 @@ def fixture_cases(recon_of):
     b = make_case(221, 136, 104, n_refs=(1, 0))
     b["refs"][(0, 0)]["recon"] = recon_of(a)
     yield "window_picture_2", dict(seed=221), b
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Edge cases: pictures built so that the dispense takes the paths the seeded cases above never take.  Each goes through make_case
+# (whose draws stay as they are) and then changes the arrays it needs; test_tpl_dispenser_edges.py asserts, from restate()'s counters,
+# that every case still reaches what it was built for.  Groups A-F and H are in the reference fixture tests/golden/tpl_dispenser_edges.npz
+# (tools/gen_tpl_golden.py); group G (stored stats the reference never produces) is the project's own definition, see restate().
+GOLDEN_EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tpl_dispenser_edges.npz")
+EDGE_FIXTURE_GROUPS = "ABCDEFH"
+EDGE_PLANES_STORED = "ACDEF"  # groups whose recon planes the fixture stores whole; the others store the plane's sha256
+LEVEL_SUB = [(0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (1, 2)]
+
+
+def unpack_mv(case):
+    mv = case["me"]["mv"]
+    x = (mv & 0xFFFF).astype(np.int64)
+    y = (mv >> 16).astype(np.int64)
+    return np.where(x >= 0x8000, x - 0x10000, x), np.where(y >= 0x8000, y - 0x10000, y)
+
+
+def pack_mv(case, mvx, mvy):
+    case["me"]["mv"] = ((mvx & 0xFFFF) | ((mvy & 0xFFFF) << 16)).astype(np.uint32)
+
+
+def set_inner(plane, inner):
+    """Replaces the picture inside a padded plane and pads it again."""
+    H, W = inner.shape
+    plane[PAD:PAD + H, PAD:PAD + W] = inner
+    generate_padding(plane, W, H, PAD, PAD)
+
+
+def far_mvs(c, seed, share, reach, axes="xy"):
+    """Replaces a share of the ME vectors by far ones (within +-reach full-pel samples), independently per axis."""
+    rng = np.random.default_rng(seed)
+    mvx, mvy = unpack_mv(c)
+    if "x" in axes:
+        mvx = np.where(rng.random(mvx.shape) < share, rng.integers(-reach, reach + 1, mvx.shape), mvx)
+    if "y" in axes:
+        mvy = np.where(rng.random(mvy.shape) < share, rng.integers(-reach, reach + 1, mvy.shape), mvy)
+    pack_mv(c, mvx, mvy)
+
+
+def tie_case(seed, pair, **kw):
+    """Group C: columns 0..95 of the current picture and of every reference's source are flat (DC and every vector cost 0 there); the
+    second reference of `pair` has the first one's source plane and, for every PU, its vector: equal costs wherever both are listed."""
+    c = make_case(seed, **kw)
+    c["cur"][:, :PAD + 96] = 100
+    for r in c["refs"].values():
+        r["src"][:, :PAD + 96] = 100
+    (l0, r0), (l1, r1) = pair
+    c["refs"][(l1, r1)]["src"] = c["refs"][(l0, r0)]["src"].copy()
+    mvx, mvy = unpack_mv(c)
+    slot = lambda l, r: (c["max_l0"] if l else 0) + r
+    mvx = mvx.reshape(-1, c["max_refs"])
+    mvy = mvy.reshape(-1, c["max_refs"])
+    mvx[:, slot(l1, r1)] = mvx[:, slot(l0, r0)]
+    mvy[:, slot(l1, r1)] = mvy[:, slot(l0, r0)]
+    pack_mv(c, mvx.reshape(-1), mvy.reshape(-1))
+    far_mvs(c, seed + 1000, 0.1, 300, "y")
+    # the far vectors go to the pair alike
+    mvx, mvy = (a.reshape(-1, c["max_refs"]) for a in unpack_mv(c))
+    mvy[:, slot(l1, r1)] = mvy[:, slot(l0, r0)]
+    pack_mv(c, mvx.reshape(-1), mvy.reshape(-1))
+    return c
+
+
+def coarse_case(seed, **kw):
+    """Group A: the recon-path planes are the source-path ones (a reference outside the sliding window, SvtHipTplRef.recon), so that the
+    residuals that quantize to nothing on the source path do so on the recon path as well."""
+    c = make_case(seed, **kw)
+    for r in c["refs"].values():
+        r["recon"] = r["src"].copy()
+    return c
+
+
+def range_case(seed, pattern, **kw):
+    """Group E: the current picture at one end of the sample range against references at the other: 255 / 0 in halves of the picture
+    (left | right) or a 255 / 0 checkerboard of single samples against its inverse."""
+    c = make_case(seed, **kw)
+    W, H = c["width"], c["height"]
+    if pattern == "halves":
+        inner = np.zeros((H, W), np.uint8)
+        inner[:, :W // 2] = 255
+    else:
+        inner = (((np.arange(H)[:, None] + np.arange(W)[None, :]) & 1) * 255).astype(np.uint8)
+    set_inner(c["cur"], inner)
+    for r in c["refs"].values():
+        set_inner(r["src"], 255 - inner)
+        set_inner(r["recon"], 255 - inner)
+    return c
+
+
+def stored_stats_case(seed, edit, **kw):
+    """Group G: the stored stats of a first pass of the same picture, then edited by edit(case, stats array, rng)."""
+    c = src_pass0_case(seed, **kw)
+    c["tpl_src_stats"] = c["tpl_src_stats"].copy()
+    edit(c, c["tpl_src_stats"], np.random.default_rng(seed + 2000))
+    return c
+
+
+def _edit_far(c, s, rng):
+    """Every stored NEWMV vector far outside the window, the four sides in turn (1/8 sample units; up to 500 samples away)."""
+    idx = np.flatnonzero(s["best_mode"] == NEWMV)
+    far = rng.integers(250, 500, len(idx)) * 8
+    side = np.arange(len(idx)) % 4
+    s["mv_col"][idx] = np.where(side == 0, -far, np.where(side == 1, far, s["mv_col"][idx]))
+    s["mv_row"][idx] = np.where(side == 2, -far, np.where(side == 3, far, s["mv_row"][idx]))
+
+
+def _edit_no_planes(c, s, rng):
+    idx = np.flatnonzero(s["best_mode"] == NEWMV)[::3]
+    s["best_rf_idx"][idx] = np.where(np.arange(len(idx)) % 2 == 0, 3, 6)  # (0, 3) and (1, 2): no such reference in the case
+
+
+def _edit_bad_rf(c, s, rng):
+    idx = np.flatnonzero(s["best_mode"] == NEWMV)[::3]
+    s["best_rf_idx"][idx] = np.where(np.arange(len(idx)) % 2 == 0, 9, -1)
+
+
+def _edge_list():
+    """(name, group, builder) of every edge case; the builder is called when the case is needed."""
+    L = []
+    add = lambda name, fn: L.append((name, name[0], fn))
+    mk = lambda *a, **k: (lambda: make_case(*a, **k))
+    # A: quantizers coarse enough for eob == 0 on both paths, and a fine one (every coefficient kept)
+    coarse0 = dict(W=200, H=136, level=0, sub=0, pf=1, qstep=(1336, 1828), amp=1)
+    coarse1 = dict(W=264, H=200, level=1, sub=2, pf=1, synth=16, qstep=(1336, 1828), amp=1)
+    add("A_coarse_L0", lambda: coarse_case(300, **coarse0))
+    add("A_coarse_L1_sub2", lambda: coarse_case(301, **dict(coarse1, qstep=(900, 1200))))  # NEWMV blocks with eob 0 and with eob > 0
+    add("A_coarse_L0_no_inverse", lambda: coarse_case(302, disable_intra_pred=1, is_ref=0, **coarse0))
+    add("A_coarse_L1_sub2_no_inverse", lambda: coarse_case(303, disable_intra_pred=1, is_ref=0, **coarse1))
+    add("A_fine_pf0", mk(304, W=136, H=104, pf=0, qstep=(4, 4)))
+    # B: every transform size and shape (pf 3: svt_av1_wht_fwd_txfm has no ONLY_DC case, the whole transform runs)
+    for level, sub in LEVEL_SUB:
+        for pf in (0, 1, 2):
+            add(f"B_L{level}_sub{sub}_pf{pf}", mk(320 + level * 9 + sub * 3 + pf, W=128, H=96 + 32 * level, level=level, sub=sub, pf=pf, synth=16 << (pf & 1)))
+    add("B_L0_sub0_pf3", mk(340, W=128, H=96, level=0, sub=0, pf=3))
+    add("B_L1_sub2_pf3", mk(341, W=128, H=128, level=1, sub=2, pf=3, synth=16))
+    # C: ties between candidates and between inter and intra
+    add("C_ties_L0", lambda: tie_case(350, ((0, 0), (0, 1)), W=200, H=136))
+    add("C_ties_L1", lambda: tie_case(351, ((0, 0), (0, 1)), W=264, H=200, level=1, sub=2, synth=16))
+    add("C_ties_L0_list0_list1", lambda: tie_case(352, ((0, 0), (1, 0)), W=200, H=136))
+    # D: far vectors on both axes
+    def far(seed, **kw):
+        c = make_case(seed, W=200, H=136, **kw)
+        far_mvs(c, seed + 1000, 0.3, 400)
+        return c
+    add("D_far_mvs", lambda: far(360, disable_intra_pred=1))
+    add("D_far_mvs_intra_on", lambda: far(362))
+    add("D_far_mvs_max_size_below_picture", lambda: far(361, max_shrink=(40, 24), disable_intra_pred=1))
+    # E: range limits
+    e = lambda seed, pattern, level, sub, q, dis: (lambda: range_case(seed, pattern, W=128, H=96 + 32 * level, level=level, sub=sub, synth=16,
+                                                                      qstep=q, disable_intra_pred=dis, pf=0 if pattern == "checker" else 2))
+    add("E_halves_L0_coarse_inter", e(370, "halves", 0, 0, (1336, 1828), 1))
+    add("E_halves_L0_coarse_intra", e(371, "halves", 0, 0, (1336, 1828), 0))
+    add("E_halves_L0_fine_inter", e(372, "halves", 0, 0, (4, 4), 1))
+    add("E_checker_L0_coarse_inter", e(373, "checker", 0, 0, (1336, 1828), 1))
+    add("E_checker_L0_fine_intra", e(374, "checker", 0, 0, (4, 4), 0))
+    add("E_halves_L1_sub0_coarse_inter", e(375, "halves", 1, 0, (1336, 1828), 1))
+    add("E_halves_L1_sub2_coarse_inter", e(376, "halves", 1, 2, (1336, 1828), 1))
+    add("E_halves_L1_sub2_fine_intra", e(377, "halves", 1, 2, (4, 4), 0))
+    add("E_halves_L0_sub1_coarse_inter", e(378, "halves", 0, 1, (1336, 1828), 1))
+    # with step 1336 the clamp of t fires but the quantized value stays (32767 * 49 >> 16 == 33305 * 49 >> 16); with step 300 it changes
+    add("E_halves_L0_step300_inter", e(379, "halves", 0, 0, (300, 400), 1))
+    add("E_halves_L1_sub0_step300_inter", e(365, "halves", 1, 0, (300, 400), 1))
+    add("E_halves_L1_sub2_step300_inter", e(366, "halves", 1, 2, (300, 400), 1))
+    # F: 32x32 blocks on the 16 grid whose 2x2 writes run past a grid row's end / below the grid's last row
+    add("F_grid_row_wrap", mk(380, W=240, H=128, level=1, sub=2, synth=16, spare_cells=17))
+    add("F_grid_below_last_row", mk(381, W=208, H=144, level=1, sub=2, synth=16, spare_cells=15))
+    # H: anti-diagonals of DC blocks longer than the intra kernel's 16 waves
+    add("H_islice_L0", mk(390, W=336, H=336, slice_is_i=1))
+    add("H_islice_L1", mk(391, W=576, H=576, level=1, sub=2, synth=16, slice_is_i=1))
+    add("H_inter_L0", mk(392, W=336, H=336, amp=40))
+    # G: stored stats the reference never produces (not in the fixture)
+    add("G_far_stored_mvs_L0", lambda: stored_stats_case(400, _edit_far, W=200, H=136))
+    add("G_far_stored_mvs_L1", lambda: stored_stats_case(401, _edit_far, W=232, H=178, level=1, sub=2, synth=16, max_shrink=(24, 16)))
+    add("G_newmv_without_planes", lambda: stored_stats_case(402, _edit_no_planes, W=200, H=136))
+    add("G_rf_idx_out_of_range", lambda: stored_stats_case(403, _edit_bad_rf, W=200, H=136))
+    return L
+
+
+def edge_case_names(groups="ABCDEFGH"):
+    return [name for name, g, _ in _edge_list() if g in groups]
+
+
+def edge_case(name):
+    return next(fn for n, _, fn in _edge_list() if n == name)()
+
+
+def edge_cases(groups="ABCDEFGH"):
+    """(name, case) of the edge cases of the given groups."""
+    return [(name, fn()) for name, g, fn in _edge_list() if g in groups]
+
+
+def exact_cells(case):
+    """The case with n_tpl_stats equal to the grid's cells exactly (the buffer stays longer): writes past the grid are dropped."""
+    G = case["synth"]
+    c = dict(case)
+    c["n_tpl_stats"] = ((case["aligned_width"] + G - 1) // G) * ((case["aligned_height"] + G - 1) // G)
+    return c

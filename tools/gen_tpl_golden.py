@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Writes tests/golden/tpl_dispenser.npz: the reference encoder's own TPL dispenser on the seeded cases of tests/tpl_dispenser_cases.py.
+"""Writes tests/golden/tpl_dispenser.npz and tests/golden/tpl_dispenser_edges.npz: the reference encoder's own TPL dispenser on the seeded
+cases (FIXTURE_CASES) and on the edge cases (edge_cases, groups A-F and H) of tests/tpl_dispenser_cases.py.
 
 Run by hand on a machine that has the reference's sources (--ref: the root of its source tree); never by the tests, build(), smoke() or
 bench.py.  It compiles, where they lie, the reference's Codec/src_ops_process.c -- #included by a small harness of its own, because
@@ -12,7 +13,8 @@ it reaches, calls the dispenser for every b64 in raster order and then svt_aom_g
 The fixture holds numbers only: per case its generator arguments (the inputs are the deterministic planes, candidate lists and MVs of
 tpl_dispenser_cases.make_case, pinned by a checksum of every input array) and the outputs -- the TplStats grid, the TplSrcStats and the whole
 padded recon plane.  The sliding-window case dispenses two pictures: the second's list-0 recon-path reference is the first's TPL recon.
---check recomputes everything and compares it with the committed file instead of writing it."""
+The edge-case file has the same layout, except that the recon plane of the groups with many or large pictures is stored as its sha256.
+--check recomputes everything and compares it with the two committed files instead of writing them."""
 import argparse
 import ctypes as C
 import os
@@ -294,20 +296,42 @@ def generate(L):
     return out
 
 
+def generate_edges(L):
+    """The edge cases (groups A-F and H of tpl_dispenser_cases.edge_cases; G is the project's own definition) in the same layout.  The
+    recon plane is stored whole for the groups in tc.EDGE_PLANES_STORED; the others (many pictures, or large ones) store its sha256 as
+    recon_sha_<i> instead, next to the full grids, to keep the file small."""
+    out = {}
+    for i, (name, c) in enumerate(tc.edge_cases(tc.EDGE_FIXTURE_GROUPS)):
+        g, s, r = run_ref(L, c)
+        out[f"name_{i}"] = np.array(name)
+        out[f"checksum_{i}"] = tc.input_checksum(c)
+        out[f"tpl_stats_{i}"], out[f"tpl_src_stats_{i}"] = g, s
+        if name[0] in tc.EDGE_PLANES_STORED:
+            out[f"recon_{i}"] = r
+        else:
+            out[f"recon_sha_{i}"] = tc.plane_checksum(r)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--ref", required=True, help="root of the reference encoder's source tree")
-    ap.add_argument("--check", action="store_true", help="compare with the committed fixture instead of writing it")
+    ap.add_argument("--check", action="store_true", help="compare with the committed fixtures instead of writing them")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
-        out = generate(build(a.ref, tmp))
+        L = build(a.ref, tmp)
+        outs = [(tc.GOLDEN, generate(L)), (tc.GOLDEN_EDGES, generate_edges(L))]
     if a.check:
-        z = np.load(tc.GOLDEN)
-        bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-        print("identical" if not bad else f"differs: {bad}")
-        sys.exit(1 if bad else 0)
-    np.savez_compressed(tc.GOLDEN, **out)
-    print(f"wrote {tc.GOLDEN}: {len(out) // 5} cases, {os.path.getsize(tc.GOLDEN)} bytes")
+        worst = 0
+        for path, out in outs:
+            z = np.load(path)
+            bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
+            print(f"{os.path.basename(path)}: " + ("identical" if not bad else f"differs: {bad}"))
+            worst |= bool(bad)
+        sys.exit(worst)
+    for path, out in outs:
+        np.savez_compressed(path, **out)
+        print(f"wrote {path}: {len([k for k in out if k.startswith('name_')])} cases, {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":
