@@ -4,108 +4,52 @@
 // Reference functions restated (Source/Lib):
 //   svt_av1_cost_coeffs_txb, allow_update_cdf == 0              Codec/rd_cost.c:434-559
 //   svt_av1_txb_init_levels_c                                   Codec/rd_cost.c:99-111
-//   svt_av1_get_nz_map_contexts_c, get_nz_map_ctx               C_DEFAULT/encode_txb_ref_c.c:17-40
-//   get_nz_mag, get_nz_map_ctx_from_stats                       Codec/coefficients.h:2884-2943
-//   get_br_ctx                                                  Codec/common_utils.h:114-151
-//   get_eob_cost, get_eob_pos_token                             Codec/rd_cost.c:281-298,188-201
 //   av1_transform_type_rate_estimation, get_ext_tx_set{,_type}  Codec/rd_cost.c:113-158, Codec/definitions.h:1787-1828
 //   av1_cost_coeffs_txb_loop_cost_{one_,}eob                    Codec/rd_cost.c:310-431
 //   svt_aom_txb_estimate_coeff_bits, av1_cost_skip_txb          Codec/rd_cost.c:1405-1450,299-308
 //   the short-cuts and the winner of tx_type_search             Codec/product_coding_loop.c:4947-4952,4976-4985
 //   RDCOST                                                      Codec/rd_cost.h:37
 //
-// A batch shares tx_size and plane_type, hence ONE LvMapCoeffCost and one LvMapEobCost: a workgroup of four waves copies both into LDS
-// once and then walks its share of the jobs.  A group of G = min(64, coefficients) lanes takes one job, so a wave holds four 4x4 jobs,
-// two 4x8 / 8x4 jobs, one job of any other size.  Every lane takes raster positions (four in a row from 256
-// coefficients up), writes their clamped levels into the group's padded levels array in LDS (one byte per level, stride width + 4, four
-// zero rows below: the lay-out of svt_av1_txb_init_levels_c without the two rows above, which nothing reads), and then adds the cost terms
-// of its own positions: a position's place in the scan comes from the inverse scan table, its contexts from the levels array alone.
-// There is no serial dependency, and the 32-bit sums of the lanes meet by cross-lane adds in any order.
+// The lay-out (the cost tables and a group's padded levels array in LDS, G lanes per job), the context rules and the cost terms of the level
+// map: lvmap_core.h.  Every lane takes raster positions (four in a row from 256 coefficients up), writes their clamped levels into the group's
+// levels array, and then adds the cost terms of its own positions: a position's place in the scan comes from the inverse scan table, its
+// contexts from the levels array alone.  There is no serial dependency, and the 32-bit sums of the lanes meet by cross-lane adds in any order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include "svt_hip_internal.h"
 #include "../../include/svt_hip_dsp.h"
+#include "lvmap_core.h"
 #include "wave_ops.h"
 
 namespace {
 
-constexpr int kWaves      = 4;                   // waves of a workgroup
-constexpr int kCoeffInts  = sizeof(SvtHipLvMapCoeffCost) / 4;
-constexpr int kEobInts    = sizeof(SvtHipLvMapEobCost) / 4;
-constexpr int kLevelBytes = (32 + 4) * (32 + 4); // TX_PAD_HOR = 4 columns, TX_PAD_BOTTOM = 4 rows
-constexpr int kMaxGrid    = 2048;
-constexpr uint32_t kCostLiteral = 512;           // av1_cost_literal(1)
-
 struct RateParams {
     SvtHipCoeffRateDesc d;
     const int16_t *iscan[3];  // default, row (V_*), column (H_*) inverse scans of this tx_size
-    int      bwl, w, h;       // get_txb_bwl_tab / get_txb_wide_tab / get_txb_high_tab: the packed block
-    int      txs_ctx;         // (txsize_sqr_map + txsize_sqr_up_map + 1) >> 1
-    int      eob_multi;       // txsize_log2_minus4
-    int      shape;           // 0 square, 1 tx width < tx height, 2 tx width > tx height (the real dimensions)
+    LvMapGeom g;
     int      ext_set[2];      // get_ext_tx_set(tx_size, is_inter, reduced) by is_inter, 0 where get_ext_tx_types <= 1
-    int      sq;              // txsize_sqr_map
-    uint32_t th;              // (tx_width * tx_height) >> 6
     uint32_t c_div;           // MAX(1, mds_fast_coeff_est_level - mds_subres_step)
     uint32_t n_packs;
 };
 
-// get_golomb_cost (rd_cost.c:90-97) of a level >= 1 + NUM_BASE_LEVELS + COEFF_BASE_RANGE = 15
-__device__ __forceinline__ uint32_t golomb_cost(uint32_t a) { return kCostLiteral * (2u * (32u - (uint32_t)__builtin_clz(a - 14u)) - 1u); }
-
-// lps_cost[ctx][min(level - 1 - NUM_BASE_LEVELS, COEFF_BASE_RANGE)] (+ the Golomb tail) of a level above NUM_BASE_LEVELS
-__device__ __forceinline__ uint32_t range_cost(const SvtHipLvMapCoeffCost *cc, int br, uint32_t a) {
-    const uint32_t base_range = a - 3u;
-    return (uint32_t)cc->lps_cost[br][base_range < 12u ? base_range : 12u] + (a >= 15u ? golomb_cost(a) : 0u);
-}
-
 // The cost terms of the coefficient at raster position `pos` (scan index si < eob) of a block with eob >= 2; `bad` is set where the reference
-// would index base_eob_cost[..][-1].  lev: the group's levels array.
-__device__ __forceinline__ uint32_t position_cost(const RateParams &p, const SvtHipLvMapCoeffCost *cc, const uint8_t *lev, int cls, int n, uint32_t eob,
-                                                  uint32_t c_start, int dc_sign_ctx, int pos, uint32_t si, int32_t v, uint32_t &bad) {
+// would index base_eob_cost[..][-1].
+__device__ __forceinline__ uint32_t position_cost(const LvBlk &b, const SvtHipLvMapCoeffCost *cc, uint32_t eob, uint32_t c_start, int dc_sign_ctx, int pos,
+                                                  uint32_t si, int32_t v, uint32_t &bad) {
     const bool last = si == eob - 1u;
     if (!last && si > c_start) return 0u; // si == 0 is the DC: always counted
-    const uint32_t a      = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
-    const int      stride = p.w + 4, row = pos >> p.bwl, col = pos - (row << p.bwl);
-    const uint8_t *l      = lev + row * stride + col;
-    uint32_t       cost   = 0;
-    if (last) { // rd_cost.c:351-376; get_nz_map_ctx with is_eob (encode_txb_ref_c.c:19-27)
+    const uint32_t a = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+    uint32_t       cost;
+    if (last) { // rd_cost.c:351-376
         if (a == 0u) { bad = 1u; return 0u; }
-        const int ctx = si <= (uint32_t)(n >> 3) ? 1 : (si <= (uint32_t)(n >> 2) ? 2 : 3);
-        cost = (uint32_t)cc->base_eob_cost[ctx][(a < 3u ? a : 3u) - 1u] + kCostLiteral;
+        cost = (uint32_t)(cc->base_eob_cost[eob_ctx(b, (int)si)][(a < 3u ? a : 3u) - 1u] + kCostLiteral);
     } else { // the DC (:377-404) and the middle loop (:410-427)
-        int mag = (l[1] < 3 ? l[1] : 3) + (l[stride] < 3 ? l[stride] : 3); // get_nz_mag: clip_max3 of {0,1}, {1,0}
-        int off;
-        if (cls == 0) { // {1,1}, {0,2}, {2,0}
-            mag += (l[stride + 1] < 3 ? l[stride + 1] : 3) + (l[2] < 3 ? l[2] : 3) + (l[2 * stride] < 3 ? l[2 * stride] : 3);
-            // the rule behind eb_av1_nz_map_ctx_offset (coefficients.h:2918-2928), on the real transform dimensions
-            if (p.shape == 1 && row < 2) off = 11;
-            else if (p.shape == 2 && col < 2) off = 16;
-            else off = row + col < 2 ? 1 : (row + col < 4 ? 6 : 21);
-        } else if (cls == 2) { // TX_CLASS_VERT: {2,0}, {3,0}, {4,0}
-            mag += (l[2 * stride] < 3 ? l[2 * stride] : 3) + (l[3 * stride] < 3 ? l[3 * stride] : 3) + (l[4 * stride] < 3 ? l[4 * stride] : 3);
-            off = row == 0 ? 26 : (row == 1 ? 31 : 36); // nz_map_ctx_offset_1d
-        } else { // TX_CLASS_HORIZ: {0,2}, {0,3}, {0,4}
-            mag += (l[2] < 3 ? l[2] : 3) + (l[3] < 3 ? l[3] : 3) + (l[4] < 3 ? l[4] : 3);
-            off = col == 0 ? 26 : (col == 1 ? 31 : 36);
-        }
-        int ctx = (mag + 1) >> 1;
-        ctx     = (ctx < 4 ? ctx : 4) + off;
-        if ((cls | pos) == 0) ctx = 0;
-        cost = (uint32_t)cc->base_cost[ctx][a < 3u ? a : 3u];
-        if (a != 0u) cost += pos == 0 ? (uint32_t)cc->dc_sign_cost[dc_sign_ctx][v < 0 ? 1 : 0] : kCostLiteral;
+        cost = (uint32_t)cc->base_cost[lower_ctx(b, pos)][a < 3u ? a : 3u];
+        if (a != 0u) cost += (uint32_t)(pos == 0 ? cc->dc_sign_cost[dc_sign_ctx][v < 0 ? 1 : 0] : kCostLiteral);
     }
-    if (a > 2u) { // get_br_ctx (common_utils.h:114-151)
-        int  mag = l[1] + l[stride];
-        bool near;
-        if (cls == 0) { mag += l[stride + 1]; near = row < 2 && col < 2; }
-        else if (cls == 1) { mag += l[2]; near = col == 0; }
-        else { mag += l[2 * stride]; near = row == 0; }
-        mag = (mag + 1) >> 1;
-        mag = mag < 6 ? mag : 6;
-        cost += range_cost(cc, pos == 0 ? mag : mag + (near ? 7 : 14), a);
-    }
+    // get_br_ctx, not get_br_ctx_eob, for the last one too: the reference reads its neighbours, and levels behind eob count
+    if (a > 2u) cost += (uint32_t)range_cost(cc, br_ctx(b, pos), (int)a);
     return cost;
 }
 
@@ -123,17 +67,13 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) coeff_rate_kerne
     constexpr int V = N >= 256 ? 4 : 1, G = N / V < 64 ? N / V : 64, ITER = N / (G * V), JPW = 64 / G;
     __shared__ int32_t tab[kCoeffInts + kEobInts];
     __shared__ __attribute__((aligned(16))) uint8_t levels[kWaves][kLevelBytes];
-    {
-        const int32_t *src_c = reinterpret_cast<const int32_t *>(&p.d.tables->coeff_fac_bits[p.txs_ctx][p.d.plane_type]);
-        const int32_t *src_e = reinterpret_cast<const int32_t *>(&p.d.tables->eob_frac_bits[p.eob_multi][p.d.plane_type]);
-        for (int i = threadIdx.x; i < kCoeffInts + kEobInts; i += 64 * kWaves) tab[i] = i < kCoeffInts ? src_c[i] : src_e[i - kCoeffInts];
-    }
-    __syncthreads();
+    stage_cost_tables(tab, p.d.tables, p.g.txs_ctx, p.g.eob_multi, p.d.plane_type);
     const SvtHipLvMapCoeffCost *cc = reinterpret_cast<const SvtHipLvMapCoeffCost *>(tab);
     const SvtHipLvMapEobCost   *ec = reinterpret_cast<const SvtHipLvMapEobCost *>(tab + kCoeffInts);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = lane / G, gl = lane % G;
-    const int stride = p.w + 4, lev_bytes = stride * (p.h + 4); // a multiple of 16
+    const int stride = p.g.w + 4, lev_bytes = stride * (p.g.h + 4); // a multiple of 16
     uint8_t  *lev = levels[wave] + grp * lev_bytes;
+    LvBlk     b   = {lev, stride, p.g.bwl, p.g.shape, 0, N};
     for (uint32_t pack = blockIdx.x * kWaves + wave; pack < p.n_packs; pack += gridDim.x * kWaves) { // uniform per wave
         const uint32_t job   = pack * JPW + grp;
         const bool     valid = job < p.d.n_jobs;
@@ -144,18 +84,18 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) coeff_rate_kerne
         const uint32_t lvl = p.d.coeff_rate_est_lvl;
         uint64_t bits    = ~0ull;
         bool     compute = false;
-        if (p.d.plane_type == 0 && lvl != 1 && eob < p.th) bits = 6000ull + (uint64_t)eob * 1000ull;
+        if (p.d.plane_type == 0 && lvl != 1 && eob < (uint32_t)p.g.area >> 6) bits = 6000ull + (uint64_t)eob * 1000ull;
         else if (p.d.plane_type == 0 && lvl == 0) bits = 3000ull + (uint64_t)eob * 100ull;
         else if (jb.txb_skip_ctx >= 13) bits = ~0ull; // a context outside its table: undefined, nothing is read
         else if (eob == 0) bits = (uint64_t)(int64_t)cc->txb_skip_cost[jb.txb_skip_ctx][1]; // av1_cost_skip_txb
         else // intra_dir is read by intra luma jobs alone (rd_cost.c:137-153): an inter candidate's pred_mode is 13 or above and is fine
             compute = valid && eob <= (uint32_t)N && jb.tx_type < 16 && jb.dc_sign_ctx < 3 && (p.d.plane_type != 0 || jb.is_inter || jb.intra_dir < 13);
-        const int      kind    = jb.tx_type >= 10 ? ((jb.tx_type & 1) ? 2 : 1) : 0; // the scan: default, rows (V_*), columns (H_*)
-        const int      cls     = jb.tx_type >= 10 ? ((jb.tx_type & 1) ? 1 : 2) : 0; // tx_type_to_class: TX_CLASS_2D / HORIZ / VERT
+        const int      kind    = tx_scan_kind(jb.tx_type);
+        b.cls                  = tx_class(jb.tx_type);
         const uint32_t c_start = eob >= 2 ? (eob - 2u < eob / p.c_div ? eob - 2u : eob / p.c_div) : 0u; // rd_cost.c:408
 
         // svt_av1_txb_init_levels_c: min(|qcoeff|, 127) over the WHOLE block, in a zero frame
-        for (int i = gl * 16; i < lev_bytes; i += G * 16) *reinterpret_cast<uint4 *>(lev + i) = make_uint4(0, 0, 0, 0);
+        zero_levels<G>(lev, lev_bytes, gl);
         wave_sync();
 #pragma unroll 1
         for (int it = 0; it < ITER; it++) {
@@ -168,7 +108,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) coeff_rate_kerne
                 const uint32_t a = q[v] < 0 ? 0u - (uint32_t)q[v] : (uint32_t)q[v];
                 packed |= (a < 127u ? a : 127u) << (8 * v);
             }
-            const int row = pos >> p.bwl, col = pos - (row << p.bwl); // four positions in a row never straddle rows: the width is a multiple of 4
+            const int row = pos >> p.g.bwl, col = pos - (row << p.g.bwl); // four positions in a row never straddle rows: the width is a multiple of 4
             if constexpr (V == 4) *reinterpret_cast<uint32_t *>(lev + row * stride + col) = packed;
             else lev[row * stride + col] = (uint8_t)packed;
         }
@@ -183,7 +123,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) coeff_rate_kerne
                     if (a == 0u) bad = 1u;
                     else {
                         cost = (uint32_t)cc->base_eob_cost[0][(a < 3u ? a : 3u) - 1u] + (uint32_t)cc->dc_sign_cost[jb.dc_sign_ctx][v < 0 ? 1 : 0];
-                        if (a > 2u) cost += range_cost(cc, 0, a);
+                        if (a > 2u) cost += (uint32_t)range_cost(cc, 0, (int)a);
                     }
                 }
             } else {
@@ -201,7 +141,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) coeff_rate_kerne
 #pragma unroll
                     for (int v = 0; v < V; v++) {
                         const uint32_t s = (uint32_t)(uint16_t)si[v];
-                        if (s < eob) cost += position_cost(p, cc, lev, cls, N, eob, c_start, jb.dc_sign_ctx, pos + v, s, q[v], bad);
+                        if (s < eob) cost += position_cost(b, cc, eob, c_start, jb.dc_sign_ctx, pos + v, s, q[v], bad);
                     }
                 }
             }
@@ -215,18 +155,10 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) coeff_rate_kerne
                 if (p.d.plane_type == 0) { // av1_transform_type_rate_estimation
                     const int inter = jb.is_inter ? 1 : 0, set = p.ext_set[inter];
                     if (set > 0)
-                        cost += (uint32_t)(inter ? p.d.tables->inter_tx_type_fac_bits[set][p.sq][jb.tx_type]
-                                                 : p.d.tables->intra_tx_type_fac_bits[set][p.sq][jb.intra_dir][jb.tx_type]);
+                        cost += (uint32_t)(inter ? p.d.tables->inter_tx_type_fac_bits[set][p.g.sq][jb.tx_type]
+                                                 : p.d.tables->intra_tx_type_fac_bits[set][p.g.sq][jb.intra_dir][jb.tx_type]);
                 }
-                // get_eob_pos_token: 1, 2, then one token per power of two: eb_k_eob_group_start = 0 1 2 3 5 9 17 .. 513, eb_k_eob_offset_bits = 0 0 0 1 2 .. 9
-                const int eob_pt = 33 - (eob > 1 ? __builtin_clz(eob - 1u) : 32);
-                cost += (uint32_t)ec->eob_cost[cls == 0 ? 0 : 1][eob_pt - 1];
-                if (eob_pt > 2) {
-                    const int      offset_bits = eob_pt - 2;
-                    const uint32_t eob_extra   = eob - ((1u << offset_bits) + 1u);
-                    cost += (uint32_t)cc->eob_extra_cost[eob_pt - 3][(eob_extra >> (offset_bits - 1)) & 1u];
-                    if (offset_bits > 1) cost += kCostLiteral * (uint32_t)(offset_bits - 1);
-                }
+                cost += (uint32_t)eob_cost(cc, ec, b.cls, (int)eob);
                 bits = (uint64_t)(int64_t)(int32_t)cost; // the reference's int32_t cost, returned as uint64_t
                 if (p.d.plane_type == 0) bits <<= p.d.mds_subres_step;
             }
@@ -256,12 +188,6 @@ __global__ void __launch_bounds__(256) rate_group_kernel(const SvtHipCoeffRateDe
     d.best_cost[g] = best_cost;
 }
 
-const int kTxW[19]      = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64};
-const int kTxH[19]      = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16};
-const int kSqrMap[19]   = {0, 1, 2, 3, 4, 0, 0, 1, 1, 2, 2, 3, 3, 0, 0, 1, 1, 2, 2}; // txsize_sqr_map (Codec/definitions.h:1509)
-const int kSqrUpMap[19] = {0, 1, 2, 3, 4, 1, 1, 2, 2, 3, 3, 4, 4, 2, 2, 3, 3, 4, 4}; // txsize_sqr_up_map (:1530)
-const int kLog2M4[19]   = {0, 2, 4, 6, 6, 1, 1, 3, 3, 5, 5, 6, 6, 2, 2, 4, 4, 5, 5}; // txsize_log2_minus4 (Codec/inv_transforms.h:329)
-
 // get_ext_tx_set (Codec/definitions.h:1787-1828), 0 where get_ext_tx_types <= 1 or the set carries no rate
 int ext_tx_set(int tx_size, int is_inter, int reduced) {
     const int up = kSqrUpMap[tx_size], sq = kSqrMap[tx_size];
@@ -288,7 +214,9 @@ int svt_hip_coeff_rate_batch(SvtHipContext *ctx, const SvtHipCoeffRateDesc *d) {
                             d->mds_subres_step, d->mds_fast_coeff_est_level);
     if (!d->jobs || !d->tables || !d->qcoeff || !d->eob || !d->bits)
         return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: a mandatory pointer (jobs, tables, qcoeff, eob, bits) is null");
-    if (((uintptr_t)d->qcoeff & 15) && (kTxW[d->tx_size] > 32 ? 32 : kTxW[d->tx_size]) * (kTxH[d->tx_size] > 32 ? 32 : kTxH[d->tx_size]) >= 256)
+    const int       ts = d->tx_size;
+    const LvMapGeom g  = lvmap_geom(ts);
+    if (((uintptr_t)d->qcoeff & 15) && g.n >= 256)
         return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: qcoeff is not 16-byte aligned (sizes of 256 coefficients and more are read 16 bytes at a time)");
     if (d->rd_cost && !d->dist) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: rd_cost without dist");
     const bool groups = d->n_groups || d->group_start || d->best_job || d->best_cost;
@@ -297,33 +225,21 @@ int svt_hip_coeff_rate_batch(SvtHipContext *ctx, const SvtHipCoeffRateDesc *d) {
         return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: groups need group_start, best_job and best_cost");
     if (d->n_jobs == 0 && d->n_groups == 0) return SVT_HIP_OK;
     hipSetDevice(ctx->device);
-    const int ts = d->tx_size;
     RateParams p;
     memset(&p, 0, sizeof(p));
     p.d = *d;
     for (int k = 0; k < 3; k++) p.iscan[k] = ctx->iscan_dev + ((size_t)ts * 3 + k) * 1024;
-    p.w = kTxW[ts] > 32 ? 32 : kTxW[ts];
-    p.h = kTxH[ts] > 32 ? 32 : kTxH[ts];
-    p.bwl = p.w == 4 ? 2 : (p.w == 8 ? 3 : (p.w == 16 ? 4 : 5));
-    p.txs_ctx   = (kSqrMap[ts] + kSqrUpMap[ts] + 1) >> 1;
-    p.eob_multi = kLog2M4[ts];
-    p.shape     = kTxW[ts] < kTxH[ts] ? 1 : (kTxW[ts] > kTxH[ts] ? 2 : 0);
-    p.sq        = kSqrMap[ts];
+    p.g = g;
     for (int inter = 0; inter < 2; inter++) p.ext_set[inter] = ext_tx_set(ts, inter, d->reduced_tx_set != 0);
-    p.th    = (uint32_t)(kTxW[ts] * kTxH[ts]) >> 6;
     p.c_div = d->mds_fast_coeff_est_level > d->mds_subres_step ? (uint32_t)(d->mds_fast_coeff_est_level - d->mds_subres_step) : 1u;
-    const int n   = p.w * p.h;
-    const int jpw = n >= 64 ? 1 : 64 / n;
-    p.n_packs     = (d->n_jobs + (uint32_t)jpw - 1) / (uint32_t)jpw;
+    const uint32_t grid = lvmap_grid(g, d->n_jobs, p.n_packs);
     std::lock_guard<std::mutex> lock(ctx->async_mu); // the winners' launch follows its own costs' when several threads enqueue
     if (d->n_jobs) {
-        uint32_t grid = (p.n_packs + kWaves - 1) / kWaves;
-        grid = grid < (uint32_t)kMaxGrid ? grid : (uint32_t)kMaxGrid;
-        switch (n) {
+        switch (g.n) {
 #define CASE(N) case N: hipLaunchKernelGGL(coeff_rate_kernel<N>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, p); break;
             CASE(16) CASE(32) CASE(64) CASE(128) CASE(256) CASE(512) CASE(1024)
 #undef CASE
-        default: return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: %d coefficients", n);
+        default: return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: %d coefficients", g.n);
         }
         SVT_HIP_CHECK(ctx, hipGetLastError());
     }

@@ -6,18 +6,16 @@
 //   svt_av1_optimize_b                                                               Codec/full_loop.c:1127-1336
 //   update_coeff_general, update_coeff_eob, update_coeff_simple, update_skip         Codec/full_loop.c:948-999,847-947,1001-1045,1046-1061
 //   get_coeff_cost_general / _eob, get_two_coeff_cost_simple, get_br_cost_with_diff and its two Golomb tables   Codec/full_loop.c:734-838
-//   get_eob_cost, get_dqv, get_qc_dqc_low, get_coeff_dist, plane_rd_mult             Codec/full_loop.c:694-711,840-845,762-772,1077-1085
+//   get_dqv, get_qc_dqc_low, get_coeff_dist, plane_rd_mult                           Codec/full_loop.c:840-845,762-772,1077-1085
 //   svt_fast_optimize_b = update_coeff_eob_fast                                      Codec/full_loop.c:1092-1126
-//   get_lower_levels_ctx, get_lower_levels_ctx_eob, get_br_ctx_eob, get_padded_idx   Codec/coefficients.h:2851-2950
-//   get_br_ctx                                                                       Codec/common_utils.h:114-151
 //   RDCOST (signed 64-bit: dist - dist0 is negative)                                 Codec/rd_cost.h:37
 //   svt_av1_compute_cul_level_c, svt_full_distortion_kernel32_bits                   Codec/full_loop.c:1449-1466, Codec/pic_operators.c:150-172
 // TUNE_CHROMA_SSIM is 1 in the reference tree (Source/API/EbDebugMacros.h:43): plane_rd_mult = {17, 13}, {16, 10}.
 //
-// Lay-out as in coeff_rate_kernel.hip: a batch shares tx_size and plane_type, so a workgroup of four waves copies ONE LvMapCoeffCost and one
-// LvMapEobCost into LDS; a group of G = min(64, coefficients) lanes takes one job and keeps its padded levels array (one byte per level) and
-// one decision byte per coefficient in LDS.  The coefficient arrays are only READ until the tail: a coefficient is decided once, before that
-// its value is the caller's, so a decision is a byte (0 kept, 1 lowered by one, 2 zeroed) and the tail writes the changed coefficients.
+// The lay-out (the cost tables and a group's padded levels array in LDS, G lanes per job), the context rules and the shared cost terms of the
+// level map: lvmap_core.h.  Beside its levels a group keeps one decision byte per coefficient in LDS.  The coefficient arrays are only READ
+// until the tail: a coefficient is decided once, before that its value is the caller's, so a decision is a byte (0 kept, 1 lowered by one,
+// 2 zeroed) and the tail writes the changed coefficients.
 //   head    update_coeff_eob until more than four non-zeros are kept, then update_skip: serial in accu_rate / accu_dist.  Every lane of the
 //           group carries the same state and takes the same decision (the loads are broadcasts); between two non-zeros the zeros only add
 //           base_cost[ctx][0], with contexts that are fixed once the previous decision is made: a lane-parallel sum.
@@ -31,99 +29,44 @@
 #include <string.h>
 #include "svt_hip_internal.h"
 #include "../../include/svt_hip_dsp.h"
+#include "lvmap_core.h"
 #include "wave_ops.h"
 
 namespace {
 
-constexpr int kWaves      = 4;
-constexpr int kCoeffInts  = sizeof(SvtHipLvMapCoeffCost) / 4;
-constexpr int kEobInts    = sizeof(SvtHipLvMapEobCost) / 4;
-constexpr int kLevelBytes = (32 + 4) * (32 + 4);
-constexpr int kMaxGrid    = 2048;
-constexpr int kCostLiteral = 512; // av1_cost_literal(1)
 enum : uint8_t { kKept = 0, kLowered = 1, kZeroed = 2 };
 enum : uint8_t { kStOptimised = 0, kStEmpty = 1, kStGated = 2, kStUndefined = 0xFF };
 
 struct RdoqParams {
     SvtHipRdoqDesc d;
     const int16_t *iscan;    // [3][1024]: default, row (V_*), column (H_*) inverse scans of this tx_size
-    int bwl;                 // get_txb_bwl_tab: the packed block is (1 << bwl) wide
-    int txs_ctx, eob_multi;
-    int shape;               // 0 square, 1 tx width < tx height, 2 tx width > tx height (the real dimensions)
-    int shift;               // av1_get_tx_scale_tab
-    int area;                // tx_width * tx_height, the real dimensions (eob_perc)
+    LvMapGeom g;             // the packed block is (1 << g.bwl) wide; g.area: eob_perc
     int rshift;              // MAX(2, CLIP3(0, 7, sharpness))
     uint32_t n_packs;
 };
 
 // what a job's walk needs of its block
-struct Blk {
+struct Blk : LvBlk {
     const SvtHipLvMapCoeffCost *cc;
     const SvtHipLvMapEobCost   *ec;
-    const uint8_t *lev;
     const uint8_t *iqm; // null: flat
-    int stride, bwl, w, n, shape, cls, shift, dc_sign_ctx;
+    int w, shift, dc_sign_ctx;
     int dq0, dq1;
     int64_t rdmult;
 };
 
-__device__ __forceinline__ int min3(int v) { return v < 3 ? v : 3; }
 __device__ __forceinline__ int64_t rdcost(int64_t rm, int64_t r, int64_t d) { return ((r * rm + 256) >> 9) + d * 128; }
 __device__ __forceinline__ int64_t coeff_dist(int64_t t, int64_t d, int shift) { const int64_t e = (t - d) * ((int64_t)1 << shift); return e * e; }
 __device__ __forceinline__ int dqv_at(const Blk &b, int pos) {
     const int d = pos ? b.dq1 : b.dq0;
     return b.iqm ? (b.iqm[pos] * d + 16) >> 5 : d;
 }
-// get_lower_levels_ctx
-__device__ __forceinline__ int lower_ctx(const Blk &b, int pos) {
-    const int      row = pos >> b.bwl, col = pos - (row << b.bwl), stride = b.stride;
-    const uint8_t *l = b.lev + row * stride + col;
-    int mag = min3(l[1]) + min3(l[stride]), off;
-    if (b.cls == 0) {
-        if (pos == 0) return 0;
-        mag += min3(l[stride + 1]) + min3(l[2]) + min3(l[2 * stride]);
-        if (b.shape == 1 && row < 2) off = 11;
-        else if (b.shape == 2 && col < 2) off = 16;
-        else off = row + col < 2 ? 1 : (row + col < 4 ? 6 : 21);
-    } else if (b.cls == 2) {
-        mag += min3(l[2 * stride]) + min3(l[3 * stride]) + min3(l[4 * stride]);
-        off = row == 0 ? 26 : (row == 1 ? 31 : 36);
-    } else {
-        mag += min3(l[2]) + min3(l[3]) + min3(l[4]);
-        off = col == 0 ? 26 : (col == 1 ? 31 : 36);
-    }
-    const int ctx = (mag + 1) >> 1;
-    return (ctx < 4 ? ctx : 4) + off;
-}
-// get_lower_levels_ctx_eob
-__device__ __forceinline__ int eob_ctx(const Blk &b, int si) { return si == 0 ? 0 : (si <= (b.n >> 3) ? 1 : (si <= (b.n >> 2) ? 2 : 3)); }
-__device__ __forceinline__ bool near_origin(const Blk &b, int pos) {
-    const int row = pos >> b.bwl, col = pos - (row << b.bwl);
-    return b.cls == 0 ? (row < 2 && col < 2) : (b.cls == 1 ? col == 0 : row == 0);
-}
-// get_br_ctx_eob / get_br_ctx
-__device__ __forceinline__ int br_ctx_eob(const Blk &b, int pos) { return pos == 0 ? 0 : (near_origin(b, pos) ? 7 : 14); }
-__device__ __forceinline__ int br_ctx(const Blk &b, int pos) {
-    const int      row = pos >> b.bwl, col = pos - (row << b.bwl), stride = b.stride;
-    const uint8_t *l = b.lev + row * stride + col;
-    int mag = l[1] + l[stride] + (b.cls == 0 ? l[stride + 1] : (b.cls == 1 ? l[2] : l[2 * stride]));
-    mag = (mag + 1) >> 1;
-    mag = mag < 6 ? mag : 6;
-    return pos == 0 ? mag : mag + (near_origin(b, pos) ? 7 : 14);
-}
-// get_golomb_cost of a level >= 15
-__device__ __forceinline__ int golomb_cost(int a) { return kCostLiteral * (2 * (32 - __builtin_clz((uint32_t)(a - 14))) - 1); }
-// get_br_cost
-__device__ __forceinline__ int br_cost(const Blk &b, int br, int a) {
-    const int base_range = a - 3;
-    return b.cc->lps_cost[br][base_range < 12 ? base_range : 12] + (a >= 15 ? golomb_cost(a) : 0);
-}
 // get_coeff_cost_general; is_last: get_coeff_cost_eob (ctx is then get_lower_levels_ctx_eob's)
 __device__ __forceinline__ int coeff_cost(const Blk &b, bool is_last, int pos, int a, int sign, int ctx) {
     int cost = is_last ? b.cc->base_eob_cost[ctx][min3(a) - 1] : b.cc->base_cost[ctx][min3(a)];
     if (a != 0) {
         cost += pos == 0 ? b.cc->dc_sign_cost[b.dc_sign_ctx][sign] : kCostLiteral;
-        if (a > 2) cost += br_cost(b, is_last ? br_ctx_eob(b, pos) : br_ctx(b, pos), a);
+        if (a > 2) cost += range_cost(b.cc, is_last ? br_ctx_eob(b, pos) : br_ctx(b, pos), a);
     }
     return cost;
 }
@@ -144,17 +87,6 @@ __device__ __forceinline__ int two_coeff_cost(const Blk &b, int pos, int a, int 
         cost += lps[base_range] + golomb;
     }
     cost_low = cost - diff;
-    return cost;
-}
-// get_eob_cost
-__device__ __forceinline__ int eob_cost(const Blk &b, int eob) {
-    const int eob_pt = 33 - (eob > 1 ? __builtin_clz((uint32_t)eob - 1u) : 32);
-    int cost = b.ec->eob_cost[b.cls == 0 ? 0 : 1][eob_pt - 1];
-    if (eob_pt > 2) {
-        const int offset_bits = eob_pt - 2, eob_extra = eob - ((1 << offset_bits) + 1);
-        cost += b.cc->eob_extra_cost[eob_pt - 3][(eob_extra >> (offset_bits - 1)) & 1];
-        if (offset_bits > 1) cost += kCostLiteral * (offset_bits - 1);
-    }
     return cost;
 }
 
@@ -184,21 +116,16 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
     __shared__ int32_t tab[kCoeffInts + kEobInts];
     __shared__ __attribute__((aligned(16))) uint8_t levels[kWaves][kLevelBytes];
     __shared__ uint8_t decisions[kWaves][1024];
-    {
-        const int32_t *src_c = reinterpret_cast<const int32_t *>(&p.d.tables->coeff_fac_bits[p.txs_ctx][p.d.plane_type]);
-        const int32_t *src_e = reinterpret_cast<const int32_t *>(&p.d.tables->eob_frac_bits[p.eob_multi][p.d.plane_type]);
-        for (int i = threadIdx.x; i < kCoeffInts + kEobInts; i += 64 * kWaves) tab[i] = i < kCoeffInts ? src_c[i] : src_e[i - kCoeffInts];
-    }
-    __syncthreads();
+    stage_cost_tables(tab, p.d.tables, p.g.txs_ctx, p.g.eob_multi, p.d.plane_type);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = lane / G, gl = lane % G;
-    const int w = 1 << p.bwl, h = N >> p.bwl;
+    const int w = 1 << p.g.bwl, h = N >> p.g.bwl;
     const int stride = w + 4, lev_bytes = stride * (h + 4); // a multiple of 16
     uint8_t  *lev = levels[wave] + grp * lev_bytes;
     uint8_t  *dec = decisions[wave] + grp * N;
     Blk b;
     b.cc = reinterpret_cast<const SvtHipLvMapCoeffCost *>(tab);
     b.ec = reinterpret_cast<const SvtHipLvMapEobCost *>(tab + kCoeffInts);
-    b.lev = lev; b.stride = stride; b.bwl = p.bwl; b.w = w; b.n = N; b.shape = p.shape; b.shift = p.shift;
+    b.lev = lev; b.stride = stride; b.bwl = p.g.bwl; b.w = w; b.n = N; b.shape = p.g.shape; b.shift = p.g.log_scale;
     for (uint32_t pack = blockIdx.x * kWaves + wave; pack < p.n_packs; pack += gridDim.x * kWaves) { // uniform per wave
         const uint32_t job   = pack * JPW + grp;
         const bool     valid = job < p.d.n_jobs;
@@ -211,21 +138,21 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
             eob = p.d.eob[job];
         }
         const bool defined = jb.tx_type < 16 && jb.txb_skip_ctx < 13 && jb.dc_sign_ctx < 3 && jb.quant_row < p.d.n_quant_rows;
-        const int  kind = jb.tx_type >= 10 ? ((jb.tx_type & 1) ? 2 : 1) : 0;
+        const int  kind = tx_scan_kind(jb.tx_type);
         const int16_t *iscan = p.iscan + (defined ? kind : 0) * 1024;
         const size_t   base  = (size_t)job * N;
-        b.cls = jb.tx_type >= 10 ? ((jb.tx_type & 1) ? 1 : 2) : 0;
+        b.cls = tx_class(jb.tx_type);
         b.dc_sign_ctx = jb.dc_sign_ctx;
         b.iqm = jb.tx_type < 9 ? p.d.iqmatrix : nullptr; // IS_2D_TRANSFORM (full_loop.c:1606-1608)
         const bool walk = valid && defined && eob > 0 && eob <= N; // the job reads its coefficients
         int status = !valid || !defined || eob > N ? kStUndefined : (eob == 0 ? kStEmpty : kStOptimised);
 
         // svt_av1_txb_init_levels: min(|qcoeff|, 127) over the WHOLE block in a zero frame; no decision yet
-        for (int i = gl * 16; i < lev_bytes; i += G * 16) *reinterpret_cast<uint4 *>(lev + i) = make_uint4(0, 0, 0, 0);
+        zero_levels<G>(lev, lev_bytes, gl);
         wave_sync();
 #pragma unroll 1
         for (int it = 0; it < PPL; it++) {
-            const int     pos = it * G + gl, row = pos >> p.bwl, col = pos - (row << p.bwl);
+            const int     pos = it * G + gl, row = pos >> p.g.bwl, col = pos - (row << p.g.bwl);
             const int32_t q   = walk ? p.d.qcoeff[base + pos] : 0;
             const uint32_t a  = q < 0 ? 0u - (uint32_t)q : (uint32_t)q;
             lev[row * stride + col] = (uint8_t)(a < 127u ? a : 127u);
@@ -237,14 +164,14 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
             int key = -1;
 #pragma unroll 1
             for (int it = 0; it < PPL; it++) {
-                const int pos = it * G + gl, row = pos >> p.bwl, col = pos - (row << p.bwl);
+                const int pos = it * G + gl, row = pos >> p.g.bwl, col = pos - (row << p.g.bwl);
                 const int si  = (int)(uint16_t)iscan[pos];
                 if (si < bound && lev[row * stride + col] != 0) { const int k = (si << 10) | pos; key = k > key ? k : key; }
             }
             return group_max<G>(key);
         };
         auto zero_at = [&](int pos) {
-            const int row = pos >> p.bwl, col = pos - (row << p.bwl);
+            const int row = pos >> p.g.bwl, col = pos - (row << p.g.bwl);
             lev[row * stride + col] = 0;
             dec[pos] = kZeroed;
         };
@@ -258,7 +185,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
         if (optimise) { b.dq0 = qr->dequant[0]; b.dq1 = qr->dequant[1]; }
         int eob_for_cost = eob;
         if (optimise) { // the caller's frame (full_loop.c:1764-1796)
-            const int  eob_perc  = eob * 100 / p.area;
+            const int  eob_perc  = eob * 100 / p.g.area;
             const bool fast_mode = jb.is_inter ? p.d.eob_fast_inter != 0 : p.d.eob_fast_intra != 0;
             if (eob_perc >= p.d.eob_th) {
                 status   = kStGated;
@@ -271,19 +198,19 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                 int key = -1;
 #pragma unroll 1
                 for (int it = 0; it < PPL; it++) {
-                    const int pos = it * G + gl, row = pos >> p.bwl, col = pos - (row << p.bwl);
+                    const int pos = it * G + gl, row = pos >> p.g.bwl, col = pos - (row << p.g.bwl);
                     const int si  = (int)(uint16_t)iscan[pos];
                     if (si < eob && lev[row * stride + col] != 0) {
                         const int32_t c  = p.d.coeff[base + pos];
                         const int64_t ac = c < 0 ? -(int64_t)c : (int64_t)c;
-                        if (!((ac << (1 + p.shift)) < (pos ? z1 : z0))) { const int k = (si << 10) | pos; key = k > key ? k : key; }
+                        if (!((ac << (1 + p.g.log_scale)) < (pos ? z1 : z0))) { const int k = (si << 10) | pos; key = k > key ? k : key; }
                     }
                 }
                 key = group_max<G>(key);
                 const int new_eob = (key >> 10) + 1; // key == -1: 0
 #pragma unroll 1
                 for (int it = 0; it < PPL; it++) {
-                    const int pos = it * G + gl, row = pos >> p.bwl, col = pos - (row << p.bwl);
+                    const int pos = it * G + gl, row = pos >> p.g.bwl, col = pos - (row << p.g.bwl);
                     const int si  = (int)(uint16_t)iscan[pos];
                     if (si >= new_eob && si < eob && lev[row * stride + col] != 0) { lev[row * stride + col] = 0; dec[pos] = kZeroed; }
                 }
@@ -300,7 +227,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                 const bool sharp     = (jb.flags & 1) != 0;
                 const int  mult      = jb.is_inter ? (p.d.plane_type ? 10 : 16) : (p.d.plane_type ? 13 : 17); // plane_rd_mult
                 b.rdmult             = (((int64_t)p.d.lambda * mult * (sharp ? 0 : 100)) / 100 + 2) >> p.rshift;
-                int     accu_rate    = eob_cost(b, eob_for_cost);
+                int     accu_rate    = eob_cost(b.cc, b.ec, b.cls, eob_for_cost);
                 int64_t accu_dist    = 0;
                 int     nz_num       = 1, nz0 = last_key & 1023, nz1 = 0, nz2 = 0, nz3 = 0, nz4 = 0;
                 int     S            = eob - 2; // the next scan index to visit
@@ -310,13 +237,13 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                     const int     a = qc < 0 ? -qc : qc;
                     if (a >= 2) {
                         if (general_step(b, true, eob - 1, pos, qc, dqc, tqc, accu_rate, accu_dist) && gl == 0) {
-                            const int row = pos >> p.bwl, col = pos - (row << p.bwl);
+                            const int row = pos >> p.g.bwl, col = pos - (row << p.g.bwl);
                             lev[row * stride + col] = (uint8_t)(a - 1 < 127 ? a - 1 : 127);
                             dec[pos] = kLowered;
                         }
                     } else {
                         accu_rate += coeff_cost(b, true, pos, a, qc < 0 ? 1 : 0, eob_ctx(b, eob - 1));
-                        accu_dist += coeff_dist(tqc, dqc, p.shift) - coeff_dist(tqc, 0, p.shift);
+                        accu_dist += coeff_dist(tqc, dqc, p.g.log_scale) - coeff_dist(tqc, 0, p.g.log_scale);
                     }
                     wave_sync();
                 }
@@ -327,7 +254,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                             int sum = 0;
 #pragma unroll 1
                             for (int it = 0; it < PPL; it++) {
-                                const int pos = it * G + gl, row = pos >> p.bwl, col = pos - (row << p.bwl);
+                                const int pos = it * G + gl, row = pos >> p.g.bwl, col = pos - (row << p.g.bwl);
                                 const int si  = (int)(uint16_t)iscan[pos];
                                 if (si > nsi && si <= S && lev[row * stride + col] == 0) sum += b.cc->base_cost[lower_ctx(b, pos)][0];
                             }
@@ -335,12 +262,12 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                         }
                         S = nsi - 1;
                         if (key < 0) { S = -1; break; }
-                        const int     pos = key & 1023, row = pos >> p.bwl, col = pos - (row << p.bwl);
+                        const int     pos = key & 1023, row = pos >> p.g.bwl, col = pos - (row << p.g.bwl);
                         const int32_t qc = p.d.qcoeff[base + pos], dqc = p.d.dqcoeff[base + pos], tqc = p.d.coeff[base + pos];
                         const int     a = qc < 0 ? -qc : qc, sign = qc < 0 ? 1 : 0;
                         const int     ctx = lower_ctx(b, pos);
-                        const int64_t dist0 = coeff_dist(tqc, 0, p.shift);
-                        int64_t       dist  = coeff_dist(tqc, dqc, p.shift) - dist0;
+                        const int64_t dist0 = coeff_dist(tqc, 0, p.g.log_scale);
+                        int64_t       dist  = coeff_dist(tqc, dqc, p.g.log_scale) - dist0;
                         int           rate  = coeff_cost(b, false, pos, a, sign, ctx);
                         int64_t       rd    = rdcost(b.rdmult, (int64_t)accu_rate + rate, accu_dist + dist);
                         int64_t dist_low, rd_low;
@@ -350,13 +277,13 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                             rate_low = b.cc->base_cost[ctx][0];
                             rd_low   = rdcost(b.rdmult, (int64_t)accu_rate + rate_low, accu_dist);
                         } else {
-                            const int64_t adl = ((int64_t)(a - 1) * dqv_at(b, pos)) >> p.shift;
-                            dist_low = coeff_dist(tqc, sign ? -adl : adl, p.shift) - dist0;
+                            const int64_t adl = ((int64_t)(a - 1) * dqv_at(b, pos)) >> p.g.log_scale;
+                            dist_low = coeff_dist(tqc, sign ? -adl : adl, p.g.log_scale) - dist0;
                             rate_low = coeff_cost(b, false, pos, a - 1, sign, ctx);
                             rd_low   = rdcost(b.rdmult, (int64_t)accu_rate + rate_low, accu_dist + dist_low);
                         }
                         bool      lower_new_eob = false, lower = false;
-                        const int ctx_new = eob_ctx(b, nsi), new_eob_cost = eob_cost(b, nsi + 1);
+                        const int ctx_new = eob_ctx(b, nsi), new_eob_cost = eob_cost(b.cc, b.ec, b.cls, nsi + 1);
                         int       rate_coeff_eob = new_eob_cost + coeff_cost(b, true, pos, a, sign, ctx_new);
                         int64_t   dist_new_eob = dist, rd_new_eob = rdcost(b.rdmult, rate_coeff_eob, dist_new_eob);
                         if (a > 1) {
@@ -413,7 +340,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                     int d_first = 0; // the farthest anti-diagonal that holds a non-zero of this phase: nothing is decided beyond it
 #pragma unroll 1
                     for (int it = 0; it < PPL; it++) {
-                        const int pos = it * G + gl, row = pos >> p.bwl, col = pos - (row << p.bwl);
+                        const int pos = it * G + gl, row = pos >> p.g.bwl, col = pos - (row << p.g.bwl);
                         const int si  = (int)(uint16_t)iscan[pos];
                         if (si >= 1 && si <= S && lev[row * stride + col] != 0) d_first = row + col > d_first ? row + col : d_first;
                     }
@@ -423,7 +350,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                         const int rmin = d - (w - 1) > 0 ? d - (w - 1) : 0, rmax = d < h - 1 ? d : h - 1;
                         const int row = rmin + gl, col = d - row;
                         if (row <= rmax) {
-                            const int pos = (row << p.bwl) + col;
+                            const int pos = (row << p.g.bwl) + col;
                             const int si  = (int)(uint16_t)iscan[pos];
                             if (si >= 1 && si <= S && lev[row * stride + col] != 0) {
                                 const int32_t qc = p.d.qcoeff[base + pos], dqc = p.d.dqcoeff[base + pos], tqc = p.d.coeff[base + pos];
@@ -432,8 +359,8 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                                 if (!(ad < at)) {
                                     int       rate_low;
                                     const int rate = two_coeff_cost(b, pos, a, lower_ctx(b, pos), rate_low);
-                                    const int64_t adl = ((int64_t)(a - 1) * dqv_at(b, pos)) >> p.shift;
-                                    if (rdcost(b.rdmult, rate_low, coeff_dist(at, adl, p.shift)) < rdcost(b.rdmult, rate, coeff_dist(at, ad, p.shift))) {
+                                    const int64_t adl = ((int64_t)(a - 1) * dqv_at(b, pos)) >> p.g.log_scale;
+                                    if (rdcost(b.rdmult, rate_low, coeff_dist(at, adl, p.g.log_scale)) < rdcost(b.rdmult, rate, coeff_dist(at, ad, p.g.log_scale))) {
                                         lev[row * stride + col] = (uint8_t)(a - 1 < 127 ? a - 1 : 127);
                                         dec[pos] = kLowered;
                                     }
@@ -474,7 +401,7 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
                         if (how == kZeroed) q = dq = 0;
                         else { // get_qc_dqc_low
                             const int     a   = (q < 0 ? -q : q) - 1;
-                            const int32_t adl = (int32_t)(((int64_t)a * dqv_at(b, pos)) >> p.shift);
+                            const int32_t adl = (int32_t)(((int64_t)a * dqv_at(b, pos)) >> p.g.log_scale);
                             dq = q < 0 ? -adl : adl;
                             q  = q < 0 ? -a : a;
                         }
@@ -508,13 +435,6 @@ template <int N> __global__ void __launch_bounds__(64 * kWaves) rdoq_kernel(cons
     }
 }
 
-const int kTxW[19]      = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64};
-const int kTxH[19]      = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16};
-const int kSqrMap[19]   = {0, 1, 2, 3, 4, 0, 0, 1, 1, 2, 2, 3, 3, 0, 0, 1, 1, 2, 2}; // txsize_sqr_map (Codec/definitions.h:1509)
-const int kSqrUpMap[19] = {0, 1, 2, 3, 4, 1, 1, 2, 2, 3, 3, 4, 4, 2, 2, 3, 3, 4, 4}; // txsize_sqr_up_map (:1530)
-const int kLog2M4[19]   = {0, 2, 4, 6, 6, 1, 1, 3, 3, 5, 5, 6, 6, 2, 2, 4, 4, 5, 5}; // txsize_log2_minus4 (Codec/inv_transforms.h:329)
-const int kLogScale[19] = {0, 0, 0, 1, 2, 0, 0, 0, 0, 1, 1, 2, 2, 0, 0, 0, 0, 1, 1}; // av1_get_tx_scale_tab (Codec/full_loop.h:53)
-
 } // namespace
 
 extern "C" {
@@ -533,30 +453,19 @@ int svt_hip_rdoq_batch(SvtHipContext *ctx, const SvtHipRdoqDesc *d) {
         return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_rdoq_batch: the fallback needs qcoeff_b, dqcoeff_b and eob_b");
     if (d->n_jobs == 0) return SVT_HIP_OK;
     hipSetDevice(ctx->device);
-    const int ts = d->tx_size;
     RdoqParams p;
     memset(&p, 0, sizeof(p));
     p.d = *d;
-    p.iscan = ctx->iscan_dev + (size_t)ts * 3 * 1024;
-    const int w = kTxW[ts] > 32 ? 32 : kTxW[ts], h = kTxH[ts] > 32 ? 32 : kTxH[ts];
-    p.bwl = w == 4 ? 2 : (w == 8 ? 3 : (w == 16 ? 4 : 5));
-    p.txs_ctx   = (kSqrMap[ts] + kSqrUpMap[ts] + 1) >> 1;
-    p.eob_multi = kLog2M4[ts];
-    p.shape     = kTxW[ts] < kTxH[ts] ? 1 : (kTxW[ts] > kTxH[ts] ? 2 : 0);
-    p.shift     = kLogScale[ts];
-    p.area      = kTxW[ts] * kTxH[ts];
-    p.rshift    = d->sharpness > 2 ? d->sharpness : 2;
-    const int n   = w * h;
-    const int jpw = n >= 64 ? 1 : 64 / n;
-    p.n_packs     = (d->n_jobs + (uint32_t)jpw - 1) / (uint32_t)jpw;
-    uint32_t grid = (p.n_packs + kWaves - 1) / kWaves;
-    grid = grid < (uint32_t)kMaxGrid ? grid : (uint32_t)kMaxGrid;
+    p.iscan  = ctx->iscan_dev + (size_t)d->tx_size * 3 * 1024;
+    p.g      = lvmap_geom(d->tx_size);
+    p.rshift = d->sharpness > 2 ? d->sharpness : 2;
+    const uint32_t grid = lvmap_grid(p.g, d->n_jobs, p.n_packs);
     std::lock_guard<std::mutex> lock(ctx->async_mu);
-    switch (n) {
+    switch (p.g.n) {
 #define CASE(N) case N: hipLaunchKernelGGL(rdoq_kernel<N>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, p); break;
         CASE(16) CASE(32) CASE(64) CASE(128) CASE(256) CASE(512) CASE(1024)
 #undef CASE
-    default: return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_rdoq_batch: %d coefficients", n);
+    default: return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_rdoq_batch: %d coefficients", p.g.n);
     }
     SVT_HIP_CHECK(ctx, hipGetLastError());
     return SVT_HIP_OK;

@@ -1,12 +1,13 @@
 // txfm_core.h -- device code shared by the kernels that run the AV1 integer transforms (rd_kernel.hip, tpl_kernel.hip): the 1-D
 // forward / inverse DCT, ADST and identity kernels of the reference, by structure, the shift / clamp helpers of the 2-D passes (the wave
-// reductions: wave_ops.h).  Each translation unit that includes it has its own copy of the constant tables; c_cospi is filled at context
+// reductions: wave_ops.h; tx_wide / tx_high / ilog2c / tx_log_scale: tx_geom.h).  Each translation unit that includes it has its own copy of the constant tables; c_cospi is filled at context
 // creation by txfm_upload_cospi() (svt_hip_rd_tables_init, svt_hip_tpl_tables_init).
 #ifndef SVT_HIP_TXFM_CORE_H
 #define SVT_HIP_TXFM_CORE_H
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "tx_geom.h"
 #include "wave_ops.h"
 
 namespace {
@@ -26,9 +27,6 @@ inline hipError_t txfm_upload_cospi() {
 __constant__ int32_t c_sinpi[4][5] = {{0, 330, 621, 836, 951}, {0, 660, 1241, 1672, 1901}, {0, 1321, 2482, 3344, 3803}, {0, 2642, 4964, 6689, 7606}};
 
 struct TxGeom { uint8_t w, h; };
-__host__ __device__ constexpr int tx_wide(int s) { constexpr uint8_t t[19] = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64}; return t[s]; }
-__host__ __device__ constexpr int tx_high(int s) { constexpr uint8_t t[19] = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16}; return t[s]; }
-__host__ __device__ constexpr int ilog2c(int n) { return n <= 1 ? 0 : 1 + ilog2c(n >> 1); }
 __host__ __device__ constexpr int brevc(int v, int bits) { int r = 0; for (int i = 0; i < bits; i++) r |= ((v >> i) & 1) << (bits - 1 - i); return r; }
 
 // fwd_txfm_shift_ls (Codec/transforms.h:27-45), fwd_cos_bit_col/row (:47-50), inv shifts (Codec/inv_transforms.c:17-35),
@@ -62,8 +60,6 @@ __device__ __forceinline__ uint32_t umul24_hi(uint32_t a, uint32_t b) {
     asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
     return hi;
 }
-// c_log_scale as a compile-time constant (av1_get_tx_scale: by the block's pixel count)
-__host__ __device__ constexpr int tx_log_scale(int s) { return tx_wide(s) * tx_high(s) > 1024 ? 2 : tx_wide(s) * tx_high(s) > 256 ? 1 : 0; }
 __device__ __forceinline__ int32_t rshift64(i64 v, int bit) { return (int32_t)((v + ((i64)1 << (bit - 1))) >> bit); }
 // half_btf of the reference (Codec/transforms.h / inv_transforms.h): two 32-bit wrapping products, summed and rounded in
 // 64 bits.  MUL == 1 (inverse transforms): both operands of every product fit 24 signed bits -- cos weights < 2^13, data
