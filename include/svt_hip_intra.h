@@ -27,9 +27,10 @@
  * arithmetic of svt_av1_predict_intra_block, and get_filt_type (whether the above or the left neighbour is smooth), are table logic that stays
  * with the encoder.
  *
- * Out of scope: palette, CfL (svt_cfl_predict_*, the luma sub-sampling, svt_subtract_average), intra-BC, the inter-intra blend, 12-bit, the
- * availability derivation above, pointer-level leaves for the intra rtcd entries (one call per block; the batch is the boundary), and
- * svt_hip_tpl_dispense at TPL level 1 (its open-loop path upsamples the edges but predicts with upsample 0: another contract).
+ * Out of scope: palette, intra-BC, the inter-intra blend, 12-bit, the availability derivation above, pointer-level leaves for the intra rtcd
+ * entries (one call per block; the batch is the boundary), and svt_hip_tpl_dispense at TPL level 1 (its open-loop path upsamples the edges but
+ * predicts with upsample 0: another contract).  Chroma-from-luma is svt_hip_cfl_pred_batch (svt_hip_cfl.h), which reads the DC plane this batch
+ * writes.
  *
  * Defined where the reference is not.  A job gets status 0xFF, writes nothing else and reads nothing, when: tx_size > 18 or mode > 12; a
  * directional mode (1..8) with |angle_delta| > 3; filter_intra_mode > 5; a filter-intra job (filter_intra_mode < 5) with a side > 32 or

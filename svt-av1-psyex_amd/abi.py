@@ -405,3 +405,35 @@ class IntraPredDesc(C.Structure):  # SvtHipIntraPredDesc
 INTRA_PRED_JOB_DTYPE = [("dst_offset", "<u4"), ("nbr_x", "<i4"), ("nbr_y", "<i4"), ("tx_size", "u1"), ("mode", "u1"), ("angle_delta", "i1"),
                         ("filter_intra_mode", "u1"), ("n_top_px", "u1"), ("n_topright_px", "u1"), ("n_left_px", "u1"), ("n_bottomleft_px", "u1"),
                         ("filt_type", "u1"), ("reserved", "u1", (3,))]
+
+
+# ---- include/svt_hip_cfl.h ----
+CFL_SLOTS = 33
+CFL_OK, CFL_UNDEFINED = 0, 0xFF
+CFL_PICK_TRUNCATED, CFL_PICK_UNDEFINED = 1, 0xFF
+CFL_MAX_MODE_COST = 13754408443200 * 8
+
+
+class CflPredJob(C.Structure):  # SvtHipCflPredJob
+    _fields_ = [("luma_x", C.c_int32), ("luma_y", C.c_int32), ("dc_offset", C.c_uint32 * 2), ("dst_offset", C.c_uint32 * 2)]
+
+
+class CflPlane(C.Structure):  # SvtHipCflPlane
+    _fields_ = [("dc", C.c_void_p), ("dc_stride", C.c_uint32), ("dst_stride", C.c_uint32), ("dc_samples", C.c_uint64), ("dst", C.c_void_p),
+                ("dst_samples", C.c_uint64)]
+
+
+class CflPredDesc(C.Structure):  # SvtHipCflPredDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("width", C.c_uint8), ("height", C.c_uint8), ("n_alpha", C.c_uint8), ("n_jobs", C.c_uint32),
+                ("alpha_q3", C.c_int8 * CFL_SLOTS), ("reserved", C.c_uint8 * 7), ("luma", C.c_void_p), ("luma_stride", C.c_uint32),
+                ("luma_width", C.c_uint32), ("luma_height", C.c_uint32), ("slot_stride", C.c_uint32), ("plane", CflPlane * 2), ("jobs", C.c_void_p),
+                ("status", C.c_void_p), ("ac", C.c_void_p)]
+
+
+class CflPickDesc(C.Structure):  # SvtHipCflPickDesc
+    _fields_ = [("n_blocks", C.c_uint32), ("lambda_", C.c_uint32), ("itr_th", C.c_uint8), ("n_mag", C.c_uint8), ("reserved", C.c_uint8 * 2),
+                ("dist_stride", C.c_uint32), ("bits", C.c_void_p), ("dist", C.c_void_p), ("mode_bits", C.c_void_p), ("alpha_fac_bits", C.c_void_p),
+                ("best_rd", C.c_void_p), ("cfl_alpha_idx", C.c_void_p), ("cfl_alpha_signs", C.c_void_p), ("status", C.c_void_p)]
+
+
+CFL_PRED_JOB_DTYPE = [("luma_x", "<i4"), ("luma_y", "<i4"), ("dc_offset", "<u4", (2,)), ("dst_offset", "<u4", (2,))]
