@@ -437,3 +437,76 @@ class CflPickDesc(C.Structure):  # SvtHipCflPickDesc
 
 
 CFL_PRED_JOB_DTYPE = [("luma_x", "<i4"), ("luma_y", "<i4"), ("dc_offset", "<u4", (2,)), ("dst_offset", "<u4", (2,))]
+
+
+# ---- include/svt_hip_warp.h ----
+WARP_MAX_REFS = 8
+WARP_NO_REF = 0xFF
+WARP_MODEL0_FROM_ARRAY, WARP_MODEL1_FROM_ARRAY = 1, 2
+WARP_MV_FROM_ARRAY = 1
+WARP_OK, WARP_NO_MODEL, WARP_UNDEFINED = 0, 0xFE, 0xFF
+WARP_ROTZOOM, WARP_AFFINE = 2, 3
+WARP_MAX_SAMPLES = 8
+
+
+class WarpModel(C.Structure):  # SvtHipWarpModel
+    _fields_ = [("wmmat", C.c_int32 * 6), ("alpha", C.c_int16), ("beta", C.c_int16), ("gamma", C.c_int16), ("delta", C.c_int16), ("wmtype", C.c_uint8),
+                ("valid", C.c_uint8), ("num_samples", C.c_uint16), ("reserved", C.c_uint32)]
+
+
+class WarpRef(C.Structure):  # SvtHipWarpRef
+    _fields_ = [("plane", C.c_void_p), ("stride", C.c_uint32), ("org_x", C.c_uint16), ("org_y", C.c_uint16), ("width", C.c_uint16), ("height", C.c_uint16),
+                ("rows", C.c_uint16), ("reserved", C.c_uint16)]
+
+
+class WarpPredJob(C.Structure):  # SvtHipWarpPredJob
+    _fields_ = [("dst_offset", C.c_uint32), ("p_col", C.c_int16), ("p_row", C.c_int16), ("width", C.c_uint8), ("height", C.c_uint8), ("ref", C.c_uint8 * 2),
+                ("flags", C.c_uint8), ("comp_mode", C.c_uint8), ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8), ("model_index", C.c_uint32 * 2),
+                ("model", WarpModel * 2)]
+
+
+class WarpPredDesc(C.Structure):  # SvtHipWarpPredDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("ss_x", C.c_uint8), ("ss_y", C.c_uint8), ("n_refs", C.c_uint8), ("n_jobs", C.c_uint32),
+                ("refs", WarpRef * WARP_MAX_REFS), ("dst", C.c_void_p), ("dst_stride", C.c_uint32), ("reserved", C.c_uint32), ("dst_samples", C.c_uint64),
+                ("jobs", C.c_void_p), ("models", C.c_void_p), ("n_models", C.c_uint32), ("reserved2", C.c_uint32), ("status", C.c_void_p)]
+
+
+class WarpModelJob(C.Structure):  # SvtHipWarpModelJob
+    _fields_ = [("pts", C.c_int32 * 16), ("pts_inref", C.c_int32 * 16), ("blk_org_x", C.c_uint16), ("blk_org_y", C.c_uint16), ("bwidth", C.c_uint8),
+                ("bheight", C.c_uint8), ("n_samples", C.c_uint8), ("flags", C.c_uint8), ("mv", C.c_int16 * 2), ("mv_index", C.c_uint32)]
+
+
+class WarpModelDesc(C.Structure):  # SvtHipWarpModelDesc
+    _fields_ = [("n_jobs", C.c_uint32), ("shut_approx", C.c_uint8), ("reserved", C.c_uint8), ("lower_band_th", C.c_uint16), ("upper_band_th", C.c_uint16),
+                ("reserved2", C.c_uint16), ("n_mvs", C.c_uint32), ("jobs", C.c_void_p), ("mv_array", C.c_void_p), ("models", C.c_void_p), ("status", C.c_void_p)]
+
+
+WM_START_FROM_ARRAY = 1
+WM_MAX_ITERATIONS = 16
+WM_NO_COST = 0x7FFFFFFF  # best_cost when no position had a valid fit (INT_MAX)
+
+
+class WmRefineJob(C.Structure):  # SvtHipWmRefineJob
+    _fields_ = [("pts", C.c_int32 * 16), ("pts_inref", C.c_int32 * 16), ("src_offset", C.c_uint32), ("blk_org_x", C.c_uint16), ("blk_org_y", C.c_uint16),
+                ("bwidth", C.c_uint8), ("bheight", C.c_uint8), ("n_samples", C.c_uint8), ("flags", C.c_uint8), ("start_mv", C.c_int16 * 2),
+                ("pred_mv", C.c_int16 * 2), ("mv_index", C.c_uint32), ("ref", C.c_uint8), ("reserved", C.c_uint8 * 7)]
+
+
+class WmRefineDesc(C.Structure):  # SvtHipWmRefineDesc
+    _fields_ = [("n_jobs", C.c_uint32), ("iterations", C.c_uint8), ("refine_diag", C.c_uint8), ("mv_prec_shift", C.c_uint8), ("shut_approx", C.c_uint8),
+                ("lower_band_th", C.c_uint16), ("upper_band_th", C.c_uint16), ("approx_inter_rate", C.c_uint8), ("n_refs", C.c_uint8),
+                ("waves_per_job", C.c_uint8), ("reserved", C.c_uint8), ("error_per_bit", C.c_int32), ("src_stride", C.c_uint32), ("src", C.c_void_p),
+                ("src_samples", C.c_uint64), ("refs", WarpRef * WARP_MAX_REFS), ("jobs", C.c_void_p), ("mv_array", C.c_void_p), ("n_mvs", C.c_uint32),
+                ("reserved2", C.c_uint32), ("mvjcost", C.c_void_p), ("mvcost", C.c_void_p * 2), ("best_mv", C.c_void_p), ("best_cost", C.c_void_p),
+                ("n_checked", C.c_void_p), ("status", C.c_void_p)]
+
+
+WM_REFINE_JOB_DTYPE = [("pts", "<i4", (16,)), ("pts_inref", "<i4", (16,)), ("src_offset", "<u4"), ("blk_org_x", "<u2"), ("blk_org_y", "<u2"), ("bwidth", "u1"),
+                       ("bheight", "u1"), ("n_samples", "u1"), ("flags", "u1"), ("start_mv", "<i2", (2,)), ("pred_mv", "<i2", (2,)), ("mv_index", "<u4"),
+                       ("ref", "u1"), ("reserved", "u1", (7,))]
+WARP_MODEL_DTYPE = [("wmmat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"), ("wmtype", "u1"), ("valid", "u1"),
+                    ("num_samples", "<u2"), ("reserved", "<u4")]
+WARP_PRED_JOB_DTYPE = [("dst_offset", "<u4"), ("p_col", "<i2"), ("p_row", "<i2"), ("width", "u1"), ("height", "u1"), ("ref", "u1", (2,)), ("flags", "u1"),
+                       ("comp_mode", "u1"), ("fwd_offset", "u1"), ("bck_offset", "u1"), ("model_index", "<u4", (2,)), ("model", WARP_MODEL_DTYPE, (2,))]
+WARP_MODEL_JOB_DTYPE = [("pts", "<i4", (16,)), ("pts_inref", "<i4", (16,)), ("blk_org_x", "<u2"), ("blk_org_y", "<u2"), ("bwidth", "u1"), ("bheight", "u1"),
+                        ("n_samples", "u1"), ("flags", "u1"), ("mv", "<i2", (2,)), ("mv_index", "<u4")]

@@ -34,5 +34,12 @@ __device__ __forceinline__ int mv_err_cost(int16_t row, int16_t col, const MvCos
     }
 }
 
+// svt_aom_mv_err_cost_light (Codec/av1me.c:229-235): what the warped-motion refinement (warp_kernel.hip) adds instead when approx_inter_rate is
+// set; svt_aom_mv_err_cost (:244-252) itself is the SVT_HIP_MV_COST_ENTROPY case above
+__device__ __forceinline__ int mv_err_cost_light(int row, int col, const SvtHipMv &ref_mv) {
+    const int dr = row - ref_mv.row, dc = col - ref_mv.col; // int arithmetic on the int16 fields: no wrap
+    return (int)(1296u + 50u * (uint32_t)((dr < 0 ? -dr : dr) + (dc < 0 ? -dc : dc)));
+}
+
 } // namespace
 #endif

@@ -1,0 +1,631 @@
+// warp_kernel.hip -- warped motion on gfx950: svt_hip_warp_pred_batch, the 8x8-tile warp filter into the plane svt_hip_rd_batch reads, and
+// svt_hip_warp_model_batch, the least-squares fit of the local-warp model for an MV that is already on the device, and svt_hip_wm_refine_batch,
+// the MV refinement that runs both up to 129 times per block.
+//
+// Reference functions restated (Source/Lib/Codec):
+//   svt_av1_warp_plane, svt_warp_plane, svt_highbd_warp_plane, svt_av1_warp_affine_c, svt_av1_highbd_warp_affine_c   warped_motion.c:569-895
+//   plane_warped_motion_prediction (the ConvolveParams: round_0 3, round_1 7 for a compound)                          enc_inter_prediction.c:2040-2145
+//   svt_aom_warped_motion_parameters (from the MV on), svt_aom_select_samples                                          adaptive_mv_pred.c:1736-1754, warped_motion.c:924-972
+//   find_affine_int, svt_find_projection, svt_get_shear_params, is_affine_shear_allowed, resolve_divisor_64 / _32      warped_motion.c:320-483, 898-921
+//   get_mult_shift_diag / _ndiag (USE_LIMITED_PREC_MULT 0)                                                              warped_motion.c:277-289
+//   svt_aom_wm_motion_refinement (the search loop), svt_aom_variance{W}x{H}_c, svt_aom_mv_err_cost / _light           mode_decision.c:2082-2204, C_DEFAULT/variance.c, av1me.c:229-252
+//
+// Lay-out of the prediction: a workgroup of four waves per job, a wave per 8x8 tile at a time, a lane per output sample.  The tile's geometry
+// (ix4, iy4, sx4, sy4) comes from the job alone and lives in scalar registers.  The 15 x 15 source window (every coordinate clamped to the
+// picture) is staged into the wave's own LDS once, four samples per lane; the horizontal filter runs as two passes of 8 x 8 lanes over it and
+// leaves its 15 x 8 intermediate (at most 15 bits) in LDS; the vertical filter reads a column of eight from there.  Only wave_sync() orders the
+// traffic: no wave waits for another.  The filter of a lane differs per lane and per row, so the 193 x 8 table is read with one 16-byte load per
+// lane from constant memory, where its 3 KB stay in the vector cache; an LDS copy would cost every workgroup a fill and a barrier it cannot
+// amortise over one job.  A compound job runs both references per tile and keeps the first result in a register.
+//
+// The fit is one lane per job, 32- and 64-bit integer code.  svt_aom_select_samples only reorders: the least-squares sums do not depend on the
+// order, so the kept samples are summed where they lie, and no array is indexed by a register.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <type_traits>
+#include "svt_hip_internal.h"
+#include "../../include/svt_hip_warp.h"
+#include "wave_ops.h"
+#include "mv_cost.h"
+
+namespace {
+
+constexpr int kWaves = 4;
+
+// Warped_Filters of the AV1 specification (7.11.3.5), 1/64 sample steps.  Rows 0..63 (offsets [-1, 0)) are the six taps of kSide at positions
+// 0..5, rows 128..191 (offsets [1, 2)) the same six at positions 2..7 -- but for row 128, which is kRow128 --, rows 64..127 (offsets [0, 1)) the
+// eight taps of kMid, row 192 repeats 191.
+constexpr int8_t kRow128[8] = {0, 0, 0, 1, 127, 0, 0, 0};
+constexpr int8_t kSide[64][6] = {
+    {0, 0, 127, 1, 0, 0},      {0, -1, 127, 2, 0, 0},     {1, -3, 127, 4, -1, 0},    {1, -4, 126, 6, -2, 1},    {1, -5, 126, 8, -3, 1},
+    {1, -6, 125, 11, -4, 1},   {1, -7, 124, 13, -4, 1},   {2, -8, 123, 15, -5, 1},   {2, -9, 122, 18, -6, 1},   {2, -10, 121, 20, -6, 1},
+    {2, -11, 120, 22, -7, 2},  {2, -12, 119, 25, -8, 2},  {3, -13, 117, 27, -8, 2},  {3, -13, 116, 29, -9, 2},  {3, -14, 114, 32, -10, 3},
+    {3, -15, 113, 35, -10, 2}, {3, -15, 111, 37, -11, 3}, {3, -16, 109, 40, -11, 3}, {3, -16, 108, 42, -12, 3}, {4, -17, 106, 45, -13, 3},
+    {4, -17, 104, 47, -13, 3}, {4, -17, 102, 50, -14, 3}, {4, -17, 100, 52, -14, 3}, {4, -18, 98, 55, -15, 4},  {4, -18, 96, 58, -15, 3},
+    {4, -18, 94, 60, -16, 4},  {4, -18, 91, 63, -16, 4},  {4, -18, 89, 65, -16, 4},  {4, -18, 87, 68, -17, 4},  {4, -18, 85, 70, -17, 4},
+    {4, -18, 82, 73, -17, 4},  {4, -18, 80, 75, -17, 4},  {4, -18, 78, 78, -18, 4},  {4, -17, 75, 80, -18, 4},  {4, -17, 73, 82, -18, 4},
+    {4, -17, 70, 85, -18, 4},  {4, -17, 68, 87, -18, 4},  {4, -16, 65, 89, -18, 4},  {4, -16, 63, 91, -18, 4},  {4, -16, 60, 94, -18, 4},
+    {3, -15, 58, 96, -18, 4},  {4, -15, 55, 98, -18, 4},  {3, -14, 52, 100, -17, 4}, {3, -14, 50, 102, -17, 4}, {3, -13, 47, 104, -17, 4},
+    {3, -13, 45, 106, -17, 4}, {3, -12, 42, 108, -16, 3}, {3, -11, 40, 109, -16, 3}, {3, -11, 37, 111, -15, 3}, {2, -10, 35, 113, -15, 3},
+    {3, -10, 32, 114, -14, 3}, {2, -9, 29, 116, -13, 3},  {2, -8, 27, 117, -13, 3},  {2, -8, 25, 119, -12, 2},  {2, -7, 22, 120, -11, 2},
+    {1, -6, 20, 121, -10, 2},  {1, -6, 18, 122, -9, 2},   {1, -5, 15, 123, -8, 2},   {1, -4, 13, 124, -7, 1},   {1, -4, 11, 125, -6, 1},
+    {1, -3, 8, 126, -5, 1},    {1, -2, 6, 126, -4, 1},    {0, -1, 4, 127, -3, 1},    {0, 0, 2, 127, -1, 0}};
+constexpr int8_t kMid[64][8] = {
+    {0, 0, 0, 127, 1, 0, 0, 0},         {0, 0, -1, 127, 2, 0, 0, 0},        {0, 1, -3, 127, 4, -2, 1, 0},       {0, 1, -5, 127, 6, -2, 1, 0},
+    {0, 2, -6, 126, 8, -3, 1, 0},       {-1, 2, -7, 126, 11, -4, 2, -1},    {-1, 3, -8, 125, 13, -5, 2, -1},    {-1, 3, -10, 124, 16, -6, 3, -1},
+    {-1, 4, -11, 123, 18, -7, 3, -1},   {-1, 4, -12, 122, 20, -7, 3, -1},   {-1, 4, -13, 121, 23, -8, 3, -1},   {-2, 5, -14, 120, 25, -9, 4, -1},
+    {-1, 5, -15, 119, 27, -10, 4, -1},  {-1, 5, -16, 118, 30, -11, 4, -1},  {-2, 6, -17, 116, 33, -12, 5, -1},  {-2, 6, -17, 114, 35, -12, 5, -1},
+    {-2, 6, -18, 113, 38, -13, 5, -1},  {-2, 7, -19, 111, 41, -14, 6, -2},  {-2, 7, -19, 110, 43, -15, 6, -2},  {-2, 7, -20, 108, 46, -15, 6, -2},
+    {-2, 7, -20, 106, 49, -16, 6, -2},  {-2, 7, -21, 104, 51, -16, 7, -2},  {-2, 7, -21, 102, 54, -17, 7, -2},  {-2, 8, -21, 100, 56, -18, 7, -2},
+    {-2, 8, -22, 98, 59, -18, 7, -2},   {-2, 8, -22, 96, 62, -19, 7, -2},   {-2, 8, -22, 94, 64, -19, 7, -2},   {-2, 8, -22, 91, 67, -20, 8, -2},
+    {-2, 8, -22, 89, 69, -20, 8, -2},   {-2, 8, -22, 87, 72, -21, 8, -2},   {-2, 8, -21, 84, 74, -21, 8, -2},   {-2, 8, -22, 82, 77, -21, 8, -2},
+    {-2, 8, -21, 79, 79, -21, 8, -2},   {-2, 8, -21, 77, 82, -22, 8, -2},   {-2, 8, -21, 74, 84, -21, 8, -2},   {-2, 8, -21, 72, 87, -22, 8, -2},
+    {-2, 8, -20, 69, 89, -22, 8, -2},   {-2, 8, -20, 67, 91, -22, 8, -2},   {-2, 7, -19, 64, 94, -22, 8, -2},   {-2, 7, -19, 62, 96, -22, 8, -2},
+    {-2, 7, -18, 59, 98, -22, 8, -2},   {-2, 7, -18, 56, 100, -21, 8, -2},  {-2, 7, -17, 54, 102, -21, 7, -2},  {-2, 7, -16, 51, 104, -21, 7, -2},
+    {-2, 6, -16, 49, 106, -20, 7, -2},  {-2, 6, -15, 46, 108, -20, 7, -2},  {-2, 6, -15, 43, 110, -19, 7, -2},  {-2, 6, -14, 41, 111, -19, 7, -2},
+    {-1, 5, -13, 38, 113, -18, 6, -2},  {-1, 5, -12, 35, 114, -17, 6, -2},  {-1, 5, -12, 33, 116, -17, 6, -2},  {-1, 4, -11, 30, 118, -16, 5, -1},
+    {-1, 4, -10, 27, 119, -15, 5, -1},  {-1, 4, -9, 25, 120, -14, 5, -2},   {-1, 3, -8, 23, 121, -13, 4, -1},   {-1, 3, -7, 20, 122, -12, 4, -1},
+    {-1, 3, -7, 18, 123, -11, 4, -1},   {-1, 3, -6, 16, 124, -10, 3, -1},   {-1, 2, -5, 13, 125, -8, 3, -1},    {-1, 2, -4, 11, 126, -7, 2, -1},
+    {0, 1, -3, 8, 126, -6, 2, 0},       {0, 1, -2, 6, 127, -5, 1, 0},       {0, 1, -2, 4, 127, -3, 1, 0},       {0, 0, 0, 2, 127, -1, 0, 0}};
+
+struct WarpTables {
+    int16_t  filter[193][8]; // 16-byte rows
+    uint16_t div_lut[257];   // round(2^22 / (256 + i)): DIV_LUT_PREC_BITS 14 over DIV_LUT_BITS 8
+};
+constexpr WarpTables make_tables() {
+    WarpTables t{};
+    for (int i = 0; i < 64; i++) {
+        for (int m = 0; m < 6; m++) { t.filter[i][m] = kSide[i][m]; t.filter[128 + i][m + 2] = kSide[i][m]; }
+        for (int m = 0; m < 8; m++) t.filter[64 + i][m] = kMid[i][m];
+    }
+    for (int m = 0; m < 8; m++) t.filter[128][m] = kRow128[m];
+    for (int m = 0; m < 8; m++) t.filter[192][m] = t.filter[191][m];
+    for (int i = 0; i <= 256; i++) t.div_lut[i] = (uint16_t)(((1u << 22) + (256u + (unsigned)i) / 2u) / (256u + (unsigned)i));
+    return t;
+}
+constexpr WarpTables                                       kTablesHost = make_tables();
+__constant__ __attribute__((aligned(16))) const WarpTables kTables     = make_tables();
+
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
+
+__device__ __forceinline__ bool is_warp_size(int w, int h) { // the 17 block sizes with both dimensions >= 8
+    const bool pw = w >= 8 && w <= 128 && (w & (w - 1)) == 0, ph = h >= 8 && h <= 128 && (h & (h - 1)) == 0;
+    if (!pw || !ph) return false;
+    const int big = w > h ? w : h, small = w > h ? h : w;
+    return big == small || big == 2 * small || (big == 4 * small && big <= 64);
+}
+// is_affine_shear_allowed, and what the filter takes for granted: multiples of 1 << WARP_PARAM_REDUCE_BITS
+__device__ __forceinline__ bool shear_allowed(int alpha, int beta, int gamma, int delta) {
+    if (((alpha | beta | gamma | delta) & 63) != 0) return false;
+    return 4 * iabs(alpha) + 7 * iabs(beta) < (1 << 16) && 4 * iabs(gamma) + 4 * iabs(delta) < (1 << 16);
+}
+
+// the eight taps of the filter at offset s (1/65536 sample): ROUND_POWER_OF_TWO(s, WARPEDDIFF_PREC_BITS) + WARPEDPIXEL_PREC_SHIFTS, which the
+// shear test keeps inside [0, 192]; the clamp costs one instruction and keeps the load inside the table whatever the job says
+__device__ __forceinline__ void load_taps(int s, int *f) {
+    const int   offs = clampi(((s + 512) >> 10) + 64, 0, 192);
+    const uint4 t    = *(const uint4 *)&kTables.filter[offs][0];
+    f[0] = (int)(int16_t)(t.x & 0xFFFFu); f[1] = (int)t.x >> 16; f[2] = (int)(int16_t)(t.y & 0xFFFFu); f[3] = (int)t.y >> 16;
+    f[4] = (int)(int16_t)(t.z & 0xFFFFu); f[5] = (int)t.z >> 16; f[6] = (int)(int16_t)(t.w & 0xFFFFu); f[7] = (int)t.w >> 16;
+}
+
+struct Model { // wave-uniform
+    int mat[6], alpha, beta, gamma, delta;
+};
+
+// One 8x8 tile of one reference: the vertical filter's sum of this lane's sample, rounded by `reduce_vert`
+template <bool HBD>
+__device__ __forceinline__ int warp_tile(const SvtHipWarpRef &r, const Model &m, int jx, int iy, int ss_x, int ss_y, int reduce_vert, uint16_t *s_src,
+                                         uint16_t *s_mid, int lane) {
+    using Px = typename std::conditional<HBD, uint16_t, uint8_t>::type;
+    constexpr int bd = HBD ? 10 : 8;
+    // the tile's centre, projected: 32-bit arithmetic as the reference's
+    const uint32_t src_x = (uint32_t)(jx + 4) << ss_x, src_y = (uint32_t)(iy + 4) << ss_y;
+    const int x4  = (int)((uint32_t)m.mat[2] * src_x + (uint32_t)m.mat[3] * src_y + (uint32_t)m.mat[0]) >> ss_x;
+    const int y4  = (int)((uint32_t)m.mat[4] * src_x + (uint32_t)m.mat[5] * src_y + (uint32_t)m.mat[1]) >> ss_y;
+    const int ix4 = x4 >> 16, iy4 = y4 >> 16;
+    const int sx4 = ((x4 & 0xFFFF) - 4 * (m.alpha + m.beta)) & ~63, sy4 = ((y4 & 0xFFFF) - 4 * (m.gamma + m.delta)) & ~63;
+
+    // the window: rows iy4 - 7 .. iy4 + 7, columns ix4 - 7 .. ix4 + 7, every coordinate clamped to the picture
+    const Px *plane = (const Px *)r.plane + (size_t)r.org_y * r.stride + r.org_x;
+    const int max_x = (int)r.width - 1, max_y = (int)r.height - 1;
+    {
+        const int wc = lane & 15, x = clampi(ix4 + wc - 7, 0, max_x);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int wr = (lane >> 4) + 4 * i;
+            if (wr < 15) s_src[wr * 16 + wc] = (uint16_t)plane[(size_t)clampi(iy4 + wr - 7, 0, max_y) * r.stride + (size_t)x];
+        }
+    }
+    wave_sync();
+    const int c = lane & 7, rr = lane >> 3;
+    // horizontal: row k = wr - 7, column l = c - 4; sx = sx4 + beta * (k + 4) + alpha * (l + 4)
+#pragma unroll
+    for (int p = 0; p < 2; p++) {
+        const int wr = rr + 8 * p;
+        if (wr < 15) {
+            int f[8];
+            load_taps(sx4 + m.beta * (wr - 3) + m.alpha * c, f);
+            int sum = 1 << (bd + 6);
+#pragma unroll
+            for (int t = 0; t < 8; t++) sum += (int)s_src[wr * 16 + c + t] * f[t];
+            s_mid[wr * 8 + c] = (uint16_t)((sum + 4) >> 3); // round_0 = 3; below 1 << (bd + 5)
+        }
+    }
+    wave_sync();
+    // vertical: row k = rr - 4, column l = c - 4; sy = sy4 + delta * (k + 4) + gamma * (l + 4)
+    int f[8];
+    load_taps(sy4 + m.delta * rr + m.gamma * c, f);
+    int sum = 1 << (bd + 11);
+#pragma unroll
+    for (int t = 0; t < 8; t++) sum += (int)s_mid[(rr + t) * 8 + c] * f[t];
+    wave_sync(); // the next tile's window and intermediate may follow
+    return (sum + ((1 << reduce_vert) >> 1)) >> reduce_vert;
+}
+
+template <bool HBD> __global__ __launch_bounds__(64 * kWaves) void warp_pred_kernel(const SvtHipWarpPredDesc d) {
+    using Px = typename std::conditional<HBD, uint16_t, uint8_t>::type;
+    __shared__ uint16_t s_src[kWaves][15 * 16];
+    __shared__ uint16_t s_mid[kWaves][15 * 8];
+    constexpr int bd = HBD ? 10 : 8, px_max = (1 << bd) - 1;
+    const int      lane = (int)(threadIdx.x & 63u);
+    const int      wave = uniform((int)(threadIdx.x >> 6));
+    const uint32_t job  = blockIdx.x;
+    if (job >= d.n_jobs) return;
+    const SvtHipWarpPredJob *jp = d.jobs + job;
+    const int  w = jp->width, h = jp->height, flags = jp->flags;
+    const int  ref0 = jp->ref[0], ref1 = jp->ref[1];
+    const bool comp = ref1 != SVT_HIP_WARP_NO_REF;
+    const int  comp_mode = jp->comp_mode, fwd = jp->fwd_offset, bck = jp->bck_offset;
+    const bool first = wave == 0 && lane == 0;
+
+    bool ok = is_warp_size(w, h) && ref0 < d.n_refs;
+    if (comp) {
+        ok = ok && ref1 < d.n_refs && comp_mode <= 1;
+        if (comp_mode == 1) // quant_dist_lookup_table: {9,7} {11,5} {12,4} {13,3} and their mirrors
+            ok = ok && fwd + bck == 16 && (fwd == 9 || fwd == 11 || fwd == 12 || fwd == 13 || fwd == 7 || fwd == 5 || fwd == 4 || fwd == 3);
+    }
+    const bool arr0 = (flags & SVT_HIP_WARP_MODEL0_FROM_ARRAY) != 0, arr1 = comp && (flags & SVT_HIP_WARP_MODEL1_FROM_ARRAY) != 0;
+    if (arr0) ok = ok && d.models != nullptr && jp->model_index[0] < d.n_models;
+    if (arr1) ok = ok && d.models != nullptr && jp->model_index[1] < d.n_models;
+    ok = ok && (uint64_t)jp->dst_offset + (uint64_t)(h > 0 ? h - 1 : 0) * d.dst_stride + (uint64_t)w <= d.dst_samples;
+    if (!ok) {
+        if (first) d.status[job] = SVT_HIP_WARP_UNDEFINED;
+        return;
+    }
+    const SvtHipWarpModel *mp0 = arr0 ? d.models + jp->model_index[0] : &jp->model[0];
+    const SvtHipWarpModel *mp1 = !comp ? mp0 : (arr1 ? d.models + jp->model_index[1] : &jp->model[1]);
+    if ((arr0 && mp0->valid == 0) || (arr1 && mp1->valid == 0)) {
+        if (first) d.status[job] = SVT_HIP_WARP_NO_MODEL;
+        return;
+    }
+    Model m[2];
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const SvtHipWarpModel *mp = r ? mp1 : mp0;
+        const int type = mp->wmtype;
+#pragma unroll
+        for (int i = 0; i < 6; i++) m[r].mat[i] = uniform(mp->wmmat[i]);
+        if (type == SVT_HIP_WARP_ROTZOOM) { m[r].mat[5] = m[r].mat[2]; m[r].mat[4] = (int)(0u - (uint32_t)m[r].mat[3]); }
+        m[r].alpha = uniform(mp->alpha); m[r].beta = uniform(mp->beta); m[r].gamma = uniform(mp->gamma); m[r].delta = uniform(mp->delta);
+        ok = ok && (type == SVT_HIP_WARP_ROTZOOM || type == SVT_HIP_WARP_AFFINE) && shear_allowed(m[r].alpha, m[r].beta, m[r].gamma, m[r].delta);
+    }
+    if (!ok) {
+        if (first) d.status[job] = SVT_HIP_WARP_UNDEFINED;
+        return;
+    }
+
+    const SvtHipWarpRef r0 = d.refs[ref0], r1 = d.refs[comp ? ref1 : ref0];
+    const int ss_x = d.ss_x, ss_y = d.ss_y, p_col = jp->p_col, p_row = jp->p_row;
+    const int log2_tx = 31 - __builtin_clz((unsigned)(w >> 3)), n_tiles = (w >> 3) * (h >> 3);
+    Px *const dst = (Px *)d.dst + (size_t)jp->dst_offset;
+    const int c = lane & 7, rr = lane >> 3;
+    for (int t = wave; t < n_tiles; t += kWaves) {
+        const int ty = t >> log2_tx, tx = t & ((1 << log2_tx) - 1);
+        const int jx = p_col + 8 * tx, iy = p_row + 8 * ty;
+        int v;
+        if (!comp) {
+            v = warp_tile<HBD>(r0, m[0], jx, iy, ss_x, ss_y, 11, s_src[wave], s_mid[wave], lane) - (1 << (bd - 1)) - (1 << bd);
+        } else {
+            const int a = warp_tile<HBD>(r0, m[0], jx, iy, ss_x, ss_y, 7, s_src[wave], s_mid[wave], lane);
+            const int b = warp_tile<HBD>(r1, m[1], jx, iy, ss_x, ss_y, 7, s_src[wave], s_mid[wave], lane);
+            int tmp = comp_mode ? (a * fwd + b * bck) >> 4 : (a + b) >> 1;
+            tmp -= (1 << (bd + 4)) + (1 << (bd + 3)); // offset_bits - round_1 and one below, offset_bits = bd + 2 * FILTER_BITS - round_0
+            v = (tmp + 8) >> 4;                       // round_bits = 2 * FILTER_BITS - round_0 - round_1
+        }
+        dst[(size_t)(8 * ty + rr) * d.dst_stride + (size_t)(8 * tx + c)] = (Px)clampi(v, 0, px_max);
+    }
+    if (first) d.status[job] = SVT_HIP_WARP_OK;
+}
+
+// ---- the fit ----
+__device__ __forceinline__ int msb64(uint64_t v) { return 63 - __builtin_clzll(v); }
+__device__ __forceinline__ int64_t round_shift_signed_64(int64_t v, int n) { // ROUND_POWER_OF_TWO_SIGNED_64
+    const int64_t half = ((int64_t)1 << n) >> 1;
+    return v < 0 ? -((-v + half) >> n) : (v + half) >> n;
+}
+__device__ __forceinline__ int round_shift_signed(int v, int n) { // ROUND_POWER_OF_TWO_SIGNED
+    const int half = (1 << n) >> 1;
+    return v < 0 ? -((-v + half) >> n) : (v + half) >> n;
+}
+// resolve_divisor_64 (resolve_divisor_32 is the same on a narrower argument): 1 / D = y / 2^shift
+__device__ __forceinline__ int resolve_divisor(uint64_t D, int *shift) {
+    const int     s = msb64(D);
+    const int64_t e = (int64_t)(D - ((uint64_t)1 << s));
+    const int64_t f = s > 8 ? (e + (((int64_t)1 << (s - 8)) >> 1)) >> (s - 8) : e << (8 - s);
+    *shift = s + 14;
+    return kTables.div_lut[f];
+}
+__device__ __forceinline__ int clamp64(int64_t v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
+__device__ __forceinline__ int reduce_shear(int v) { return (int16_t)(round_shift_signed((int16_t)clampi(v, INT16_MIN, INT16_MAX), 6) * 64); }
+
+// What the two jobs that fit a model share: the samples and the block (the head of SvtHipWarpModelJob and of SvtHipWmRefineJob)
+struct FitInput {
+    const int32_t *pts, *pts_inref;
+    int n, bw, bh, org_x, org_y;
+    bool shut_approx;
+    int  lower_band_th, upper_band_th;
+};
+
+// The MV-dependent half of svt_aom_warped_motion_parameters for the MV (mvy, mvx): the record as svt_hip_warp_model_batch writes it
+__device__ __forceinline__ SvtHipWarpModel fit_model(const FitInput &in, int mvy, int mvx) {
+    const int32_t *const pts = in.pts, *const pts_inref = in.pts_inref;
+    const int bw = in.bw, bh = in.bh, n = in.n;
+    SvtHipWarpModel out;
+    memset(&out, 0, sizeof(out));
+    out.wmtype = SVT_HIP_WARP_AFFINE;
+    bool valid = n > 0;
+    if (valid) {
+        // svt_aom_select_samples: which samples stay (bit i), and how many
+        const int thresh = clampi(bw > bh ? bw : bh, 16, 112);
+        uint32_t  keep = 0;
+        int       np = 0;
+#pragma unroll
+        for (int i = 0; i < SVT_HIP_WARP_MAX_SAMPLES; i++) {
+            if (i < n) {
+                const int mvd = iabs(pts_inref[2 * i] - pts[2 * i] - mvx) + iabs(pts_inref[2 * i + 1] - pts[2 * i + 1] - mvy);
+                if (mvd <= thresh) { keep |= 1u << i; np++; }
+            }
+        }
+        if (n == 1 || np == 0) { keep = 1; np = 1; } // a single sample is not selected; none kept: the first one, untouched
+        out.num_samples = (uint16_t)np;
+
+        // find_affine_int
+        const int rsuy = bh / 2 - 1, rsux = bw / 2 - 1, suy = rsuy * 8, sux = rsux * 8, duy = suy + mvy, dux = sux + mvx;
+        const int isuy = (in.org_y >> 2) * 4 + rsuy, isux = (in.org_x >> 2) * 4 + rsux;
+        int32_t   a00 = 0, a01 = 0, a11 = 0, bx0 = 0, bx1 = 0, by0 = 0, by1 = 0;
+#pragma unroll
+        for (int i = 0; i < SVT_HIP_WARP_MAX_SAMPLES; i++) {
+            if (keep & (1u << i)) {
+                const int dx = pts_inref[2 * i] - dux, dy = pts_inref[2 * i + 1] - duy, sx = pts[2 * i] - sux, sy = pts[2 * i + 1] - suy;
+                if (iabs(sx - dx) < 256 && iabs(sy - dy) < 256) { // LS_MV_MAX; LS_SQUARE, LS_PRODUCT1, LS_PRODUCT2 with LS_STEP 8
+                    a00 += (sx * sx * 4 + sx * 32 + 128) >> 4;
+                    a01 += (sx * sy * 4 + (sx + sy) * 16 + 64) >> 4;
+                    a11 += (sy * sy * 4 + sy * 32 + 128) >> 4;
+                    bx0 += (sx * dx * 4 + (sx + dx) * 16 + 128) >> 4;
+                    bx1 += (sy * dx * 4 + (sy + dx) * 16 + 64) >> 4;
+                    by0 += (sx * dy * 4 + (sx + dy) * 16 + 64) >> 4;
+                    by1 += (sy * dy * 4 + (sy + dy) * 16 + 128) >> 4;
+                }
+            }
+        }
+        const int64_t det = (int64_t)a00 * a11 - (int64_t)a01 * a01;
+        valid = det != 0;
+        if (valid) {
+            int shift;
+            int i_det = (int16_t)(resolve_divisor((uint64_t)(det < 0 ? -det : det), &shift) * (det < 0 ? -1 : 1));
+            shift -= 16;
+            if (shift < 0) { i_det = (int16_t)(i_det * (1 << -shift)); shift = 0; } // i_det is an int16_t in the reference
+            const int64_t px0 = (int64_t)a11 * bx0 - (int64_t)a01 * bx1, px1 = -(int64_t)a01 * bx0 + (int64_t)a00 * bx1;
+            const int64_t py0 = (int64_t)a11 * by0 - (int64_t)a01 * by1, py1 = -(int64_t)a01 * by0 + (int64_t)a00 * by1;
+            const int     lo = -(1 << 13) + 1, hi = (1 << 13) - 1;
+            const int m2 = clamp64(round_shift_signed_64(px0 * i_det, shift), (1 << 16) + lo, (1 << 16) + hi);
+            const int m3 = clamp64(round_shift_signed_64(px1 * i_det, shift), lo, hi);
+            const int m4 = clamp64(round_shift_signed_64(py0 * i_det, shift), lo, hi);
+            const int m5 = clamp64(round_shift_signed_64(py1 * i_det, shift), (1 << 16) + lo, (1 << 16) + hi);
+            const int vx = (int)((uint32_t)mvx * (1u << 13) - ((uint32_t)isux * (uint32_t)(m2 - (1 << 16)) + (uint32_t)isuy * (uint32_t)m3));
+            const int vy = (int)((uint32_t)mvy * (1u << 13) - ((uint32_t)isux * (uint32_t)m4 + (uint32_t)isuy * (uint32_t)(m5 - (1 << 16))));
+            const int m0 = clampi(vx, -(1 << 23), (1 << 23) - 1), m1 = clampi(vy, -(1 << 23), (1 << 23) - 1);
+            // svt_get_shear_params
+            valid = m2 > 0;
+            if (valid) {
+                int       sh;
+                const int y  = (int16_t)resolve_divisor((uint64_t)m2, &sh);
+                const int al = reduce_shear(m2 - (1 << 16)), be = reduce_shear(m3);
+                const int ga = reduce_shear((int)round_shift_signed_64((int64_t)m4 * (1 << 16) * y, sh));
+                const int de = reduce_shear(m5 - (int)round_shift_signed_64((int64_t)m3 * m4 * y, sh) - (1 << 16));
+                valid = 4 * iabs(al) + 7 * iabs(be) < (1 << 16) && 4 * iabs(ga) + 4 * iabs(de) < (1 << 16);
+                if (valid && !in.shut_approx) {
+                    if (iabs(al) + iabs(be) < in.lower_band_th && iabs(ga) + iabs(de) < in.lower_band_th) valid = false;
+                    if (4 * iabs(al) + 7 * iabs(be) > in.upper_band_th && 4 * iabs(ga) + 4 * iabs(de) > in.upper_band_th) valid = false;
+                }
+                if (valid) {
+                    out.wmmat[0] = m0; out.wmmat[1] = m1; out.wmmat[2] = m2; out.wmmat[3] = m3; out.wmmat[4] = m4; out.wmmat[5] = m5;
+                    out.alpha = (int16_t)al; out.beta = (int16_t)be; out.gamma = (int16_t)ga; out.delta = (int16_t)de;
+                }
+            }
+        }
+    }
+    out.valid = valid ? 1 : 0;
+    return out;
+}
+
+__global__ __launch_bounds__(64) void warp_model_kernel(const SvtHipWarpModelDesc d) {
+    const uint32_t job = blockIdx.x * 64u + threadIdx.x;
+    if (job >= d.n_jobs) return;
+    const SvtHipWarpModelJob *jp = d.jobs + job;
+    const int bw = jp->bwidth, bh = jp->bheight, n = jp->n_samples;
+    const bool from_array = (jp->flags & SVT_HIP_WARP_MV_FROM_ARRAY) != 0;
+    if (!is_warp_size(bw, bh) || n > SVT_HIP_WARP_MAX_SAMPLES || (from_array && (d.mv_array == nullptr || jp->mv_index >= d.n_mvs))) {
+        d.status[job] = SVT_HIP_WARP_UNDEFINED;
+        return;
+    }
+    const int mvy = from_array ? d.mv_array[2 * (size_t)jp->mv_index] : jp->mv[0];
+    const int mvx = from_array ? d.mv_array[2 * (size_t)jp->mv_index + 1] : jp->mv[1];
+    const FitInput in = {jp->pts, jp->pts_inref, n, bw, bh, jp->blk_org_x, jp->blk_org_y, d.shut_approx != 0, d.lower_band_th, d.upper_band_th};
+    d.models[job] = fit_model(in, mvy, mvx);
+    d.status[job] = SVT_HIP_WARP_OK;
+}
+
+// ---- the refinement ----
+// neighbors[9] of svt_aom_wm_motion_refinement as (row, col): the centre, the four sides, the four corners
+__constant__ const int8_t kNeighbour[9][2] = {{0, 0}, {0, -1}, {1, 0}, {0, 1}, {-1, 0}, {-1, 1}, {1, 1}, {1, -1}, {-1, -1}};
+
+// A workgroup of WAVES waves per job.  The search is one sequence of decisions, so every lane of the workgroup walks it with the same values:
+// the positions, the record of tested MVs (in LDS, scanned 64 entries at a time), the fit (every lane computes it; it is a few hundred
+// instructions against the thousands of a warp) and the comparison.  Only the warp is shared out: a wave takes every WAVES-th tile, reduces
+// sum and SSE of its samples against the source, and the partial sums meet in LDS.
+// The descriptor as it lies in the kernel-argument segment (it is the only argument), behind a barrier the compiler cannot see through: a field
+// read through it is loaded where it is used, instead of being held in a scalar register across the whole search loop.
+typedef __attribute__((address_space(4))) const SvtHipWmRefineDesc *KernargDesc; // the constant address space: scalar loads
+__device__ __forceinline__ KernargDesc desc_in_kernarg() {
+    KernargDesc p = (KernargDesc)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
+template <int WAVES> __global__ __launch_bounds__(64 * WAVES) void wm_refine_kernel(const SvtHipWmRefineDesc d) {
+    __shared__ uint16_t s_src[WAVES][15 * 16];
+    __shared__ uint16_t s_mid[WAVES][15 * 8];
+    __shared__ uint32_t s_rec[1 + 8 * SVT_HIP_WM_MAX_ITERATIONS]; // mv_record: 9 positions in the first round, 8 in every other
+    __shared__ uint32_t s_part[WAVES][2];
+    const int      lane = (int)(threadIdx.x & 63u);
+    const int      wave = uniform((int)(threadIdx.x >> 6));
+    const uint32_t job  = blockIdx.x;
+    if (job >= d.n_jobs) return;
+    const SvtHipWmRefineJob *jp = d.jobs + job;
+    const int  bw = jp->bwidth, bh = jp->bheight, n = jp->n_samples, ref = jp->ref;
+    const bool from_array = (jp->flags & SVT_HIP_WM_START_FROM_ARRAY) != 0;
+    bool ok = is_warp_size(bw, bh) && n <= SVT_HIP_WARP_MAX_SAMPLES && ref < d.n_refs;
+    if (from_array) ok = ok && d.mv_array != nullptr && jp->mv_index < d.n_mvs;
+    ok = ok && (uint64_t)jp->src_offset + (uint64_t)(bh > 0 ? bh - 1 : 0) * d.src_stride + (uint64_t)bw <= d.src_samples;
+    if (!uniform((int)ok)) { // a scalar branch: the whole workgroup leaves here
+        if (threadIdx.x == 0) d.status[job] = SVT_HIP_WARP_UNDEFINED;
+        return;
+    }
+    const int  org_x = jp->blk_org_x, org_y = jp->blk_org_y;
+    const int  c = lane & 7, rr = lane >> 3;
+
+    // an MV is one word, as Mv.as_int is: the row in the upper half, the column in the lower
+    const int start_r = uniform(from_array ? d.mv_array[2 * (size_t)jp->mv_index] : jp->start_mv[0]);
+    const int start_c = uniform(from_array ? d.mv_array[2 * (size_t)jp->mv_index + 1] : jp->start_mv[1]);
+    uint32_t  centre = ((uint32_t)start_r << 16) | ((uint32_t)start_c & 0xFFFFu), best = centre, prev = centre;
+    int       best_cost = INT32_MAX, tot = 0;
+    for (int iter = 0; iter < (int)desc_in_kernarg()->iterations; iter++) {
+        const int shift = desc_in_kernarg()->mv_prec_shift, n_pos = desc_in_kernarg()->refine_diag ? 9 : 5;
+        for (int i = iter ? 1 : 0; i < n_pos; i++) { // offset (0, 0) in the first round only
+            const int      test_r = (int16_t)((int)(int16_t)(centre >> 16) + ((int)kNeighbour[i][0] << shift));
+            const int      test_c = (int16_t)((int)(int16_t)(centre & 0xFFFFu) + ((int)kNeighbour[i][1] << shift));
+            const uint32_t key    = ((uint32_t)test_r << 16) | ((uint32_t)test_c & 0xFFFFu);
+            if (iter) { // positions tested before are not tested again
+                if (key == prev) continue;
+                bool hit = false;
+                for (int e = lane; e < tot; e += 64) hit = hit || s_rec[e] == key;
+                if (__ballot(hit) != 0) continue;
+            }
+            if (threadIdx.x == 0) s_rec[tot] = key; // recorded whether or not its fit is valid
+            tot++;
+            __syncthreads();
+            // The fit's inputs are wave-uniform, and left to itself the compiler runs all of it on the scalar unit and keeps the 32 sample
+            // coordinates in scalar registers across the loop, which the loop's own state already fills: handing the MV and the samples' address
+            // over in vector registers keeps the fit on the vector unit, one copy per lane.
+            int      vec_r = test_r, vec_c = test_c;
+            const KernargDesc kd = desc_in_kernarg();
+            FitInput vin = {jp->pts, jp->pts_inref, n, bw, bh, org_x, org_y, kd->shut_approx != 0, kd->lower_band_th, kd->upper_band_th};
+            asm volatile("" : "+v"(vec_r), "+v"(vec_c), "+v"(vin.pts), "+v"(vin.pts_inref), "+v"(vin.n), "+v"(vin.bw), "+v"(vin.bh), "+v"(vin.org_x),
+                         "+v"(vin.org_y)); // n: else eight `i < n` masks stay in scalar pairs; the block: else what the fit derives from it does
+            const SvtHipWarpModel fit = fit_model(vin, vec_r, vec_c);
+            if (uniform(fit.valid) == 0) continue;
+            Model m;
+#pragma unroll
+            for (int k = 0; k < 6; k++) m.mat[k] = uniform(fit.wmmat[k]);
+            m.alpha = uniform(fit.alpha); m.beta = uniform(fit.beta); m.gamma = uniform(fit.gamma); m.delta = uniform(fit.delta);
+            const SvtHipWarpRef r          = {kd->refs[ref].plane, kd->refs[ref].stride, kd->refs[ref].org_x, kd->refs[ref].org_y, kd->refs[ref].width,
+                                              kd->refs[ref].height, kd->refs[ref].rows, 0};
+            const uint8_t      *src        = kd->src + jp->src_offset;
+            const uint32_t      src_stride = kd->src_stride;
+            const int           log2_tx = 31 - __builtin_clz((unsigned)(bw >> 3)), n_tiles = (bw >> 3) * (bh >> 3);
+            uint32_t            sse = 0, sum = 0;
+            for (int t = wave; t < n_tiles; t += WAVES) {
+                const int ty = t >> log2_tx, tx = t & ((1 << log2_tx) - 1);
+                const int v  = clampi(warp_tile<false>(r, m, org_x + 8 * tx, org_y + 8 * ty, 0, 0, 11, s_src[wave], s_mid[wave], lane) - 128 - 256, 0, 255);
+                const int df = v - (int)src[(size_t)(8 * ty + rr) * src_stride + (size_t)(8 * tx + c)];
+                sum += (uint32_t)df;
+                sse += (uint32_t)(df * df);
+            }
+            sse = wave_sum_dpp(sse);
+            sum = wave_sum_dpp(sum);
+            if (WAVES > 1) {
+                // no wave writes the next test's partial sums before every wave has read these: the barrier behind the record lies between
+                if (lane == 0) { s_part[wave][0] = sse; s_part[wave][1] = sum; }
+                __syncthreads();
+                sse = sum = 0;
+#pragma unroll
+                for (int w = 0; w < WAVES; w++) { sse += s_part[w][0]; sum += s_part[w][1]; }
+            }
+            // svt_aom_variance{W}x{H} as an int, plus the MV rate
+            const int64_t s64 = (int64_t)(int32_t)sum;
+            int cost = (int)(sse - (uint32_t)((s64 * s64) >> (31 - __builtin_clz((unsigned)(bw * bh)))));
+            const SvtHipWmRefineJob *jq = jp; // behind a barrier too: the predicted MV is loaded here, not held across the loop
+            asm volatile("" : "+s"(jq));
+            const SvtHipMv pred_mv = {jq->pred_mv[0], jq->pred_mv[1]};
+            int            rate;
+            if (kd->approx_inter_rate) {
+                rate = mv_err_cost_light(test_r, test_c, pred_mv);
+            } else {
+                const MvCost mc = {pred_mv, SVT_HIP_MV_COST_ENTROPY, kd->error_per_bit > 0 ? kd->error_per_bit : 1, kd->mvjcost, kd->mvcost[0], kd->mvcost[1]};
+                rate = mv_err_cost((int16_t)test_r, (int16_t)test_c, mc);
+            }
+            cost           = (int)((uint32_t)cost + (uint32_t)rate);
+            if (cost < best_cost) { best = key; best_cost = cost; }
+        }
+        prev   = centre;
+        centre = best;
+        if (prev == best) break;
+    }
+    if (threadIdx.x == 0) {
+        const KernargDesc kd = desc_in_kernarg();
+        uint32_t job = blockIdx.x; // taken again, behind a barrier: else its 64-bit form is held across the search for these four stores
+        asm volatile("" : "+s"(job));
+        kd->best_mv[2 * (size_t)job] = (int16_t)(best >> 16); kd->best_mv[2 * (size_t)job + 1] = (int16_t)(best & 0xFFFFu);
+        kd->best_cost[job] = best_cost;
+        kd->n_checked[job] = (uint32_t)tot;
+        kd->status[job]    = SVT_HIP_WARP_OK;
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+#define BAD(...) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, __VA_ARGS__)
+static int check_refs(const char *who, const SvtHipWarpRef *refs, int n_refs) {
+    for (int i = 0; i < n_refs; i++) {
+        const SvtHipWarpRef *r = &refs[i];
+        if (!r->plane) BAD("%s: reference %d has a null plane", who, i);
+        if (r->stride == 0 || r->width == 0 || r->height == 0) BAD("%s: reference %d: stride %u, picture %u x %u (all non-zero)", who, i, r->stride, r->width, r->height);
+        if ((uint32_t)r->org_x + r->width > r->stride || (uint32_t)r->org_y + r->height > r->rows)
+            BAD("%s: reference %d: the picture %u x %u at (%u, %u) lies outside its plane (stride %u, %u rows)", who, i, r->width, r->height, r->org_x, r->org_y, r->stride,
+                r->rows);
+    }
+    return SVT_HIP_OK;
+}
+
+int svt_hip_warp_check_desc(const SvtHipWarpPredDesc *d) {
+    if (!d) BAD("svt_hip_warp_check_desc: null descriptor");
+    if (!d->dst || !d->jobs || !d->status) BAD("svt_hip_warp_check_desc: a mandatory pointer (dst, jobs, status) is null");
+    if (d->bit_depth != 8 && d->bit_depth != 10) BAD("svt_hip_warp_check_desc: bit_depth %u (8 or 10)", d->bit_depth);
+    if (d->ss_x > 1 || d->ss_y > 1) BAD("svt_hip_warp_check_desc: ss_x %u, ss_y %u (0 or 1)", d->ss_x, d->ss_y);
+    if (d->n_refs == 0 || d->n_refs > SVT_HIP_WARP_MAX_REFS) BAD("svt_hip_warp_check_desc: n_refs %u (1 .. %d)", d->n_refs, SVT_HIP_WARP_MAX_REFS);
+    const int rc = check_refs("svt_hip_warp_check_desc", d->refs, d->n_refs);
+    if (rc) return rc;
+    if (d->dst_stride == 0 || d->dst_samples == 0) BAD("svt_hip_warp_check_desc: dst_stride %u / dst_samples %llu is zero", d->dst_stride, (unsigned long long)d->dst_samples);
+    if (d->n_models && !d->models) BAD("svt_hip_warp_check_desc: n_models %u without a model array", d->n_models);
+    return SVT_HIP_OK;
+}
+
+int svt_hip_wm_refine_check_desc(const SvtHipWmRefineDesc *d) {
+    if (!d) BAD("svt_hip_wm_refine_check_desc: null descriptor");
+    if (!d->src || !d->jobs || !d->best_mv || !d->best_cost || !d->n_checked || !d->status)
+        BAD("svt_hip_wm_refine_check_desc: a mandatory pointer (src, jobs, best_mv, best_cost, n_checked, status) is null");
+    if (d->iterations == 0 || d->iterations > SVT_HIP_WM_MAX_ITERATIONS) BAD("svt_hip_wm_refine_check_desc: iterations %u (1 .. %d)", d->iterations, SVT_HIP_WM_MAX_ITERATIONS);
+    if (d->mv_prec_shift > 1) BAD("svt_hip_wm_refine_check_desc: mv_prec_shift %u (0 or 1)", d->mv_prec_shift);
+    if (d->waves_per_job != 0 && d->waves_per_job != 1 && d->waves_per_job != 4) BAD("svt_hip_wm_refine_check_desc: waves_per_job %u (0, 1 or 4)", d->waves_per_job);
+    if (d->n_refs == 0 || d->n_refs > SVT_HIP_WARP_MAX_REFS) BAD("svt_hip_wm_refine_check_desc: n_refs %u (1 .. %d)", d->n_refs, SVT_HIP_WARP_MAX_REFS);
+    const int rc = check_refs("svt_hip_wm_refine_check_desc", d->refs, d->n_refs);
+    if (rc) return rc;
+    if (d->src_stride == 0 || d->src_samples == 0) BAD("svt_hip_wm_refine_check_desc: src_stride %u / src_samples %llu is zero", d->src_stride, (unsigned long long)d->src_samples);
+    if (d->n_mvs && !d->mv_array) BAD("svt_hip_wm_refine_check_desc: n_mvs %u without mv_array", d->n_mvs);
+    if (d->error_per_bit < 0) BAD("svt_hip_wm_refine_check_desc: error_per_bit %d is negative", d->error_per_bit);
+    if (!d->approx_inter_rate && (!d->mvjcost || !d->mvcost[0] || !d->mvcost[1])) BAD("svt_hip_wm_refine_check_desc: a cost table is null and approx_inter_rate is not set");
+    return SVT_HIP_OK;
+}
+#undef BAD
+
+size_t svt_hip_warp_layout(int what, int field) {
+#define D(f) offsetof(SvtHipWarpPredDesc, f)
+#define J(f) offsetof(SvtHipWarpPredJob, f)
+#define R(f) offsetof(SvtHipWarpRef, f)
+#define M(f) offsetof(SvtHipWarpModel, f)
+#define E(f) offsetof(SvtHipWarpModelDesc, f)
+#define K(f) offsetof(SvtHipWarpModelJob, f)
+    static const size_t desc[]  = {D(bit_depth), D(ss_x), D(ss_y), D(n_refs), D(n_jobs), D(refs), D(dst), D(dst_stride), D(reserved), D(dst_samples), D(jobs),
+                                   D(models), D(n_models), D(reserved2), D(status)};
+    static const size_t job[]   = {J(dst_offset), J(p_col), J(p_row), J(width), J(height), J(ref), J(flags), J(comp_mode), J(fwd_offset), J(bck_offset),
+                                   J(model_index), J(model)};
+    static const size_t ref[]   = {R(plane), R(stride), R(org_x), R(org_y), R(width), R(height), R(rows), R(reserved)};
+    static const size_t model[] = {M(wmmat), M(alpha), M(beta), M(gamma), M(delta), M(wmtype), M(valid), M(num_samples), M(reserved)};
+    static const size_t mdesc[] = {E(n_jobs), E(shut_approx), E(reserved), E(lower_band_th), E(upper_band_th), E(reserved2), E(n_mvs), E(jobs), E(mv_array),
+                                   E(models), E(status)};
+    static const size_t mjob[]  = {K(pts), K(pts_inref), K(blk_org_x), K(blk_org_y), K(bwidth), K(bheight), K(n_samples), K(flags), K(mv), K(mv_index)};
+#define F(f) offsetof(SvtHipWmRefineDesc, f)
+#define G(f) offsetof(SvtHipWmRefineJob, f)
+    static const size_t rdesc[] = {F(n_jobs), F(iterations), F(refine_diag), F(mv_prec_shift), F(shut_approx), F(lower_band_th), F(upper_band_th), F(approx_inter_rate),
+                                   F(n_refs), F(waves_per_job), F(reserved), F(error_per_bit), F(src_stride), F(src), F(src_samples), F(refs), F(jobs), F(mv_array),
+                                   F(n_mvs), F(reserved2), F(mvjcost), F(mvcost), F(best_mv), F(best_cost), F(n_checked), F(status)};
+    static const size_t rjob[]  = {G(pts), G(pts_inref), G(src_offset), G(blk_org_x), G(blk_org_y), G(bwidth), G(bheight), G(n_samples), G(flags), G(start_mv),
+                                   G(pred_mv), G(mv_index), G(ref), G(reserved)};
+#undef D
+#undef J
+#undef R
+#undef M
+#undef E
+#undef K
+#undef F
+#undef G
+#define N(a) (sizeof(a) / sizeof((a)[0]))
+    const size_t *tab[8]  = {desc, job, ref, model, mdesc, mjob, rdesc, rjob};
+    const size_t  n[8]    = {N(desc), N(job), N(ref), N(model), N(mdesc), N(mjob), N(rdesc), N(rjob)};
+    const size_t  size[8] = {sizeof(SvtHipWarpPredDesc), sizeof(SvtHipWarpPredJob), sizeof(SvtHipWarpRef), sizeof(SvtHipWarpModel), sizeof(SvtHipWarpModelDesc),
+                             sizeof(SvtHipWarpModelJob), sizeof(SvtHipWmRefineDesc), sizeof(SvtHipWmRefineJob)};
+#undef N
+    if (what < 0 || what > 7) return (size_t)-1;
+    if (field < 0) return size[what];
+    return (size_t)field < n[what] ? tab[what][field] : (size_t)-1;
+}
+
+const int16_t  *svt_hip_warp_filter_table(void) { return &kTablesHost.filter[0][0]; }
+const uint16_t *svt_hip_warp_div_lut(void) { return kTablesHost.div_lut; }
+
+int svt_hip_warp_pred_batch(SvtHipContext *ctx, const SvtHipWarpPredDesc *d) {
+    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_warp_pred_batch: null context or descriptor");
+    const int rc = svt_hip_warp_check_desc(d);
+    if (rc) return rc;
+    if (d->n_jobs == 0) return SVT_HIP_OK;
+    hipSetDevice(ctx->device);
+    std::lock_guard<std::mutex> lock(ctx->async_mu);
+    if (d->bit_depth == 10) hipLaunchKernelGGL(warp_pred_kernel<true>, dim3(d->n_jobs), dim3(64 * kWaves), 0, ctx->stream, *d);
+    else hipLaunchKernelGGL(warp_pred_kernel<false>, dim3(d->n_jobs), dim3(64 * kWaves), 0, ctx->stream, *d);
+    SVT_HIP_CHECK(ctx, hipGetLastError());
+    return SVT_HIP_OK;
+}
+
+int svt_hip_warp_model_batch(SvtHipContext *ctx, const SvtHipWarpModelDesc *d) {
+    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_warp_model_batch: null context or descriptor");
+    if (!d->jobs || !d->models || !d->status) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_warp_model_batch: a mandatory pointer (jobs, models, status) is null");
+    if (d->n_mvs && !d->mv_array) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_warp_model_batch: n_mvs %u without mv_array", d->n_mvs);
+    if (d->n_jobs == 0) return SVT_HIP_OK;
+    hipSetDevice(ctx->device);
+    std::lock_guard<std::mutex> lock(ctx->async_mu);
+    hipLaunchKernelGGL(warp_model_kernel, dim3((d->n_jobs + 63u) / 64u), dim3(64), 0, ctx->stream, *d);
+    SVT_HIP_CHECK(ctx, hipGetLastError());
+    return SVT_HIP_OK;
+}
+
+int svt_hip_wm_refine_batch(SvtHipContext *ctx, const SvtHipWmRefineDesc *d) {
+    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_wm_refine_batch: null context or descriptor");
+    const int rc = svt_hip_wm_refine_check_desc(d);
+    if (rc) return rc;
+    if (d->n_jobs == 0) return SVT_HIP_OK;
+    hipSetDevice(ctx->device);
+    std::lock_guard<std::mutex> lock(ctx->async_mu);
+    if (d->waves_per_job == 1) hipLaunchKernelGGL(wm_refine_kernel<1>, dim3(d->n_jobs), dim3(64), 0, ctx->stream, *d);
+    else hipLaunchKernelGGL(wm_refine_kernel<kWaves>, dim3(d->n_jobs), dim3(64 * kWaves), 0, ctx->stream, *d);
+    SVT_HIP_CHECK(ctx, hipGetLastError());
+    return SVT_HIP_OK;
+}
+
+} // extern "C"
