@@ -695,6 +695,7 @@ __device__ __forceinline__ void run_searches(Shared &sh PROF_PARAM) {
 // rows, and a lane fetches its window rows straight from global memory (a row is NDW + 2 dwords: two or five unaligned 16-byte loads, the
 // next row on its way while the current one is evaluated) -- no tile plan, no staging rounds, one pass for the whole stage.  Per-position
 // sums meet in the (idle) arena by LDS atomics; one arg-min per search.  Returns false (nothing done) when the stage does not qualify.
+// That is the GENERAL layout (requests with different areas: edge blocks); requests that are alike take the ring form further down.
 // One pass of a direct stage.  A lane owns one item (an octet of positions x a slice of block rows) and needs, per block row, the NDW + 2
 // window dwords under it: NV 16-byte pieces of ONE window row.  Fetched by their owner the pieces of a step lie in 64 different rows -- every
 // lane of every load instruction in a cache line of its own, and the texture addresser, which takes them one line at a time, becomes the
@@ -793,20 +794,181 @@ __device__ __forceinline__ bool small_direct_ok(const St &st, int *q_total = nul
     if (q_total) *q_total = q;
     return q <= kThreads;
 }
-template <int DEPTH = 1> __device__ __forceinline__ bool run_small_searches_direct(Shared &sh PROF_PARAM) {
+// The RING form of a direct stage, for requests that are alike: one octet per search row (sa_w <= 8), one sa_h <= 3 for all, rs <= 2.  A lane
+// is (request, slice of the block rows): lane = request * G + slice, G the largest power of two with G * nreq <= 64, so that a request's
+// slices are neighbours and meet by DPP.  Of the G lanes S = ceil(bh / rows_per) work, rows_per = ceil(bh / min(bh, G)).  A lane walks the
+// window rows under its slice ONCE -- rs * (rows - 1) + sa_h of them -- and adds window row j to every search row y with (j - y) a multiple
+// of rs and block row t = (j - y) / rs inside the slice: one pair of packed accumulators per y, each flushed after kRowsPerFlush rows of ITS
+// OWN.  The fetch is direct_rows': linear piece order through the arena, DEPTH steps in flight; the piece's owner is a lane whose request and
+// slice follow from its number, so its pointer is computed, not shuffled.  Out: the lane's partial sums a[y][x].
+template <int NDW, int DEPTH>
+__device__ __forceinline__ void ring_rows(uint8_t *arena, const uint8_t *src, int sp, int srs, const St &st, int nreq, int lg, int S, int rows_per, int bh, int rs, int sa_h,
+                                          long long stride, uint32_t (&a)[3][8]) {
+    constexpr int NV = (NDW + 2 + 3) / 4, kRowsPerFlush = 64 / NDW;
+    static_assert(NV & 1, "owners read their pieces back without bank conflicts");
+    static_assert(DEPTH >= 1 && DEPTH <= 3, "steps in flight");
+    const int lane = threadIdx.x, gmask = (1 << lg) - 1;
+    const int steps_max = rs * (rows_per - 1) + sa_h; // uniform: the window rows under a full slice
+    const uint8_t *pp[NV]; // where this lane fetches piece (lane + 64 k) of the next step to request
+    int            pn[NV]; // steps its owner makes
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        const int  n = lane + 64 * k, owner = n / NV, part = n - owner * NV, orq = owner >> lg, osl = owner & gmask;
+        const bool act = orq < nreq && osl < S;
+        const int  oe0 = osl * rows_per, orows = imin(oe0 + rows_per, bh) - oe0;
+        pn[k] = act ? rs * (orows - 1) + sa_h : 0;
+        pp[k] = st.req[act ? orq : 0].win + (long long)(oe0 * rs) * stride + 16 * part;
+    }
+    const int  req = lane >> lg, slice = lane & gmask, e0 = slice * rows_per;
+    const int  rows = (req < nreq && slice < S) ? imin(e0 + rows_per, bh) - e0 : 0;
+    V4U v[DEPTH][NV];
+    auto request = [&](V4U (&r)[NV], int step) { // the pieces of `step` (requests are made in step order: pp walks along)
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            if (step < pn[k]) r[k] = *reinterpret_cast<GV4U *>(reinterpret_cast<uintptr_t>(pp[k]));
+            pp[k] += stride;
+        }
+    };
+#pragma unroll
+    for (int dpt = 0; dpt < DEPTH; dpt++) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) v[dpt][k] = V4U{0, 0, 0, 0};
+        request(v[dpt], dpt);
+    }
+#pragma unroll
+    for (int y = 0; y < 3; y++)
+#pragma unroll
+        for (int i = 0; i < 8; i++) a[y][i] = 0;
+    u64 acc[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+    auto step = [&](V4U (&r)[NV], int j) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) *reinterpret_cast<V4U *>(arena + 16 * (lane + 64 * k)) = r[k];
+        wave_sync();
+        request(r, j + DEPTH);
+        uint32_t wv[4 * NV];
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(arena + 16 * (lane * NV + k));
+            wv[4 * k] = q.x; wv[4 * k + 1] = q.y; wv[4 * k + 2] = q.z; wv[4 * k + 3] = q.w;
+        }
+#pragma unroll
+        for (int y = 0; y < 3; y++) {
+            const int dd = j - y, t = rs == 2 ? dd >> 1 : dd; // uniform
+            if (y < sa_h && dd >= 0 && (rs == 1 || !(dd & 1)) && t < rows_per) {
+                if (t < rows) {
+                    const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (e0 + t) * srs * sp);
+                    uint32_t sv[NDW];
+#pragma unroll
+                    for (int c = 0; c < NDW; c += 4) {
+                        const uint4 q = *reinterpret_cast<const uint4 *>(s + c);
+                        sv[c] = q.x; sv[c + 1] = q.y; sv[c + 2] = q.z; sv[c + 3] = q.w;
+                    }
+#pragma unroll
+                    for (int c = 0; c < NDW; c++) {
+                        acc[y][0] = __builtin_amdgcn_qsad_pk_u16_u8(((u64)wv[c + 1] << 32) | wv[c], sv[c], acc[y][0]);
+                        acc[y][1] = __builtin_amdgcn_qsad_pk_u16_u8(((u64)wv[c + 2] << 32) | wv[c + 1], sv[c], acc[y][1]);
+                    }
+                }
+                if ((t + 1) % kRowsPerFlush == 0 || t + 1 == rows_per) { // uniform: the 16-bit sums of search row y hold kRowsPerFlush rows
+#pragma unroll
+                    for (int i = 0; i < 4; i++) { a[y][i] += (uint32_t)((acc[y][0] >> (16 * i)) & 0xFFFF); a[y][4 + i] += (uint32_t)((acc[y][1] >> (16 * i)) & 0xFFFF); }
+                    acc[y][0] = acc[y][1] = 0;
+                }
+            }
+        }
+        wave_sync(); // the arena is rewritten
+    };
+    for (int j = 0; j < steps_max; j += DEPTH) { // uniform
+        step(v[0], j);
+        if (DEPTH >= 2 && j + 1 < steps_max) step(v[DEPTH >= 2 ? 1 : 0], j + 1);
+        if (DEPTH >= 3 && j + 2 < steps_max) step(v[DEPTH >= 3 ? 2 : 0], j + 2);
+    }
+}
+
+// A ring stage: the rows, the slices of a request summed over its G neighbouring lanes (DPP inside a 16-lane row), and the arg-min of each
+// request in its own lanes -- every lane of a group holds all sa_w x sa_h sums, so the first minimum in raster order is the smallest
+// (sad << 6 | position) over the request's OWN area (sad < 2^20), taken in registers: no trip through LDS, no loop over the requests.
+template <int DEPTH> __device__ __forceinline__ void run_ring_searches(Shared &sh, int nreq, int bw, int bh, int rs, int level, int sa_h PROF_PARAM) {
+    St       &st   = sh.st;
+    const int lane = threadIdx.x;
+    int lg = 0;
+    while ((2 << lg) * nreq <= kThreads) lg++; // uniform: G = 1 << lg lanes per request
+    const int S0 = imin(bh, 1 << lg), rows_per = (int)uni(div_by_rcp((uint32_t)(bh + S0 - 1), rcp_of((uint32_t)S0)));
+    const int S  = (int)uni(div_by_rcp((uint32_t)(bh + rows_per - 1), rcp_of((uint32_t)rows_per)));
+    const uint8_t *src = src_view(sh, level);
+    const int      sp  = (level == 2) ? kSrc64Pitch : (level == 1 ? kSrc32Pitch : kSrc16Pitch), srs = rs >> sh.cshift;
+    const long long stride = (long long)(int)uni((uint32_t)st.req[0].stride);
+    uint32_t a[3][8];
+    PROF(26);
+    if (bw == 64) ring_rows<16, DEPTH>(LDS(sh.win), src, sp, srs, st, nreq, lg, S, rows_per, bh, rs, sa_h, stride, a);
+    else ring_rows<8, DEPTH>(LDS(sh.win), src, sp, srs, st, nreq, lg, S, rows_per, bh, rs, sa_h, stride, a);
+    PROF(27);
+#define SVT_RING_SUM(cond, expr)                                                  \
+    if (cond) {                                                                   \
+        _Pragma("unroll") for (int y = 0; y < 3; y++)                             \
+            _Pragma("unroll") for (int i = 0; i < 8; i++) { const uint32_t v = a[y][i]; a[y][i] = v + (uint32_t)(expr); } \
+    }
+    SVT_RING_SUM(lg >= 1, __builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true))
+    SVT_RING_SUM(lg >= 2, __builtin_amdgcn_mov_dpp((int)v, 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, true))
+    SVT_RING_SUM(lg >= 3, __builtin_amdgcn_mov_dpp((int)v, 0x141 /* row_half_mirror */, 0xF, 0xF, true))
+    SVT_RING_SUM(lg >= 4, __builtin_amdgcn_mov_dpp((int)v, 0x140 /* row_mirror */, 0xF, 0xF, true))
+    SVT_RING_SUM(lg >= 5, __shfl_xor((int)v, 16, 64)) // one or two requests: across the rows
+    SVT_RING_SUM(lg >= 6, __shfl_xor((int)v, 32, 64))
+#undef SVT_RING_SUM
+    PROF(23);
+    const int req = lane >> lg;
+    if (req < nreq && (lane & ((1 << lg) - 1)) == 0) {
+        const int w = st.req[req].sa_w;
+        uint32_t  best = 0xFFFFFFFFu;
+#pragma unroll
+        for (int y = 0; y < 3; y++)
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                if (y < sa_h && i < w) best = umin(best, (a[y][i] << 6) | (uint32_t)(y * w + i));
+        const int wl = (int)(best & 63u), wy = (int)div_by_rcp((uint32_t)wl, rcp_of((uint32_t)w)), wx = wl - wy * w;
+        st.req_key[req] = ((u64)(best >> 6) << 32) | ((uint32_t)wy << 16) | (uint32_t)wx;
+    }
+    wave_sync(); // the arena is free again
+}
+
+#ifndef SVT_HIP_ME_DIRECT_RING
+#define SVT_HIP_ME_DIRECT_RING 1 /* 0: every direct stage keeps the general (item) layout */
+#endif
+#ifndef SVT_HIP_ME_DIRECT_RING_FULL
+#define SVT_HIP_ME_DIRECT_RING_FULL 0 /* 1: the one-kernel form's HME stages take the ring form too (it is at 256 VGPRs: 87 -> 139 spilled with it, and measured slower) */
+#endif
+#ifndef SVT_HIP_ME_DIRECT_TRUST
+#define SVT_HIP_ME_DIRECT_TRUST 1 /* 0: the search kernels evaluate small_direct_ok again */
+#endif
+// QUALIFIED: the caller knows that the stage qualifies (the search kernels: the mid kernel routed the block there because it does)
+template <int DEPTH = 1, bool QUALIFIED = false, bool RING = true> __device__ __forceinline__ bool run_small_searches_direct(Shared &sh PROF_PARAM) {
     St       &st   = sh.st;
     const int lane = threadIdx.x, nreq = (int)uni((uint32_t)st.nreq);
     // few positions per search, whole-vector source rows, one block shape
-    int Q = 0; // octet items of one slice
-    if (!small_direct_ok(st, &Q)) return false;
-    Q = (int)uni((uint32_t)Q);
+    if constexpr (!(QUALIFIED && SVT_HIP_ME_DIRECT_TRUST)) {
+        if (!small_direct_ok(st)) return false;
+    }
     const Req &r0 = st.req[0];
     const int  bw = (int)uni(r0.bw), bh = (int)uni(r0.bh), rs = (int)uni(r0.rs), level = (int)uni(r0.level);
+    int per = 0; // octet items of this lane's request
+    if constexpr (RING && SVT_HIP_ME_DIRECT_RING) { // are the requests alike?  one compare per lane, one ballot
+        const int h0 = (int)uni((uint32_t)r0.sa_h);
+        bool alike = true;
+        if (lane < nreq) {
+            const int w = st.req[lane].sa_w, h = st.req[lane].sa_h;
+            alike = w <= 8 && h == h0;
+            per   = ((w + 7) >> 3) * h;
+        }
+        if (h0 <= 3 && rs <= 2 && __all(alike)) { // uniform
+            run_ring_searches<DEPTH>(sh, nreq, bw, bh, rs, level, h0 PROF_ARG);
+            return true;
+        }
+    } else if (lane < nreq)
+        per = ((st.req[lane].sa_w + 7) >> 3) * st.req[lane].sa_h;
+    const int Q = (int)wave_sum_dpp((uint32_t)per); // octet items of one slice (<= 64: the stage qualifies)
     // where a request's items start inside a slice: exclusive prefix of its item count over the requests (lane <-> request), parked in the
     // requests' key slots until the keys themselves are written
     {
-        int per = 0;
-        if (lane < nreq) per = ((st.req[lane].sa_w + 7) >> 3) * st.req[lane].sa_h;
         int incl = per;
 #pragma unroll
         for (int o = 1; o < 32; o <<= 1) { const int t = __shfl_up(incl, o, 64); if ((lane & 31) >= o) incl += t; } // (kMaxReq = 32 requests)
@@ -1475,7 +1637,9 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
             wave_sync();
             PROF(25);
             if (st.nreq) { // uniform
-                (void)run_small_searches_direct<SVT_HIP_ME_SEARCH_DEPTH>(sh PROF_ARG); // (the Mid kernel routed the block here because it qualifies)
+                // (the Mid kernel routed the block here because it qualifies.  s1 does not ask again; in s2 leaving the question out did not separate
+                // from asking it -- profiles/r11_me_direct_ring_before_after.txt -- so s2 keeps it)
+                (void)run_small_searches_direct<SVT_HIP_ME_SEARCH_DEPTH, MODE == kMeS1>(sh PROF_ARG);
             }
             wave_sync();
             u64 *keys = keys_of(gjob);
@@ -2060,7 +2224,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 } else if (step < kProbe) {
                     PROF_STEP(step);
                     if (st.nreq) { // uniform (LDS value read after the barrier)
-                        if (!run_small_searches_direct(sh PROF_ARG)) run_searches(sh PROF_ARG);
+                        if (!run_small_searches_direct<1, false, SVT_HIP_ME_DIRECT_RING_FULL != 0>(sh PROF_ARG)) run_searches(sh PROF_ARG);
                     }
                 } else {
                     const bool   probe = step == kProbe;

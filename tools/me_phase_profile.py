@@ -42,7 +42,7 @@ PHASES = [
 ] + [(24 + i, f"{n}: plan a round + issue its window loads" if MODE not in (2, 5) else ("search kernel: set-up batch (job flags, requests, source view: direct-to-LDS loads, one wait)", "search kernel: after the batch (nothing left to copy)", "direct search: qualification, lane set-up", "direct search: row loop")[i] if i < 4 else "-") for i, n in enumerate(STAGES)] + [(32 + i, f"{n}: window registers -> LDS arena") for i, n in enumerate(STAGES)] + [
     (40 + i, f"{n}: rest of the evaluation (tile entry -> registers, arg-min across the wave, result)") for i, n in enumerate(STAGES)] + [
     (22, "all stages: plan the next round + issue its window loads (inside the evaluation phase)"), (30, "all stages: wide tiles, item loop (8 positions x whole block per lane)"),
-    (23, "all stages: small searches, item loop (8 positions x row slice per lane, LDS atomics)"), (19, "searches: tail"),
+    (23, "all stages: small searches, item loop (8 positions x row slice per lane, LDS atomics)" if MODE not in (2, 5) else "direct search: the slices' sums meet (ring form: DPP sums over a request's lanes; general form: LDS atomics)"), (19, "searches: tail"),
     (18, "check-00: the two SADs per reference, inline (no search stage)"),  # 17, 18: the tail kernel only
     (17, "8x8-variance probe: reference rows of all probes requested (global -> registers)"),
     # the tail kernel evaluates the probe on its own (probe_sads); every other form sends it through run_me_searches like the integer search, so
