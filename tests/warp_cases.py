@@ -1,5 +1,5 @@
 """The cases of the warped-motion entries (svt_hip_warp_pred_batch, svt_hip_warp_model_batch, svt_hip_wm_refine_batch) and numpy restatements of all three, shared by
-tests/test_warp.py, tests/test_warp_gpu.py, tests/test_warp_chain_gpu.py and tools/gen_warp_golden.py, which compares the restatements with the
+tests/test_warp.py, tests/test_warp_gpu.py, tests/test_warp_chain_gpu.py, tests/warp_edge_cases.py and tools/gen_warp_golden.py, which compares the restatements with the
 reference encoder on every job and writes golden/warp.npz.  The restatements follow the reference's C line by line (Source/Lib/Codec/
 warped_motion.c: svt_av1_warp_affine_c, svt_av1_highbd_warp_affine_c, svt_aom_select_samples, find_affine_int, svt_get_shear_params;
 adaptive_mv_pred.c: svt_aom_warped_motion_parameters from the MV on; mode_decision.c: the loop of svt_aom_wm_motion_refinement), in Python integers where C has 32- and 64-bit ones.  The 193 x 8 filter
@@ -520,12 +520,14 @@ def find_affine_int(n, pts, pts_inref, bw, bh, mvy, mvx, mi_row, mi_col, trace):
     sq = lambda a: (a * a * 4 + a * 4 * 8 + 8 * 8 * 2) >> 4
     p1 = lambda a, b: (a * b * 4 + (a + b) * 2 * 8 + 8 * 8) >> 4
     p2 = lambda a, b: (a * b * 4 + (a + b) * 2 * 8 + 8 * 8 * 2) >> 4
+    wide = []  # what the reference holds in 32 bits, unwrapped here: for the trace alone
     for i in range(n):
         dx, dy = pts_inref[2 * i] - dux, pts_inref[2 * i + 1] - duy
         sx, sy = pts[2 * i] - sux, pts[2 * i + 1] - suy
         if abs(sx - dx) < 256 and abs(sy - dy) < 256:
             A[0][0] += sq(sx); A[0][1] += p1(sx, sy); A[1][1] += sq(sy)
             bx[0] += p2(sx, dx); bx[1] += p1(sy, dx); by[0] += p1(sx, dy); by[1] += p2(sy, dy)
+            wide += [4 * a * b + 16 * (abs(a) + abs(b)) + 128 for a in (sx, sy) for b in (sx, sy, dx, dy)] + A[0] + A[1] + bx + by
         else:
             trace.add("ls_mv_max")
     det = A[0][0] * A[1][1] - A[0][1] * A[0][1]
@@ -554,6 +556,15 @@ def find_affine_int(n, pts, pts_inref, bw, bh, mvy, mvx, mi_row, mi_col, trace):
     m = [0, 0, mult(px[0], True, "diag"), mult(px[1], False, "ndiag"), mult(py[0], False, "ndiag"), mult(py[1], True, "diag")]
     vx = i32(mvx * (1 << 13) - (isux * (m[2] - (1 << 16)) + isuy * m[3]))
     vy = i32(mvy * (1 << 13) - (isux * m[4] + isuy * (m[5] - (1 << 16))))
+    wide += [mvx * (1 << 13), isux * (m[2] - (1 << 16)), isuy * m[3], isux * (m[2] - (1 << 16)) + isuy * m[3], mvx * (1 << 13) - (isux * (m[2] - (1 << 16)) + isuy * m[3]),
+             mvy * (1 << 13), isux * m[4], isuy * (m[5] - (1 << 16)), isux * m[4] + isuy * (m[5] - (1 << 16)), mvy * (1 << 13) - (isux * m[4] + isuy * (m[5] - (1 << 16)))]
+    if any(i32(v) != v for v in wide):
+        trace.add("int32_left")  # a 32-bit intermediate of the reference wrapped
+    for k, v in enumerate((vx, vy)):
+        if v < -(1 << 23):
+            trace.add(f"trans_lo_{k}")
+        if v > (1 << 23) - 1:
+            trace.add(f"trans_hi_{k}")
     m[0], m[1] = clamp(vx, -(1 << 23), (1 << 23) - 1), clamp(vy, -(1 << 23), (1 << 23) - 1)
     return 0, m
 
@@ -711,18 +722,19 @@ NEIGHBOURS = [(0, 0), (0, -1), (1, 0), (0, 1), (-1, 0), (-1, 1), (1, 1), (1, -1)
 def mv_err_cost(mv, ref, tables, error_per_bit):
     """svt_aom_mv_err_cost: mv, ref = (row, col); tables = (mvjcost, row table, column table), the tables indexed from -16384"""
     jc, tr, tc = tables
-    dr, dc = i16(mv[0] - ref[0]), i16(mv[1] - ref[1])
+    dr, dc = i16(int(mv[0]) - int(ref[0])), i16(int(mv[1]) - int(ref[1]))
     joint = (0 if dc == 0 else 1) if dr == 0 else (2 if dc == 0 else 3)
     bits = int(jc[joint]) + int(tr[MV_CENTRE + clamp(dr, -MV_CENTRE, MV_CENTRE)]) + int(tc[MV_CENTRE + clamp(dc, -MV_CENTRE, MV_CENTRE)])
     return i32((bits * error_per_bit + (1 << 13)) >> 14)
 
 
 def mv_err_cost_light(mv, ref):
-    return 1296 + 50 * (abs(mv[1] - ref[1]) + abs(mv[0] - ref[0]))
+    return 1296 + 50 * (abs(int(mv[1]) - int(ref[1])) + abs(int(mv[0]) - int(ref[0])))  # int arithmetic on the int16 fields: no wrap
 
 
-def refine_cost(b, job, mv):
-    """the cost svt_aom_wm_motion_refinement gives the MV (row, col), or None when its fit is invalid"""
+def refine_cost(b, job, mv, detail=None):
+    """the cost svt_aom_wm_motion_refinement gives the MV (row, col), or None when its fit is invalid; detail: a dict that receives the sum and the SSE
+    of the differences, and the tiles of the warp in detail["seen"] (new_seen()) when it holds one"""
     s = b["settings"]
     fit = fit_model(job, mv, s["shut_approx"], s["lower_band_th"], s["upper_band_th"])
     if not int(fit["valid"]):
@@ -730,10 +742,12 @@ def refine_cost(b, job, mv):
     bw, bh = int(job["bwidth"]), int(job["bheight"])
     view = dict(bit_depth=8, ss_x=0, ss_y=0, planes=b["planes"])
     pj = pred_job(0, int(job["blk_org_x"]), int(job["blk_org_y"]), bw, bh, [int(job["ref"])], [fit])
-    pred = warp_block(view, pj, [model_of(fit)])
+    pred = warp_block(view, pj, [model_of(fit)], None if detail is None else detail.get("seen"))
     y, x = divmod(int(job["src_offset"]), b["src"].shape[1])
     diff = pred - b["src"][y:y + bh, x:x + bw].astype(np.int64)
     sse, total = int((diff * diff).sum()), int(diff.sum())
+    if detail is not None:
+        detail["sum"], detail["sse"] = total, sse
     var = i32((sse - ((total * total) // (bw * bh) & 0xFFFFFFFF)) & 0xFFFFFFFF)
     rate = mv_err_cost_light(mv, job["pred_mv"]) if s["approx_inter_rate"] else mv_err_cost(mv, job["pred_mv"], b["cost_tables"], max(1, s["error_per_bit"]))
     return i32(var + int(rate))
@@ -749,32 +763,47 @@ def refine_job_status(b, job):
     return ST_OK if ok else ST_UNDEFINED
 
 
-def refine(b, job, trace=None):
-    """the loop of svt_aom_wm_motion_refinement: ((row, col), best_cost, tot_checked_pos, the positions whose fit was valid)"""
+def refine(b, job, trace=None, log=None):
+    """the loop of svt_aom_wm_motion_refinement: ((row, col), best_cost, tot_checked_pos, the positions whose fit was valid).  log: a dict that receives
+    "start", "costed" (the MV, its cost, the sum and the SSE of each warped position, in order), "record_hits" (the record index of every skip by
+    mv_record), "wrapped" ((the component 0 row / 1 col, the value before the int16 wrap, the value recorded) of every recorded position that wrapped)
+    and "seen" (the tiles of every warp)"""
     trace = set() if trace is None else trace
+    if log is not None:
+        log.update(costed=[], record_hits=[], wrapped=[], seen=new_seen())
     s = b["settings"]
     start = b["mv_array"][int(job["mv_index"])] if int(job["flags"]) & WM_START_FROM_ARRAY else job["start_mv"]
     centre = best = prev = (int(start[0]), int(start[1]))
+    if log is not None:
+        log["start"] = centre
     best_cost, record, n_valid = INT_MAX, [], 0
     stopped = "iterations"
     seen_valid = False
     for it in range(s["iterations"]):
         for i in range(1 if it else 0, 9 if s["refine_diag"] else 5):
-            test = (i16(centre[0] + (NEIGHBOURS[i][0] << s["mv_prec_shift"])), i16(centre[1] + (NEIGHBOURS[i][1] << s["mv_prec_shift"])))
+            wide = (centre[0] + (NEIGHBOURS[i][0] << s["mv_prec_shift"]), centre[1] + (NEIGHBOURS[i][1] << s["mv_prec_shift"]))
+            test = (i16(wide[0]), i16(wide[1]))
             if it:
                 if test == prev:
                     trace.add("skip_prev")
                     continue
                 if test in record:
                     trace.add("skip_record")
+                    if log is not None:
+                        log["record_hits"].append(record.index(test))
                     continue
             record.append(test)
-            cost = refine_cost(b, job, test)
+            detail = None if log is None else {"seen": log["seen"]}
+            if log is not None:
+                log["wrapped"] += [(k, wide[k], test[k]) for k in range(2) if wide[k] != test[k]]
+            cost = refine_cost(b, job, test, detail)
             if cost is None:
                 trace.add("invalid_after_valid" if seen_valid else "invalid")
                 continue
             seen_valid = True
             n_valid += 1
+            if log is not None:
+                log["costed"].append((test, cost, detail["sum"], detail["sse"]))
             if cost == best_cost:
                 trace.add("tie")
             if cost < best_cost:
@@ -789,8 +818,9 @@ def refine(b, job, trace=None):
     return best, best_cost, len(record), n_valid
 
 
-def restate_refine(b, traces=None):
-    """the four outputs as svt_hip_wm_refine_batch leaves them, from the byte FILL, and n_valid [n]: the warps the reference runs per job"""
+def restate_refine(b, traces=None, logs=None):
+    """the four outputs as svt_hip_wm_refine_batch leaves them, from the byte FILL, and n_valid [n]: the warps the reference runs per job; logs: a list
+    that receives refine()'s log of every defined job"""
     n = len(b["jobs"])
     fill16, fill32 = np.frombuffer(bytes([FILL] * 2), "<i2")[0], np.frombuffer(bytes([FILL] * 4), "<i4")[0]
     out = {"best_mv": np.full((n, 2), fill16, np.int16), "best_cost": np.full(n, fill32, np.int32), "n_checked": np.full(n, fill32, np.int32).view(np.uint32),
@@ -799,7 +829,10 @@ def restate_refine(b, traces=None):
         out["status"][i] = refine_job_status(b, j)
         if out["status"][i] == ST_OK:
             t = set()
-            mv, cost, tot, n_valid = refine(b, j, t)
+            log = None if logs is None else {}
+            mv, cost, tot, n_valid = refine(b, j, t, log)
+            if logs is not None:
+                logs.append(log)
             out["best_mv"][i], out["best_cost"][i], out["n_checked"][i], out["n_valid"][i] = mv, cost, tot, n_valid
             if traces is not None:
                 traces.append(t)

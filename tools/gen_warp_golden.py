@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Writes tests/golden/warp.npz: the reference encoder's own warped-motion results on the cases of tests/warp_cases.py.
+"""Writes tests/golden/warp.npz and tests/golden/warp_edges.npz: the reference encoder's own warped-motion results on the cases of tests/warp_cases.py
+and of tests/warp_edge_cases.py (the same harness; per refinement the best MV, tot_checked_pos and the warp count, a CRC-32 per fit and per
+predicted block).
 
 Run by hand on a machine that has the reference's sources (--ref: the root of its source tree) and a built libsvthip.so (the restatement takes
 the filter table from it; no GPU is needed); never by the tests, build(), smoke() or bench.py.  It compiles a harness of its own into a temporary
@@ -42,6 +44,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import warp_cases as wc  # noqa: E402
+import warp_edge_cases as ec  # noqa: E402
 
 HARNESS = r"""
 #define RTCD_C
@@ -299,7 +302,8 @@ def reference_block(L, b, j):
     for r in range(2 if comp else 1):
         plane, ox, oy, pw, ph = b["planes"][int(j["ref"][r])]
         pics.append(np.ascontiguousarray(plane[oy:oy + ph, ox:ox + pw], dtype=np.uint16))
-    m = [model_words(j["model"][r]) for r in range(2)]
+    from_array = (wc.MODEL0_FROM_ARRAY, wc.MODEL1_FROM_ARRAY)
+    m = [model_words(b["models"][int(j["model_index"][r])] if int(j["flags"]) & from_array[r] else j["model"][r]) for r in range(2)]
     out = np.full((h, w), 0xEEEE, np.uint16)
     pw, ph = pics[0].shape[1], pics[0].shape[0]
     rc = L.harness_warp(int(bd > 8), m[0].ctypes.data, m[1].ctypes.data, (1 + int(j["comp_mode"])) if comp else 0, int(j["fwd_offset"]), int(j["bck_offset"]),
@@ -321,6 +325,89 @@ def search_small_determinant():
         a00, a11, a01 = sq(s[..., 0]).sum(1), sq(s[..., 1]).sum(1), p1(s[..., 0], s[..., 1]).sum(1)
         best = min(best, int(np.abs(a00 * a11 - a01 * a01).min()))
     return best
+
+
+def reference_fits(L, b, models, status, bad):
+    """MODEL_DTYPE records of the reference's fit on the batch; the jobs on which the restatement (models, status) differs are added to `bad`"""
+    name = b["name"]
+    ref = np.zeros(len(models), wc.MODEL_DTYPE)
+    for i, j in enumerate(b["jobs"]):
+        mv = b["mv_array"][int(j["mv_index"])] if int(j["flags"]) & wc.MV_FROM_ARRAY else j["mv"]
+        o = np.zeros(12, np.int32)
+        pts, inref = np.ascontiguousarray(j["pts"], np.int32), np.ascontiguousarray(j["pts_inref"], np.int32)
+        ref[i]["wmtype"] = wc.AFFINE
+        if int(j["n_samples"]):  # the host half returns before the fit without samples
+            rc = L.harness_fit(pts.ctypes.data, inref.ctypes.data, int(j["n_samples"]), int(j["bwidth"]), int(j["bheight"]), int(mv[0]), int(mv[1]),
+                               int(j["blk_org_x"]), int(j["blk_org_y"]), b["shut_approx"], b["lower_band_th"], b["upper_band_th"], o.ctypes.data)
+            assert rc == 0
+            ref[i]["valid"], ref[i]["num_samples"] = o[0], o[1]
+            if o[0]:
+                ref[i]["wmmat"] = o[2:8]
+                ref[i]["alpha"], ref[i]["beta"], ref[i]["gamma"], ref[i]["delta"] = o[8:12]
+        if status[i] != wc.ST_OK or ref[i].tobytes() != models[i].tobytes():
+            bad.append((name, i))
+    return ref
+
+
+def reference_refinements(L, b, want, bad):
+    """[n][4] of svt_aom_wm_motion_refinement on the batch: best row, col, the positions tested, the positions warped; the jobs on which the
+    restatement (want) differs are added to `bad`"""
+    name = b["name"]
+    ref = np.zeros((len(b["jobs"]), 4), np.int32)
+    settings = np.array([b["settings"][k] for k in wc.SETTING_KEYS], np.int32)
+    jc, tr, tc = (np.ascontiguousarray(t, np.int32) for t in b["cost_tables"])
+    for i, j in enumerate(b["jobs"]):
+        if want["status"][i] != wc.ST_OK:
+            raise RuntimeError(f"refine {name} job {i} is not defined")
+        start = b["mv_array"][int(j["mv_index"])] if int(j["flags"]) & wc.WM_START_FROM_ARRAY else j["start_mv"]
+        geom = np.array([j["blk_org_x"], j["blk_org_y"], j["bwidth"], j["bheight"], j["n_samples"], start[0], start[1], j["pred_mv"][0], j["pred_mv"][1]], np.int32)
+        plane, ox, oy, pw, ph = b["planes"][int(j["ref"])]
+        pic = np.ascontiguousarray(plane[oy:oy + ph, ox:ox + pw], np.uint8)
+        src = np.ascontiguousarray(b["src"], np.uint8)
+        pts, inref = np.ascontiguousarray(j["pts"], np.int32), np.ascontiguousarray(j["pts_inref"], np.int32)
+        o = np.zeros(5, np.int32)
+        rc = L.harness_refine(settings.ctypes.data, geom.ctypes.data, pts.ctypes.data, inref.ctypes.data, src.ctypes.data + int(j["src_offset"]), src.shape[1],
+                              pic.ctypes.data, pw, ph, jc.ctypes.data, tr.ctypes.data, tc.ctypes.data, o.ctypes.data)
+        if rc or o[4] != 1:
+            raise RuntimeError(f"harness_refine: {rc}, returned {o[4]}")
+        ref[i] = o[:4]
+        got = (int(want["best_mv"][i][0]), int(want["best_mv"][i][1]), int(want["n_checked"][i]), int(want["n_valid"][i]))
+        if tuple(int(v) for v in o[:4]) != got:
+            bad.append((name, i, tuple(int(v) for v in o[:4]), got))
+    return ref
+
+
+def generate_edges(L):
+    """the arrays of golden/warp_edges.npz: the cases of tests/warp_edge_cases.py through the same harness"""
+    out, bad = {}, []
+    for name in ec.REFINE_EDGE_BATCHES:
+        out[f"refine_{name}"] = reference_refinements(L, ec.refine_edge_batch(name), ec.restated_refine_edge(name)[0], bad)
+    if bad:
+        raise RuntimeError(f"the refinement restatement differs from the reference on {len(bad)} edge jobs, first: {bad[:6]}")
+    models, status, _ = ec.restated_far()
+    out["fit_far"] = wc.models_crc(reference_fits(L, ec.far_batch(), models, status, bad), status)
+    if bad:
+        raise RuntimeError(f"the fit restatement differs from the reference on {len(bad)} jobs of the far batch, first: {bad[:8]}")
+    for name in ec.pred_edge_names():
+        b = ec.pred_edge_batch(name)
+        _, status, blocks = ec.restated_pred_edge(name)
+        crcs = np.zeros(len(b["jobs"]), np.uint32)
+        for i, j in enumerate(b["jobs"]):
+            if status[i] != wc.ST_OK:
+                raise RuntimeError(f"{name} job {i} is not defined")
+            ref = reference_block(L, b, j)
+            if not np.array_equal(ref, blocks[i]):
+                bad.append((name, i, int(np.count_nonzero(ref != blocks[i]))))
+            crcs[i] = wc.block_crc(ref)
+        out[f"crc_{name}"] = crcs
+    if bad:
+        raise RuntimeError(f"the prediction restatement differs from the reference on {len(bad)} edge jobs, first: {bad[:8]}")
+    missing = ec.edge_coverage_missing()
+    if missing:
+        raise RuntimeError(f"edge coverage conditions not met: {missing}")
+    print(f"edges: {sum(len(out[k]) for k in out if k.startswith('refine_'))} refinements (the wrap batches included: the reference's own function takes them), "
+          f"{len(out['fit_far'])} fits and {sum(len(out[k]) for k in out if k.startswith('crc_'))} prediction jobs, the restatements equal to the reference on all of them")
+    return out
 
 
 def generate(L):
@@ -353,53 +440,15 @@ def generate(L):
         raise RuntimeError(f"the prediction restatement differs from the reference on {len(mismatch)} jobs, first: {mismatch[:8]}")
     n_fits, bad = 0, []
     for name in wc.MODEL_BATCHES:
-        b = wc.model_batch(name)
         models, status, _ = wc.restated_models(name)
-        ref = np.zeros(len(models), wc.MODEL_DTYPE)
-        for i, j in enumerate(b["jobs"]):
-            mv = b["mv_array"][int(j["mv_index"])] if int(j["flags"]) & wc.MV_FROM_ARRAY else j["mv"]
-            o = np.zeros(12, np.int32)
-            pts, inref = np.ascontiguousarray(j["pts"], np.int32), np.ascontiguousarray(j["pts_inref"], np.int32)
-            ref[i]["wmtype"] = wc.AFFINE
-            if int(j["n_samples"]):  # the host half returns before the fit without samples
-                rc = L.harness_fit(pts.ctypes.data, inref.ctypes.data, int(j["n_samples"]), int(j["bwidth"]), int(j["bheight"]), int(mv[0]), int(mv[1]),
-                                   int(j["blk_org_x"]), int(j["blk_org_y"]), b["shut_approx"], b["lower_band_th"], b["upper_band_th"], o.ctypes.data)
-                assert rc == 0
-                ref[i]["valid"], ref[i]["num_samples"] = o[0], o[1]
-                if o[0]:
-                    ref[i]["wmmat"] = o[2:8]
-                    ref[i]["alpha"], ref[i]["beta"], ref[i]["gamma"], ref[i]["delta"] = o[8:12]
-            if status[i] != wc.ST_OK or ref[i].tobytes() != models[i].tobytes():
-                bad.append((name, i))
+        ref = reference_fits(L, wc.model_batch(name), models, status, bad)
         out[f"fit_{name}"] = wc.models_crc(ref, status)
         n_fits += len(ref)
     if bad:
         raise RuntimeError(f"the fit restatement differs from the reference on {len(bad)} jobs, first: {bad[:8]}")
     n_refine, bad = 0, []
     for name in wc.REFINE_BATCHES:
-        b = wc.refine_batch(name)
-        want, _ = wc.restated_refine(name)
-        ref = np.zeros((len(b["jobs"]), 4), np.int32)  # best row, col, the positions tested, the positions warped
-        settings = np.array([b["settings"][k] for k in wc.SETTING_KEYS], np.int32)
-        jc, tr, tc = (np.ascontiguousarray(t, np.int32) for t in b["cost_tables"])
-        for i, j in enumerate(b["jobs"]):
-            if want["status"][i] != wc.ST_OK:
-                raise RuntimeError(f"refine {name} job {i} is not defined")
-            start = b["mv_array"][int(j["mv_index"])] if int(j["flags"]) & wc.WM_START_FROM_ARRAY else j["start_mv"]
-            geom = np.array([j["blk_org_x"], j["blk_org_y"], j["bwidth"], j["bheight"], j["n_samples"], start[0], start[1], j["pred_mv"][0], j["pred_mv"][1]], np.int32)
-            plane, ox, oy, pw, ph = b["planes"][int(j["ref"])]
-            pic = np.ascontiguousarray(plane[oy:oy + ph, ox:ox + pw], np.uint8)
-            src = np.ascontiguousarray(b["src"], np.uint8)
-            pts, inref = np.ascontiguousarray(j["pts"], np.int32), np.ascontiguousarray(j["pts_inref"], np.int32)
-            o = np.zeros(5, np.int32)
-            rc = L.harness_refine(settings.ctypes.data, geom.ctypes.data, pts.ctypes.data, inref.ctypes.data, src.ctypes.data + int(j["src_offset"]), src.shape[1],
-                                  pic.ctypes.data, pw, ph, jc.ctypes.data, tr.ctypes.data, tc.ctypes.data, o.ctypes.data)
-            if rc or o[4] != 1:
-                raise RuntimeError(f"harness_refine: {rc}, returned {o[4]}")
-            ref[i] = o[:4]
-            got = (int(want["best_mv"][i][0]), int(want["best_mv"][i][1]), int(want["n_checked"][i]), int(want["n_valid"][i]))
-            if tuple(int(v) for v in o[:4]) != got:
-                bad.append((name, i, tuple(int(v) for v in o[:4]), got))
+        ref = reference_refinements(L, wc.refine_batch(name), wc.restated_refine(name)[0], bad)
         out[f"refine_{name}"] = ref
         n_refine += len(ref)
     if bad:
@@ -432,14 +481,19 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare with the committed fixture instead of writing it")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
-        out = generate(build(a.ref, tmp))
+        L = build(a.ref, tmp)
+        outs = [(wc.GOLDEN, generate(L)), (ec.GOLDEN, generate_edges(L))]
     if a.check:
-        z = np.load(wc.GOLDEN)
-        bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-        print("identical" if not bad else f"differs: {bad}")
-        sys.exit(1 if bad else 0)
-    save(wc.GOLDEN, out)
-    print(f"wrote {wc.GOLDEN} ({os.path.getsize(wc.GOLDEN)} bytes), {len(out)} arrays")
+        differs = False
+        for path, out in outs:
+            z = np.load(path)
+            bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
+            print(f"{os.path.basename(path)}: " + ("identical" if not bad else f"differs: {bad}"))
+            differs = differs or bool(bad)
+        sys.exit(1 if differs else 0)
+    for path, out in outs:
+        save(path, out)
+        print(f"wrote {path} ({os.path.getsize(path)} bytes), {len(out)} arrays")
 
 
 if __name__ == "__main__":
