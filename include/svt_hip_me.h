@@ -183,6 +183,10 @@ int   svt_hip_context_sync(SvtHipContext *ctx);
  * mode-decision kernels of earlier pictures on another context's stream beside the ME launch -- as the reference runs its ME and
  * mode-decision processes side by side -- lowers it so that both find LDS and registers on every CU. */
 int   svt_hip_context_set_me_waves_per_cu(SvtHipContext *ctx, uint32_t waves);
+/* Upper limit of the persistent ME waves of a whole launch, every kernel of its chain (0 = none, the default).  The limit per CU cannot
+ * go below one wave on each CU; this one can, for a caller that wants the ME launch to stay on a corner of the chip -- and for tests: with
+ * fewer waves than pictures, every wave walks blocks of several pictures of one launch. */
+int   svt_hip_context_set_me_max_waves(SvtHipContext *ctx, uint32_t waves);
 /* The dense pre-pass of the ME launches of this context (on by default; the environment variable SVT_HIP_ME_DENSE=0 turns it off at
  * context creation): the pre-HME strips (prehme_core, Codec/motion_estimation.c:1568-1666) and the HME level-0 regions (hme_level_0,
  * :820-920) of every block -- searches whose windows depend on the block position and the picture distance only -- are made by a kernel of

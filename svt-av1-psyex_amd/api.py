@@ -120,6 +120,14 @@ class Context:
         """with the pre-pass on: the per-block pipeline as a chain of small kernels (svt_hip_context_set_me_staged): 0 never, 1 launches of many blocks (default), 2 always; results are identical either way"""
         self.check(lib().svt_hip_context_set_me_staged(self._h, int(on)), "svt_hip_context_set_me_staged")
 
+    def set_me_waves_per_cu(self, waves):
+        """upper limit of the persistent ME waves per CU (svt_hip_context_set_me_waves_per_cu); 0: as many as fit"""
+        self.check(lib().svt_hip_context_set_me_waves_per_cu(self._h, int(waves)), "svt_hip_context_set_me_waves_per_cu")
+
+    def set_me_max_waves(self, waves):
+        """upper limit of the persistent ME waves of a whole launch (svt_hip_context_set_me_max_waves); 0: none"""
+        self.check(lib().svt_hip_context_set_me_max_waves(self._h, int(waves)), "svt_hip_context_set_me_max_waves")
+
     def set_me_timing(self, on):
         """ME launches record events around the kernels of their chain (svt_hip_context_set_me_timing)"""
         self.check(lib().svt_hip_context_set_me_timing(self._h, 1 if on else 0), "svt_hip_context_set_me_timing")

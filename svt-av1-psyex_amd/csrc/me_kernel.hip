@@ -59,6 +59,21 @@ constexpr int kWinBytes = SVT_HIP_ME_WIN_BYTES; // LDS window arena of a wave
 constexpr int kSrc64Pitch = 80, kSrc32Pitch = 48, kSrc16Pitch = 16; // LDS row pitches of the source views: block rows 2 apart land on different banks
 constexpr int kNarrowMaxPos = 32; // searches with at most this many positions are split by block row instead
 
+// ---- the control code's memory diet (profiles/r12_me_control_before_after.txt): one switch per part, so that each can be
+// timed alone.  1 = the shipped form.
+#ifndef SVT_HIP_ME_REFTAB
+#define SVT_HIP_ME_REFTAB 1 /* 0: the lane-parallel stage code indexes the launch parameters per lane (vector loads and full waits) */
+#endif
+#ifndef SVT_HIP_ME_REFTAB_FULL
+#define SVT_HIP_ME_REFTAB_FULL 1 /* 0: the one-kernel form keeps its reads of the parameter block */
+#endif
+#ifndef SVT_HIP_ME_CALC_MAPS
+#define SVT_HIP_ME_CALC_MAPS 1 /* 0: z-order -> raster and the parent maps are looked up in the tables below */
+#endif
+#ifndef SVT_HIP_ME_LEAN_EPILOGUE
+#define SVT_HIP_ME_LEAN_EPILOGUE 1 /* 0: the epilogue stores its rows stage by stage, candidate flags in an array (scratch), wave sums as ds_bpermute butterflies */
+#endif
+
 // z_to_raster, motion_estimation.c:2520-2531: n_idx (quad-tree order) -> raster-within-depth PU index
 __device__ const uint8_t c_z_to_raster[85] = {
     0,  1,  2,  3,  4,  5,  6,  9,  10, 7,  8,  11, 12, 13, 14, 17, 18, 15, 16, 19, 20, 21, 22, 29, 30, 23, 24, 31, 32,
@@ -69,6 +84,36 @@ __device__ const uint8_t c_8x8_to_16x16[64] = {5,  5,  6,  6,  7,  7,  8,  8,  5
                                                12, 12, 9,  9,  10, 10, 11, 11, 12, 12, 13, 13, 14, 14, 15, 15, 16, 16, 13, 13, 14, 14,
                                                15, 15, 16, 16, 17, 17, 18, 18, 19, 19, 20, 20, 17, 17, 18, 18, 19, 19, 20, 20};
 __device__ const uint8_t c_16x16_to_32x32[16] = {1, 1, 2, 2, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 4, 4};
+
+// The same three maps as arithmetic: inside a depth the quad-tree index interleaves the bits of the PU's column and row (x0 y0 x1 y1 ..),
+// and a PU's parent is the PU of the depth above at half its column and row.  A table read with a lane index is a vector byte load and a
+// full wait in the middle of the epilogue; these are a handful of bit operations.  Proved equal to the tables below, index by index.
+__host__ __device__ constexpr int pu_z_to_raster(int n) {
+    if (n < 5) return n;
+    const int base = n < 21 ? 5 : 21, i = n - base, dim_log = n < 21 ? 2 : 3;
+    const int x = (i & 1) | ((i >> 1) & 2) | ((i >> 2) & 4), y = ((i >> 1) & 1) | ((i >> 2) & 2) | ((i >> 3) & 4);
+    return base + (y << dim_log) + x;
+}
+__host__ __device__ constexpr int pu_8x8_to_16x16(int i) { return 5 + ((i >> 4) << 2) + ((i & 7) >> 1); }  // i: raster index inside the 8x8 depth
+__host__ __device__ constexpr int pu_16x16_to_32x32(int i) { return 1 + ((i >> 3) << 1) + ((i & 3) >> 1); } // i: raster index inside the 16x16 depth
+namespace map_proof {
+constexpr uint8_t z[85] = {0,  1,  2,  3,  4,  5,  6,  9,  10, 7,  8,  11, 12, 13, 14, 17, 18, 15, 16, 19, 20, 21, 22, 29, 30, 23, 24, 31, 32,
+                           37, 38, 45, 46, 39, 40, 47, 48, 25, 26, 33, 34, 27, 28, 35, 36, 41, 42, 49, 50, 43, 44, 51, 52, 53, 54, 61, 62, 55,
+                           56, 63, 64, 69, 70, 77, 78, 71, 72, 79, 80, 57, 58, 65, 66, 59, 60, 67, 68, 73, 74, 81, 82, 75, 76, 83, 84};
+constexpr uint8_t p16[64] = {5,  5,  6,  6,  7,  7,  8,  8,  5,  5,  6,  6,  7,  7,  8,  8,  9,  9,  10, 10, 11, 11, 12, 12, 9,  9,  10, 10, 11, 11, 12, 12,
+                             13, 13, 14, 14, 15, 15, 16, 16, 13, 13, 14, 14, 15, 15, 16, 16, 17, 17, 18, 18, 19, 19, 20, 20, 17, 17, 18, 18, 19, 19, 20, 20};
+constexpr uint8_t p32[16] = {1, 1, 2, 2, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 4, 4};
+constexpr bool equal() {
+    for (int n = 0; n < 85; n++) if (pu_z_to_raster(n) != z[n]) return false;
+    for (int i = 0; i < 64; i++) if (pu_8x8_to_16x16(i) != p16[i]) return false;
+    for (int i = 0; i < 16; i++) if (pu_16x16_to_32x32(i) != p32[i]) return false;
+    return true;
+}
+static_assert(equal(), "the computed PU maps are the reference's tables (motion_estimation.c:2520-2531, definitions.h:2613-2632)");
+} // namespace map_proof
+__device__ __forceinline__ int z_to_raster(int n) { return SVT_HIP_ME_CALC_MAPS ? pu_z_to_raster(n) : (int)c_z_to_raster[n]; }
+__device__ __forceinline__ int parent_16x16(int i) { return SVT_HIP_ME_CALC_MAPS ? pu_8x8_to_16x16(i) : (int)c_8x8_to_16x16[i]; }
+__device__ __forceinline__ int parent_32x32(int i) { return SVT_HIP_ME_CALC_MAPS ? pu_16x16_to_32x32(i) : (int)c_16x16_to_32x32[i]; }
 
 typedef unsigned long long u64;
 
@@ -153,7 +198,26 @@ struct St { // per-block state (subset of MeContext, me_context.h:366-509)
     int      job, tf_exit;
 };
 
-// A wave's LDS slice: St, the three source views, best_sad[n_slot][85] and best_mv[n_slot][85] (MeContext.p_sb_best_sad /
+// What the lane-parallel stage code wants to know about (list, reference) slot li * 4 + ri of the picture the wave is working on, in LDS.
+// The stages' lanes stand for a (list, reference) pair, strip or region, so an index into the launch parameters is a LANE value there: the
+// compiler can no longer fetch p.ref[li][ri], desc.ref_picture_number[li][ri] or desc.num_of_ref_pic_to_search[li] with a scalar load and
+// turns each into a vector load plus a full wait on the block's dependent chain (a hit in the cache, about 0.2 k clocks each, 18 - 25 of them per
+// block: profiles/r12_me_phase_table.txt).  From here the same read is a ds_read at a constant offset.  The wave fills the table when a job's picture is not the picture of its
+// previous job (me_b64_body); everything in it follows from the picture's parameter block alone.
+struct RefEnt {
+    DevPlane lvl[3];           // p.ref[li][ri].lvl[]
+    uint32_t dist, sdist;      // ref_distance(p, li, ri) and scaled_distance() of it
+    uint16_t gm_dist;          // the distance perform_gm_detection takes (its own casts, by input resolution)
+    uint8_t  live, srch;       // li < num_of_list_to_search && ri < num_of_ref_pic_to_search[li]; searched(p, li)
+    int16_t  ph_w[2], ph_h[2]; // prehme_size() of the two pre-HME strips (cfg.prehme_sa_cfg[] x the scaled distance)
+    uint32_t pad;
+};
+struct RefTab { RefEnt ent[SVT_HIP_MAX_LISTS * SVT_HIP_MAX_REFS]; };
+static_assert(SVT_HIP_MAX_LISTS == 2 && SVT_HIP_MAX_REFS == 4, "slot = li * 4 + ri, eight of them");
+static_assert(sizeof(RefTab) % 16 == 0 && sizeof(RefTab) <= 1024, "the table's budget: 1 KB of a wave's slice");
+__host__ __device__ constexpr bool me_has_reftab(int mode); // the kernels that run control code (below, with the modes)
+
+// A wave's LDS slice: St, the reference table (one-kernel form; mid1 and the tail keep it inside St: me_reftab_off), the three source views, best_sad[n_slot][85] and best_mv[n_slot][85] (MeContext.p_sb_best_sad /
 // p_sb_best_mv of the (list, reference) pairs the launch's pictures search: n_slot = the largest count among them), the window
 // arena.  When every picture of the launch sub-samples both the HME and the integer search (SUB_SAD_SEARCH: every other row),
 // the source views keep their even rows only (cshift = 1): row r of a view lives at row r >> cshift.
@@ -179,13 +243,32 @@ constexpr int kMeFull = 0, kMeMid1 = 1, kMeS1 = 2, kMeMid2 = 4, kMeS2 = 5, kMeTa
 constexpr uint32_t kListWavesPerCu = SVT_HIP_ME_LIST_WAVES_PER_CU;
 constexpr uint32_t kStagedMinJobs = 2048; // blocks of a launch from which the staged form is used (measured at 4,080 blocks -- a rank's share at 8 GPUs: 0.58 ms staged, 0.59 ms one-kernel; at 8,160: 0.75 / 0.80)
 __host__ __device__ constexpr bool me_is_search(int m) { return m == kMeS1 || m == kMeS2; }
+// (mid2 runs control code too, but reads three such values per block: with the table it measured 1 - 2 us per launch SLOWER -- the fill and 13 more
+// VGPRs against three loads -- so it keeps its reads of the parameter block; profiles/r12_me_control_before_after.txt)
+#ifndef SVT_HIP_ME_REFTAB_MID2
+#define SVT_HIP_ME_REFTAB_MID2 0
+#endif
+__host__ __device__ constexpr bool me_has_reftab(int m) {
+    return SVT_HIP_ME_REFTAB && (m == kMeFull ? SVT_HIP_ME_REFTAB_FULL != 0 : m == kMeMid2 ? SVT_HIP_ME_REFTAB_MID2 != 0 : !me_is_search(m));
+}
+// Where the table lives -- a compile-time address either way.  The kernels of the staged form that carry it (mid1, tail; mid2 if switched on)
+// never plan tiles: run_searches is compiled out of them, St.tile[] is 1280 idle bytes, and the table lies THERE -- no LDS of its own, the
+// tail's slice is what it was (bench launch: 18,448 B, 128-byte granules: 18,560 B x 8 waves = 148,480 B of the CU's 163,840; with four
+// references and even rows only 19,808 B, where 960 B more would have cost the eighth wave).  The one-kernel form plans tiles between its
+// control stages, so there the table follows St: 960 B per wave in the form of small launches and deferred blocks, which never fills a CU.
+constexpr uint32_t kStEnd = (uint32_t)((sizeof(St) + 15) & ~(size_t)15);
+__host__ __device__ constexpr bool me_reftab_in_tiles(int m) { return m != kMeFull; }
+__host__ __device__ constexpr uint32_t me_reftab_off(int m) { return me_reftab_in_tiles(m) ? (uint32_t)offsetof(St, tile) : kStEnd; }
+static_assert(offsetof(St, tile) % 16 == 0 && sizeof(RefTab) <= sizeof(TileEnt) * kMaxTiles, "the table fits the idle tile entries");
+static_assert(offsetof(St, tile) >= ((offsetof(St, req) + 15) & ~(size_t)15) + kMaxReq * sizeof(Req) && offsetof(St, tile) >= offsetof(St, req_key) + kMaxReq * sizeof(u64),
+              "no batch destination of the staged kernels (record head, requests, keys) reaches the tile entries");
 constexpr int kDirectWinBytes = 5120; // the direct searches' arena: a step's 64 x 5 window pieces, then the per-position sums [kMaxReq][kNarrowMaxPos] u32
 __host__ __device__ constexpr LdsLayout lds_layout(int n_slot, int cshift, int dense = 1, int mode = 0) {
     const bool v16 = mode == kMeFull, v32 = mode == kMeFull || mode == kMeS1, v64 = mode == kMeFull || mode == kMeS2 || mode == kMeTail;
     const bool best = mode == kMeFull || mode == kMeTail, slots = dense && (mode == kMeFull || mode == kMeMid1);
     const uint32_t arena = (mode == kMeMid1 || mode == kMeMid2) ? 0u : (mode == kMeS1 || mode == kMeS2) ? (uint32_t)kDirectWinBytes : (uint32_t)kWinBytes;
     LdsLayout l = {};
-    l.src16 = (uint32_t)((sizeof(St) + 15) & ~(size_t)15);
+    l.src16 = kStEnd + (me_has_reftab(mode) && !me_reftab_in_tiles(mode) ? (uint32_t)sizeof(RefTab) : 0u);
     l.src32 = l.src16 + (v16 ? (uint32_t)((16 >> cshift) * kSrc16Pitch) : 0u);
     l.src64 = l.src32 + (v32 ? (uint32_t)((32 >> cshift) * kSrc32Pitch) : 0u);
     l.bsad  = l.src64 + (v64 ? (uint32_t)((64 >> cshift) * kSrc64Pitch) : 0u);
@@ -226,7 +309,8 @@ __device__ __forceinline__ void clip_axis(int org, int &origin, int &size, int p
     if (org + origin + size > dim) size = imax(1, size - ((org + origin + size) - dim));
 }
 
-__device__ __forceinline__ const uint8_t *plane_at(CPlane &pl, int x, int y) {
+// (PL: a plane of the parameter block -- constant address space, scalar loads -- or of the wave's reference table in LDS)
+template <class PL> __device__ __forceinline__ const uint8_t *plane_at(PL &pl, int x, int y) {
     return pl.base + (long long)(pl.org_y + y) * pl.stride + (pl.org_x + x);
 }
 
@@ -1056,7 +1140,7 @@ __device__ __forceinline__ void push_req(St &st, const uint8_t *win, uint32_t st
 }
 
 // The svt_sad_loop_kernel call made by the HME levels and pre-HME (e.g. motion_estimation.c:891-909)
-__device__ __forceinline__ void push_hme_req(St &st, CParams &p, int level, CPlane &rp, int org_x, int org_y,
+template <class PL> __device__ __forceinline__ void push_hme_req(St &st, CParams &p, int level, PL &rp, int org_x, int org_y,
                                              int bw, int bh, int ox, int oy, int sa_w, int sa_h, int skip, int slot = -1) {
     const int full = (p.cfg.hme_search_method == 1);
     push_req(st, plane_at(rp, org_x + ox, org_y + oy), rp.stride, sa_w, sa_h, bw, full ? bh : (bh >> 1), full ? 1 : 2, level, skip, slot);
@@ -1412,10 +1496,9 @@ template <class P> __host__ __device__ __forceinline__ void prehme_size(P &p, in
     sa_w = (int16_t)(uint16_t)imin((int)(c.prehme_sa_cfg[sri].sa_min.width * f), c.prehme_sa_cfg[sri].sa_max.width);
     sa_h = (int16_t)(uint16_t)imin((int)(c.prehme_sa_cfg[sri].sa_min.height * f), c.prehme_sa_cfg[sri].sa_max.height);
 }
-__device__ __forceinline__ SearchGeo prehme_geometry(CParams &p, int li, int ri, int sri, uint32_t org_x, uint32_t org_y) {
-    int sa_w, sa_h;
-    prehme_size(p, li, ri, sri, sa_w, sa_h);
-    CPlane &rp = p.ref[li][ri].lvl[0];
+// (the per-block kernels take the strip's size and the plane from the wave's reference table, the pre-pass from the parameter block: one
+// body, so that both sides arrive at the same geometry and dense_take matches)
+template <class PL> __device__ __forceinline__ SearchGeo prehme_geometry_sized(PL &rp, int sa_w, int sa_h, uint32_t org_x, uint32_t org_y) {
     const int ox16 = (int16_t)org_x >> 2, oy16 = (int16_t)org_y >> 2;
     int ox = -(int16_t)(sa_w >> 1), oy = -(int16_t)(sa_h >> 1);
     clip_axis(ox16, ox, sa_w, rp.org_x - 1, rp.width);
@@ -1423,9 +1506,14 @@ __device__ __forceinline__ SearchGeo prehme_geometry(CParams &p, int li, int ri,
     SearchGeo g = {ox, oy, sa_w, sa_h};
     return g;
 }
+__device__ __forceinline__ SearchGeo prehme_geometry(CParams &p, int li, int ri, int sri, uint32_t org_x, uint32_t org_y) {
+    int sa_w, sa_h;
+    prehme_size(p, li, ri, sri, sa_w, sa_h);
+    return prehme_geometry_sized(p.ref[li][ri].lvl[0], sa_w, sa_h, org_x, org_y);
+}
 
 // hme_level_0/1/2 geometry (motion_estimation.c:820-1113); org_x / org_y = the block's origin on the level's plane
-__device__ __forceinline__ SearchGeo hme_level_geometry(CParams &p, int level, CPlane &rp, int org_x, int org_y, int sa_w, int sa_h, int cx, int cy, int sr_w, int sr_h) {
+template <class PL> __device__ __forceinline__ SearchGeo hme_level_geometry(CParams &p, int level, PL &rp, int org_x, int org_y, int sa_w, int sa_h, int cx, int cy, int sr_w, int sr_h) {
     sa_w = (int16_t)((sa_w + 7) & ~7);
     int pad_w, pad_h, ox, oy;
     if (level == 2) { pad_w = pad_h = 63; } else { pad_w = rp.org_x - 1; pad_h = rp.org_y - 1; }
@@ -1445,8 +1533,30 @@ __device__ __forceinline__ SearchGeo hme_level_geometry(CParams &p, int level, C
 
 struct HmeGeom { int16_t ox, oy; };
 
+// The control code's wave sums (every lane active).  The butterfly form is six ds_bpermute round trips in a row -- twelve for a 64-bit sum --
+// on the block's dependent chain; the DPP form never leaves the SIMD.  Same sums: 32-bit ones wrap alike, and a 64-bit one is added up in
+// three pieces of 24, 24 and 16 bits -- 64 of which cannot overflow 32 bits -- and put together again modulo 2^64.
+__device__ __forceinline__ uint32_t ctrl_sum32(uint32_t v) { return SVT_HIP_ME_LEAN_EPILOGUE ? wave_sum_dpp(v) : wave_sum(v); }
+__device__ __forceinline__ u64 ctrl_sum64(u64 v) {
+    if (!SVT_HIP_ME_LEAN_EPILOGUE) return wave_sum(v);
+    const u64 lo = wave_sum_dpp((uint32_t)v & 0xFFFFFFu), mid = wave_sum_dpp((uint32_t)(v >> 24) & 0xFFFFFFu), hi = wave_sum_dpp((uint32_t)(v >> 48));
+    return (hi << 48) + (mid << 24) + lo;
+}
+
+// Which (list, reference) pairs still take part in a PU's candidates: a bit per pair in a register -- or (MASK = false) the array form, which an
+// index that differs from lane to lane sends to scratch memory, a load and a wait per element.
+template <bool MASK> struct RefFlags {
+    uint32_t m = 0;
+    uint8_t  a[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    __device__ __forceinline__ bool get(int li, int ri) const { if constexpr (MASK) return (m >> (li * 4 + ri)) & 1u; else return a[li][ri] != 0; }
+    __device__ __forceinline__ void set(int li, int ri, bool v) {
+        if constexpr (MASK) m = (m & ~(1u << (li * 4 + ri))) | ((uint32_t)v << (li * 4 + ri));
+        else a[li][ri] = (uint8_t)v;
+    }
+};
+
 // hme_level_0/1/2: pushes the search and returns its origin
-__device__ HmeGeom push_hme_level(St &st, CParams &p, int level, CPlane &rp, int org_x, int org_y, int bw, int bh,
+template <class PL> __device__ __forceinline__ HmeGeom push_hme_level(St &st, CParams &p, int level, PL &rp, int org_x, int org_y, int bw, int bh,
                                   int sa_w, int sa_h, int cx, int cy, int sr_w, int sr_h, int slot = -1) {
     const SearchGeo sg = hme_level_geometry(p, level, rp, org_x, org_y, sa_w, sa_h, cx, cy, sr_w, sr_h);
     push_hme_req(st, p, level, rp, org_x, org_y, bw, bh, sg.ox, sg.oy, sg.sa_w, sg.sa_h, 0, slot);
@@ -1462,7 +1572,7 @@ __device__ __forceinline__ void key_to_result(u64 key, int full, uint32_t &sad, 
 }
 
 // zero-MV style SAD request: svt_nxm_sad_kernel on every other row (get_zz_sad, motion_estimation.c:1667-1689)
-__device__ __forceinline__ void push_zz_req(St &st, CPlane &rp, int dx, int dy, int slot = -1) {
+template <class PL> __device__ __forceinline__ void push_zz_req(St &st, PL &rp, int dx, int dy, int slot = -1) {
     push_req(st, plane_at(rp, (int)st.org_x + dx, (int)st.org_y + dy), rp.stride, 1, 1, (int)st.b64_w, (int)st.b64_h >> 1, 2, 2, 0, slot);
 }
 
@@ -1484,6 +1594,9 @@ template <int MODE>
 __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ ghdr, const MeKernelParams *__restrict__ gparams, const uint32_t launch_flags) {
     St     &st = *reinterpret_cast<St *>(g_lds);
     constexpr bool kImports = MODE == kMeMid2 || MODE == kMeTail; // the kernels that take a block's state over from the kernel before
+    constexpr bool kTab = me_has_reftab(MODE);                    // the wave keeps the reference table of its current picture
+    RefTab &tab = *reinterpret_cast<RefTab *>(g_lds + me_reftab_off(MODE));
+    int tab_pic = -1; // the picture the table was filled for (uniform)
     // launch parameters: read-only, uniform addresses -> scalar loads through the constant cache, values in SGPRs
     typedef const SVT_CONST_AS MeBatchHeader CHeader;
     CHeader  &hdr = *(CHeader *)ghdr;
@@ -1592,6 +1705,46 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
 #define BEST_MV(li, ri) (bmv + (((li) ? r0n : 0) + (ri)) * 85)
         const int n_rows   = r0n + (nl > 1 ? d.num_of_ref_pic_to_search[1] : 0);
         uint32_t *const jflag = hdr.job_flags ? hdr.job_flags + gjob : nullptr; // staged launches: how the block travels
+        // ---- the reference table: refilled when the wave moves on to another picture (the first job always fills; a wave walks one band of the
+        // launch's job range, so that is a handful of times per kernel).  Plain loads by the first eight lanes, lane <-> slot; the bytes belong
+        // to the table alone (no direct-to-LDS destination overlaps them) and the previous block's reads of it have retired: a wave's LDS
+        // instructions execute in order, and the block ended with wave_sync().
+        if constexpr (kTab) {
+            if (pic != tab_pic) { // uniform
+                tab_pic = pic;
+                if (tid < SVT_HIP_MAX_LISTS * SVT_HIP_MAX_REFS) {
+                    const int li = tid >> 2, ri = tid & 3;
+                    RefEnt &e = tab.ent[tid];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        CPlane &s = p.ref[li][ri].lvl[k];
+                        e.lvl[k].base = s.base; e.lvl[k].stride = s.stride;
+                        e.lvl[k].org_x = s.org_x; e.lvl[k].org_y = s.org_y; e.lvl[k].width = s.width; e.lvl[k].height = s.height;
+                    }
+                    const uint32_t dist = ref_distance(p, li, ri);
+                    e.dist = dist; e.sdist = scaled_distance(dist);
+                    const u64 a = d.picture_number, bb = d.ref_picture_number[li][ri]; // perform_gm_detection (:2838-2961)
+                    e.gm_dist = d.input_resolution <= 2 ? (uint16_t)iabs((int)(int16_t)((a > bb ? a : bb) - (a < bb ? a : bb))) : (uint16_t)iabs((int)(int16_t)(a - bb));
+                    e.live = (uint8_t)(li < nl && ri < (li ? d.num_of_ref_pic_to_search[1] : d.num_of_ref_pic_to_search[0]));
+                    e.srch = (uint8_t)searched(p, li);
+#pragma unroll
+                    for (int sri = 0; sri < 2; sri++) {
+                        int sa_w, sa_h;
+                        prehme_size(p, li, ri, sri, sa_w, sa_h);
+                        e.ph_w[sri] = (int16_t)sa_w; e.ph_h[sri] = (int16_t)sa_h;
+                    }
+                    e.pad = 0;
+                }
+                wave_sync();
+            }
+        }
+        // a (list, reference) pair seen from a lane: the table, or (switched off) the parameter block indexed per lane
+        auto ref_slot  = [](int li, int ri) { return (li * 4 + ri) & 7; };
+        auto ref_live  = [&](int li, int ri) -> bool { if constexpr (kTab) return tab.ent[ref_slot(li, ri)].live != 0; else return li < nl && ri < d.num_of_ref_pic_to_search[li]; };
+        auto ref_srch  = [&](int li, int ri) -> bool { if constexpr (kTab) return tab.ent[ref_slot(li, ri)].srch != 0; else return searched(p, li); };
+        auto ref_dist  = [&](int li, int ri) -> uint32_t { if constexpr (kTab) return tab.ent[ref_slot(li, ri)].dist; else return ref_distance(p, li, ri); };
+        auto ref_sdist = [&](int li, int ri) -> uint32_t { if constexpr (kTab) return tab.ent[ref_slot(li, ri)].sdist; else return scaled_distance(ref_distance(p, li, ri)); };
+        auto ref_plane = [&](int li, int ri, int k) -> decltype(auto) { if constexpr (kTab) return (tab.ent[ref_slot(li, ri)].lvl[k]); else return (p.ref[li][ri].lvl[k]); };
         if constexpr (me_is_search(MODE)) {
             // the search kernels' form of the batch below: the block's requests, the 16 bytes of its record that hold nreq, and the source view
             constexpr int lvl = MODE == kMeS1 ? 1 : 2, parts = lvl == 1 ? 3 : 5; // pieces of a view row, the last one padding
@@ -1735,8 +1888,8 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         };
         auto zz_post = [&]() { // lane <-> (list, reference); the reference's serial loops become wave reductions
             const int  li = (tid >> 2) & 1, ri = tid & 3;
-            const bool valid = tid < 8 && li < nl && ri < d.num_of_ref_pic_to_search[li];
-            const bool srch  = valid && searched(p, li);
+            const bool valid = tid < 8 && ref_live(li, ri);
+            const bool srch  = valid && ref_srch(li, ri);
             const u64  smask = __ballot(srch);
             uint32_t   z = 0xFFFFFFFFu;
             if (srch) {
@@ -1760,11 +1913,11 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         auto prehme_pre = [&](int bi) { // lane <-> (list, reference, strip) in the reference's loop order; request numbers = prefix count of the pushing lanes
             const int  l_lo = c.prehme_l1_early_exit ? bi : 0, l_hi = c.prehme_l1_early_exit ? bi + 1 : nl;
             const int  li = (tid >> 3) & 1, ri = (tid >> 1) & 3, sri = tid & 1;
-            const bool mine = tid < 16 && li >= l_lo && li < l_hi && ri < d.num_of_ref_pic_to_search[li];
+            const bool mine = tid < 16 && li >= l_lo && li < l_hi && ref_live(li, ri); // (l_hi <= nl)
             bool       push = false;
             if (mine) {
                 st.ph_req[li][ri][sri] = 0;
-                if (searched(p, li)) {
+                if (ref_srch(li, ri)) {
                     PreHme &ph = st.prehme[li][ri][sri];
                     bool    handled = false;
                     // check_prehme_early_exit (:1693-1720)
@@ -1784,9 +1937,11 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
             if (push) {
                 // prehme_core (:1568-1666)
                 PreHme &ph = st.prehme[li][ri][sri];
-                CPlane &rp = p.ref[li][ri].lvl[0];
+                auto &rp = ref_plane(li, ri, 0);
                 const int ox16 = (int16_t)st.org_x >> 2, oy16 = (int16_t)st.org_y >> 2;
-                const SearchGeo sg = prehme_geometry(p, li, ri, sri, st.org_x, st.org_y);
+                SearchGeo sg;
+                if constexpr (kTab) sg = prehme_geometry_sized(rp, tab.ent[ref_slot(li, ri)].ph_w[sri], tab.ent[ref_slot(li, ri)].ph_h[sri], st.org_x, st.org_y);
+                else sg = prehme_geometry(p, li, ri, sri, st.org_x, st.org_y);
                 push_hme_req(st, p, 0, rp, ox16, oy16, (int)st.b64_w >> 2, (int)st.b64_h >> 2, sg.ox, sg.oy, sg.sa_w, sg.sa_h, c.prehme_skip_search_line, slot);
                 st.ph_req[li][ri][sri] = (uint8_t)(slot + 1);
                 dense_take(st, dense_lds, (((li ? r0n : 0) + ri) * kDenseKinds + sri), slot, sg, n_hit, n_miss);
@@ -1798,7 +1953,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         auto prehme_post = [&](int bi) {
             const int  l_lo = c.prehme_l1_early_exit ? bi : 0, l_hi = c.prehme_l1_early_exit ? bi + 1 : nl;
             const int  li = (tid >> 3) & 1, ri = (tid >> 1) & 3, sri = tid & 1;
-            const bool mine = tid < 16 && li >= l_lo && li < l_hi && ri < d.num_of_ref_pic_to_search[li];
+            const bool mine = tid < 16 && li >= l_lo && li < l_hi && ref_live(li, ri); // (l_hi <= nl)
             const int  k = mine ? st.ph_req[li][ri][sri] : 0;
             if (k) {
                 PreHme &ph = st.prehme[li][ri][sri];
@@ -1813,10 +1968,10 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         auto prehme_final = [&]() { // lane <-> (list, reference)
             wave_sync(); // the strips' results
             const int  li = (tid >> 2) & 1, ri = tid & 3;
-            const bool valid = tid < 8 && li < nl && ri < d.num_of_ref_pic_to_search[li];
+            const bool valid = tid < 8 && ref_live(li, ri);
             uint32_t   m = 0xFFFFFFFFu;
             if (valid) {
-                if (searched(p, li)) {
+                if (ref_srch(li, ri)) {
                     m = st.prehme[li][ri][0].sad < st.prehme[li][ri][1].sad ? st.prehme[li][ri][0].sad : st.prehme[li][ri][1].sad;
                 } else { // list 1 of a base-layer picture mirrors list 0 (the reference writes list 1's entries here)
                     for (int sri = 0; sri < 2; sri++) {
@@ -1847,7 +2002,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 region_of(tid, li, ri, h, w);
                 bool push = false;
                 int  sa_w = 0, sa_h = 0;
-                const bool mine = tid < 32 && li < nl && ri < d.num_of_ref_pic_to_search[li] && !(dep && ((li == 0 && ri == 0) != (bi == 0)));
+                const bool mine = tid < 32 && ref_live(li, ri) && !(dep && ((li == 0 && ri == 0) != (bi == 0)));
                 if (mine) {
                     if (h == 0 && w == 0) st.l0_req[li][ri] = 0;
                     bool handled = false;
@@ -1860,15 +2015,15 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                         }
                     }
                     if (!handled && !st.do_ref[li][ri]) { set_region(0, li, ri, w, h, 0, 0, 0xFFFFFFFFu); handled = true; }
-                    if (!handled && searched(p, li)) {
-                        hme_l0_search_area(st, p, li, ri, ref_distance(p, li, ri), sa_w, sa_h);
+                    if (!handled && ref_srch(li, ri)) {
+                        hme_l0_search_area(st, p, li, ri, ref_dist(li, ri), sa_w, sa_h);
                         push = true;
                     }
                 }
                 const u64 mask = __ballot(push);
                 const int slot = __popcll(mask & ((1ull << tid) - 1ull));
                 if (push) {
-                    const HmeGeom g = push_hme_level(st, p, 0, p.ref[li][ri].lvl[0], (int16_t)st.org_x >> 2, (int16_t)st.org_y >> 2, (int)st.b64_w >> 2,
+                    const HmeGeom g = push_hme_level(st, p, 0, ref_plane(li, ri, 0), (int16_t)st.org_x >> 2, (int16_t)st.org_y >> 2, (int)st.b64_w >> 2,
                                                      (int)st.b64_h >> 2, sa_w, sa_h, 0, 0, w, h, slot);
                     st.hx[0][li][ri][w][h] = g.ox; st.hy[0][li][ri][w][h] = g.oy;
                     if (h == 0 && w == 0) st.l0_req[li][ri] = (uint8_t)(slot + 1);
@@ -1883,7 +2038,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
             if (tid < 64) {
                 int li, ri, h, w;
                 region_of(tid, li, ri, h, w);
-                const bool mine = tid < 32 && li < nl && ri < d.num_of_ref_pic_to_search[li] && !(dep && ((li == 0 && ri == 0) != (bi == 0)));
+                const bool mine = tid < 32 && ref_live(li, ri) && !(dep && ((li == 0 && ri == 0) != (bi == 0)));
                 const int  k0   = mine ? st.l0_req[li][ri] : 0;
                 if (k0) {
                     uint32_t sad; int x, y;
@@ -1916,7 +2071,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 region_of(tid, li, ri, h, w);
                 bool push = false;
                 if (tid < 32) st.lvl_req[li][ri][w][h] = 0;
-                if (tid < 32 && li < nl && ri < d.num_of_ref_pic_to_search[li] && searched(p, li)) {
+                if (tid < 32 && ref_live(li, ri) && ref_srch(li, ri)) {
                     bool live = true;
                     if (lvl == 1) {
                         if (c.me_early_exit_th && st.zz_sad[li][ri] < (c.me_early_exit_th >> 2)) { set_region(1, li, ri, w, h, 0, 0, 0); live = false; }
@@ -1934,11 +2089,11 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 if (push) {
                     HmeGeom g;
                     if (lvl == 1)
-                        g = push_hme_level(st, p, 1, p.ref[li][ri].lvl[1], (int16_t)st.org_x >> 1, (int16_t)st.org_y >> 1, (int)st.b64_w >> 1,
+                        g = push_hme_level(st, p, 1, ref_plane(li, ri, 1), (int16_t)st.org_x >> 1, (int16_t)st.org_y >> 1, (int)st.b64_w >> 1,
                                            (int)st.b64_h >> 1, (int16_t)c.hme_l1_sa.width, (int16_t)c.hme_l1_sa.height,
                                            st.hx[0][li][ri][w][h] >> 1, st.hy[0][li][ri][w][h] >> 1, 0, 0, slot);
                     else
-                        g = push_hme_level(st, p, 2, p.ref[li][ri].lvl[2], (int16_t)st.org_x, (int16_t)st.org_y, (int)st.b64_w, (int)st.b64_h,
+                        g = push_hme_level(st, p, 2, ref_plane(li, ri, 2), (int16_t)st.org_x, (int16_t)st.org_y, (int)st.b64_w, (int)st.b64_h,
                                            (int16_t)c.hme_l2_sa.width, (int16_t)c.hme_l2_sa.height, st.hx[1][li][ri][w][h],
                                            st.hy[1][li][ri][w][h], 0, 0, slot);
                     st.lvl_req[li][ri][w][h] = (uint8_t)(slot + 1);
@@ -1952,7 +2107,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 int li, ri, h, w;
                 region_of(tid, li, ri, h, w);
                 const int scale = (lvl == 1) ? 2 : 1;
-                const int k = (li < nl && ri < d.num_of_ref_pic_to_search[li]) ? st.lvl_req[li][ri][w][h] : 0;
+                const int k = ref_live(li, ri) ? st.lvl_req[li][ri][w][h] : 0;
                 if (k) {
                     uint32_t sad; int x, y;
                     key_to_result(st.req_key[k - 1], full_hme, sad, x, y);
@@ -1966,8 +2121,8 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         auto centre = [&]() { // lane <-> (list, reference)
             {
                 const int  li = (tid >> 2) & 1, ri = tid & 3;
-                const bool valid = tid < 8 && li < nl && ri < d.num_of_ref_pic_to_search[li];
-                const bool srch  = valid && searched(p, li);
+                const bool valid = tid < 8 && ref_live(li, ri);
+                const bool srch  = valid && ref_srch(li, ri);
                 int16_t sx = 0, sy = 0;
                 u64     hme_sad = 0;
                 if (srch && c.enable_hme_flag) {
@@ -2026,7 +2181,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         auto c00_pre = [&](int gi) { // lane <-> (list, reference)
             const bool dep = me_dep;
             const int  li = (tid >> 2) & 1, ri = tid & 3;
-            const bool mine = tid < 8 && li < nl && ri < d.num_of_ref_pic_to_search[li] && !(dep && ((li == 0 && ri == 0) != (gi == 0)));
+            const bool mine = tid < 8 && ref_live(li, ri) && !(dep && ((li == 0 && ri == 0) != (gi == 0)));
             bool    push = false;
             int16_t cx = 0, cy = 0;
             if (mine) {
@@ -2038,7 +2193,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
             const u64 mask = __ballot(push);
             const int slot = 2 * __popcll(mask & ((1ull << tid) - 1ull));
             if (push) { // check_00_center (:1139-1206)
-                CPlane &rp = p.ref[li][ri].lvl[2];
+                auto &rp = ref_plane(li, ri, 2);
                 const int ox = (int16_t)st.org_x, oy = (int16_t)st.org_y;
                 if (ox + cx < -63) cx = (int16_t)(-63 - ox);
                 if (ox + cx > rp.width - 1) cx = (int16_t)(cx - ((ox + cx) - (rp.width - 1)));
@@ -2054,12 +2209,12 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
         auto probe_pre = [&](int gi) { // lane <-> (list, reference); list entries in the reference's loop order (prefix count of the lanes that search)
             const bool dep = me_dep;
             const int  li = (tid >> 2) & 1, ri = tid & 3;
-            const bool mine = tid < 8 && li < nl && ri < d.num_of_ref_pic_to_search[li] && !(dep && ((li == 0 && ri == 0) != (gi == 0))) && st.do_ref[li][ri];
+            const bool mine = tid < 8 && ref_live(li, ri) && !(dep && ((li == 0 && ri == 0) != (gi == 0))) && st.do_ref[li][ri];
             MeReq m = {};
             if (mine) {
-                CPlane &rp = p.ref[li][ri].lvl[2];
+                auto &rp = ref_plane(li, ri, 2);
                 int16_t  cx = st.me_cx[li][ri], cy = st.me_cy[li][ri];
-                const uint32_t dist = mctf ? (uint16_t)ref_distance(p, li, ri) : (uint16_t)scaled_distance(ref_distance(p, li, ri)); // :1299-1302
+                const uint32_t dist = mctf ? (uint16_t)ref_dist(li, ri) : (uint16_t)ref_sdist(li, ri); // :1299-1302
                 int16_t sa_w = (int16_t)imin((int)(c.me_sa.sa_min.width * dist), c.me_sa.sa_max.width);
                 int16_t sa_h = (int16_t)imin((int)(c.me_sa.sa_min.height * dist), c.me_sa.sa_max.height);
                 if (c.mv_sa_adj_enabled && (!c.mv_sa_adj_nearest_ref_only || ri == 0)) {
@@ -2108,10 +2263,10 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                     const MeReq m = st.me[i];
                     int16_t sa_w = m.sa_w, sa_h = m.sa_h;
                     const int cx = m.ox, cy = m.oy;
-                    if (m.probe) { // :1391-1439 -- only one point was searched: 64x64 SAD == sum of the 8x8 SADs
+                    if (uni(m.probe)) { // (uniform: an LDS value) :1391-1439 -- only one point was searched: 64x64 SAD == sum of the 8x8 SADs
                         const uint32_t mean = BEST_SAD(m.li, m.ri)[0] / 64;
                         const int32_t  dd   = (int32_t)BEST_SAD(m.li, m.ri)[21 + tid] - (int32_t)mean;
-                        const uint32_t var  = wave_sum((uint32_t)(dd * dd)) / 64;
+                        const uint32_t var  = ctrl_sum32((uint32_t)(dd * dd)) / 64;
                         if (var > c.me_sr_mult2_th) { sa_w = (int16_t)((imax(1, sa_w * 3 / 2) + 7) & ~7); sa_h = (int16_t)imax(1, sa_h * 3 / 2); }
                         if (var < c.me_sr_div4_th) { sa_w = (int16_t)((imax(1, sa_w >> 2) + 7) & ~7); sa_h = (int16_t)imax(3, imax(1, sa_h >> 2)); }
                         else if (var < c.me_sr_div2_th) { sa_w = (int16_t)((imin(sa_w, sa_w >> 1) + 7) & ~7); sa_h = (int16_t)imax(3, imin(sa_h, sa_h >> 1)); }
@@ -2270,7 +2425,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
             for (int r = 0; r < 8; r++) { // per reference: sum of its 64 8x8 SADs
                 const int li = r >> 2, ri = r & 3;
                 if (li >= nl || ri >= d.num_of_ref_pic_to_search[li]) continue;
-                const u64 t = st.do_ref[li][ri] ? (u64)wave_sum(BEST_SAD(li, ri)[21 + (tid & 63)]) : (u64)SVT_HIP_MAX_SAD_VALUE * 64;
+                const u64 t = uni(st.do_ref[li][ri]) ? (u64)ctrl_sum32(BEST_SAD(li, ri)[21 + (tid & 63)]) : (u64)SVT_HIP_MAX_SAD_VALUE * 64; // (uniform: one LDS byte)
                 if ((tid & 63) == 0) st.hme_sad64[li][ri] = t;
             }
             wave_sync();
@@ -2312,33 +2467,34 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
             wave_sync();
             for (int n = tid; n < d.max_number_of_pus_per_sb; n += kThreads) {
                 const int use = use_pu(n);
-                const int row = (n > 4) ? c_z_to_raster[n] : n; // == pu below (c_z_to_raster is the identity on 0..4)
+                const int row = (n > 4) ? z_to_raster(n) : n; // == pu below (z_to_raster is the identity on 0..4)
                 uint8_t first = 0; // candidate 0 of this PU, kept for perform_gm_detection
                 auto put_cand = [&](int idx, uint8_t v) { l_cand[row * d.max_cand + idx] = v; if (idx == 0) first = v; };
                 uint32_t  nls = nl;
                 if (r0 == 1 && r1 == 0) { // construct_me_candidate_array_single_ref
-                    const int pu   = c_z_to_raster[n];
+                    const int pu   = z_to_raster(n);
                     st.me_dist[pu] = BEST_SAD(0, 0)[n];
                     if (use) l_total[pu] = 1;
                     if (st.do_ref[0][0] && use) { put_cand(0, pack(0, 0, 0, 0, 0)); l_mv[pu * d.max_refs] = BEST_MV(0, 0)[n]; }
                 } else if (r0 == 1 && r1 == 1) { // construct_me_candidate_array_mrp_off
-                    const int     pu = c_z_to_raster[n];
+                    const int     pu = z_to_raster(n);
                     const uint8_t d0 = st.do_ref[0][0], d1 = (nls == 1) ? 0 : st.do_ref[1][0];
                     if (nls < 2 || !st.do_ref[1][0]) nls = 1;
                     const uint32_t prune_th = (d0 && d1) ? (uint32_t)c.prune_me_candidates_th : 0;
-                    uint8_t  blk[2] = {d0, d1};
+                    RefFlags<SVT_HIP_ME_LEAN_EPILOGUE != 0> blk;
+                    blk.set(0, 0, d0 != 0); blk.set(1, 0, d1 != 0);
                     uint8_t  off = 0;
                     const uint32_t s0 = BEST_SAD(0, 0)[n], s1 = BEST_SAD(1, 0)[n];
                     const uint32_t best = (d0 && d1) ? (s0 < s1 ? s0 : s1) : (d0 ? s0 : s1);
                     st.me_dist[pu] = best;
                     if (use) l_total[pu] = 1;
                     int min_list = -1;
-                    if (c.use_best_unipred_cand_only && blk[0] && blk[1]) min_list = s0 < s1 ? 0 : 1;
+                    if (c.use_best_unipred_cand_only && blk.get(0, 0) && blk.get(1, 0)) min_list = s0 < s1 ? 0 : 1;
                     for (uint32_t li = 0; li < nls && (use || off == 0); li++) {
-                        if (!blk[li]) continue;
+                        if (!blk.get((int)li, 0)) continue;
                         if (prune_th > 0) {
                             const uint32_t dev = (BEST_SAD(li, 0)[n] - best) * 100;
-                            if (dev > best * prune_th) { blk[li] = 0; continue; }
+                            if (dev > best * prune_th) { blk.set((int)li, 0, false); continue; }
                         }
                         if (min_list != -1 && min_list != (int)li) {
                             if (use) l_mv[pu * d.max_refs + (li ? d.max_l0 : 0)] = BEST_MV(li, 0)[n];
@@ -2350,25 +2506,25 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                         }
                         off++;
                     }
-                    if (blk[0] && blk[1] && use) { put_cand(off, pack(2, 0, 0, 0, 1)); l_total[pu] = (uint8_t)(off + 1); }
+                    if (blk.get(0, 0) && blk.get(1, 0) && use) { put_cand(off, pack(2, 0, 0, 0, 1)); l_total[pu] = (uint8_t)(off + 1); }
                 } else { // construct_me_candidate_array
-                    const int pu = (n > 4) ? c_z_to_raster[n] : n;
+                    const int pu = (n > 4) ? z_to_raster(n) : n;
                     uint8_t   off = 0;
-                    uint8_t   blk[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+                    RefFlags<SVT_HIP_ME_LEAN_EPILOGUE != 0> blk; // the pairs that still take part
                     const uint32_t prune_th = (uint32_t)c.prune_me_candidates_th;
                     uint32_t       best     = ~0u;
                     for (uint32_t li = 0; li < nls; li++)
-                        for (int ri = 0; ri < d.num_of_ref_pic_to_search[li]; ri++) {
-                            blk[li][ri] = st.do_ref[li][ri];
-                            if (blk[li][ri]) best = BEST_SAD(li, ri)[n] < best ? BEST_SAD(li, ri)[n] : best;
+                        for (int ri = 0; ri < (li ? r1 : r0); ri++) {
+                            blk.set((int)li, ri, st.do_ref[li][ri] != 0);
+                            if (blk.get((int)li, ri)) best = BEST_SAD(li, ri)[n] < best ? BEST_SAD(li, ri)[n] : best;
                         }
                     st.me_dist[pu] = best;
                     for (uint32_t li = 0; li < nls && (use || off == 0); li++)
-                        for (int ri = 0; ri < d.num_of_ref_pic_to_search[li] && (use || off == 0); ri++) {
-                            if (!blk[li][ri]) continue;
+                        for (int ri = 0; ri < (li ? r1 : r0) && (use || off == 0); ri++) {
+                            if (!blk.get((int)li, ri)) continue;
                             if (prune_th > 0) {
                                 const uint32_t dev = (BEST_SAD(li, ri)[n] - best) * 100;
-                                if (dev > best * prune_th) { blk[li][ri] = 0; continue; }
+                                if (dev > best * prune_th) { blk.set((int)li, ri, false); continue; }
                             }
                             if (use) {
                                 put_cand(off, pack(li, ri, ri, li == 0 ? li : 24, li == 1 ? li : 24));
@@ -2380,12 +2536,12 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                         for (int a = 0; a < r0; a++)
                             for (int bb = 0; bb < r1; bb++) {
                                 if (d.only_l_bwd && (a > 0 || bb > 0)) continue;
-                                if (blk[0][a] && blk[1][bb]) put_cand(off++, pack(2, a, bb, 0, 1));
+                                if (blk.get(0, a) && blk.get(1, bb)) put_cand(off++, pack(2, a, bb, 0, 1));
                             }
                         if (!d.only_l_bwd) {
                             for (int a = 1; a < r0; a++)
-                                if (blk[0][0] && blk[0][a]) put_cand(off++, pack(2, 0, a, 0, 0));
-                            if (r1 == 3 && blk[1][0] && blk[1][2]) put_cand(off++, pack(2, 0, 2, 1, 1));
+                                if (blk.get(0, 0) && blk.get(0, a)) put_cand(off++, pack(2, 0, a, 0, 0));
+                            if (r1 == 3 && blk.get(1, 0) && blk.get(1, 2)) put_cand(off++, pack(2, 0, 2, 1, 1));
                         }
                     }
                     if (use) l_total[pu] = off;
@@ -2393,20 +2549,31 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 if (row < 88) st.cand0[row] = first;
             }
             wave_sync();
-            for (int i = tid; i < (int)(n_pu * d.max_refs); i += kThreads) o_mv[i] = l_mv[i];
-            for (int i = tid; i < (int)(n_pu * d.max_cand); i += kThreads) o_cand[i] = l_cand[i];
-            for (int i = tid; i < (int)n_pu; i += kThreads) o_total[i] = l_total[i];
+            // the block's rows leave LDS as coalesced stores.  The lean epilogue sends them off behind the distortions and the GM detection, so
+            // that everything the block still has to compute comes before its first store; the bounds (85 PUs, the header's limits on references
+            // and candidates) tell the compiler how short these loops are.
+            auto copy_out = [&]() {
+                if constexpr (SVT_HIP_ME_LEAN_EPILOGUE != 0) {
+                    __builtin_assume(n_pu <= 85u);
+                    __builtin_assume(d.max_refs >= 0 && d.max_refs <= SVT_HIP_MAX_LISTS * SVT_HIP_MAX_REFS);
+                    __builtin_assume(d.max_cand >= 0 && d.max_cand <= 32);
+                }
+                for (int i = tid; i < (int)(n_pu * d.max_refs); i += kThreads) o_mv[i] = l_mv[i];
+                for (int i = tid; i < (int)(n_pu * d.max_cand); i += kThreads) o_cand[i] = l_cand[i];
+                for (int i = tid; i < (int)n_pu; i += kThreads) o_total[i] = l_total[i];
+            };
+            if constexpr (SVT_HIP_ME_LEAN_EPILOGUE == 0) copy_out();
 
             PROF(14);
             // ---- compute_distortion (:2964-3008) + perform_gm_detection (:2838-2961) ---------------------------
             if (tid < 64) { // wave 0: the sums are wave reductions, lane 0 writes
                 const uint32_t v8  = st.me_dist[21 + tid];
-                const uint32_t d8  = wave_sum(v8);
-                const uint32_t d16 = wave_sum(tid < 16 ? st.me_dist[5 + tid] : 0u);
-                const uint32_t d32 = wave_sum(tid < 4 ? st.me_dist[1 + tid] : 0u);
+                const uint32_t d8  = ctrl_sum32(v8);
+                const uint32_t d16 = ctrl_sum32(tid < 16 ? st.me_dist[5 + tid] : 0u);
+                const uint32_t d32 = ctrl_sum32(tid < 4 ? st.me_dist[1 + tid] : 0u);
                 const u64       mean = d8 / 64;
                 const long long dd   = (long long)v8 - (long long)mean;
-                const u64       ssq  = wave_sum((u64)(dd * dd));
+                const u64       ssq  = ctrl_sum64((u64)(dd * dd));
                 // perform_gm_detection (:2838-2961): lane i classifies PU i of the list; the per-(list, ref, component, sign)
                 // counts of the reference's cnt[] are popcounts of ballots
                 uint8_t stationary = 0, allow_gm = 0;
@@ -2418,17 +2585,20 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                     if (tid < nn) {
                         int idx = (low ? 21 : 5) + tid;
                         if (low && !d.enable_me_8x8) {
-                            if (idx >= 21) idx = c_8x8_to_16x16[idx - 21];
-                            if (!d.enable_me_16x16 && idx >= 5) idx = c_16x16_to_32x32[idx - 5];
-                        } else if (!low && !d.enable_me_16x16 && idx >= 5) idx = c_16x16_to_32x32[idx - 5];
+                            if (idx >= 21) idx = parent_16x16(idx - 21);
+                            if (!d.enable_me_16x16 && idx >= 5) idx = parent_32x32(idx - 5);
+                        } else if (!low && !d.enable_me_16x16 && idx >= 5) idx = parent_32x32(idx - 5);
                         const uint8_t  cb  = st.cand0[idx];
                         const unsigned dir = cb & 3;
                         const unsigned li  = (dir == 0 || dir == 2) ? ((cb >> 6) & 1) : ((cb >> 7) & 1);
                         const unsigned ri  = (dir == 0 || dir == 2) ? ((cb >> 2) & 3) : ((cb >> 4) & 3);
-                        const u64 a = d.picture_number, bb = d.ref_picture_number[li][ri];
-                        int th;
-                        if (low) { const int dist = (uint16_t)iabs((int)(int16_t)((a > bb ? a : bb) - (a < bb ? a : bb))); th = d.gm_use_distance_based_active_th ? imax(dist >> 1, 4) : 4; }
-                        else     { const int dist = (uint16_t)iabs((int)(int16_t)(a - bb)); th = d.gm_use_distance_based_active_th ? imax(dist * 16, 32) : 32; }
+                        int dist; // |picture_number - ref_picture_number[li][ri]| in the casts of the resolution's branch
+                        if constexpr (kTab) dist = tab.ent[ref_slot((int)li, (int)ri)].gm_dist;
+                        else {
+                            const u64 a = d.picture_number, bb = d.ref_picture_number[li][ri];
+                            dist = low ? (uint16_t)iabs((int)(int16_t)((a > bb ? a : bb) - (a < bb ? a : bb))) : (uint16_t)iabs((int)(int16_t)(a - bb));
+                        }
+                        const int th = low ? (d.gm_use_distance_based_active_th ? imax(dist >> 1, 4) : 4) : (d.gm_use_distance_based_active_th ? imax(dist * 16, 32) : 32);
                         const uint32_t mv = BEST_MV(li, ri)[idx];
                         const int mx = (int)(int16_t)(mv & 0xFFFF) << 2, my = (int)(int16_t)(mv >> 16) << 2;
                         refk  = (int)(li * 4 + ri);
@@ -2447,14 +2617,19 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                             allow_gm = 1;
                     }
                 }
+              // normalisation to a full block: a whole 64x64 block (uniform test) divides by 4096 -- a shift, the product wrapping as it does in
+              // front of the division -- and only edge blocks pay for the four integer divisions
+              const uint32_t pix = uni(st.b64_w) * uni(st.b64_h), dist64 = st.me_dist[0];
+              const bool whole = SVT_HIP_ME_LEAN_EPILOGUE != 0 && pix == 4096u;
+              auto per_4096 = [&](uint32_t x) { return whole ? (x * 4096u) >> 12 : (x * 4096u) / pix; };
+              if constexpr (SVT_HIP_ME_LEAN_EPILOGUE != 0) copy_out();
               if (tid == 0) {
-                const uint32_t pix = st.b64_w * st.b64_h;
                 p.res.me_8x8_cost_variance[b] = (uint32_t)(ssq / 64);
                 p.res.rc_me_distortion[b]     = d.input_resolution <= 2 ? d8 : d16;
-                p.res.me_64x64_distortion[b]  = (st.me_dist[0] * 4096u) / pix;
-                p.res.me_32x32_distortion[b]  = (d32 * 4096u) / pix;
-                p.res.me_16x16_distortion[b]  = (d16 * 4096u) / pix;
-                p.res.me_8x8_distortion[b]    = (d8 * 4096u) / pix;
+                p.res.me_64x64_distortion[b]  = per_4096(dist64);
+                p.res.me_32x32_distortion[b]  = per_4096(d32);
+                p.res.me_16x16_distortion[b]  = per_4096(d16);
+                p.res.me_8x8_distortion[b]    = per_4096(d8);
                 p.res.stationary_block_present_sb[b] = stationary;
                 p.res.rc_me_allow_gm[b]              = allow_gm;
               }
@@ -2472,7 +2647,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
                 }
             if (tid < 8) {
                 const int li = tid >> 2, ri = tid & 3;
-                const bool live = li < nl && ri < d.num_of_ref_pic_to_search[li];
+                const bool live = ref_live(li, ri);
                 if (p.res.do_ref) p.res.do_ref[(size_t)b * 8 + tid] = live ? st.do_ref[li][ri] : 0;
                 if (p.res.hme_sad) p.res.hme_sad[(size_t)b * 8 + tid] = live ? (uint32_t)st.hme_sad64[li][ri] : 0;
                 if (p.res.hme_sc) {
@@ -2517,7 +2692,15 @@ SVT_ME_KERNEL(svt_hip_me_tail_kernel, kMeTail, SVT_HIP_ME_TAIL_WAVES_PER_SIMD)
 
 #include "me_dense.inl"
 
-size_t svt_hip_me_kernel_lds_bytes(void) { return lds_layout(SVT_HIP_MAX_LISTS * SVT_HIP_MAX_REFS, 0, 1).total + SVT_HIP_ME_PROFILE_LDS; }
+// the largest slice a kernel of the chain may ask for (the one-kernel form's, unless it goes without the reference table)
+size_t svt_hip_me_kernel_lds_bytes(void) {
+    uint32_t most = 0;
+    for (int mode : {kMeFull, kMeMid1, kMeS1, kMeMid2, kMeS2, kMeTail}) {
+        const uint32_t t = lds_layout(SVT_HIP_MAX_LISTS * SVT_HIP_MAX_REFS, 0, 1, mode).total;
+        most = t > most ? t : most;
+    }
+    return most + SVT_HIP_ME_PROFILE_LDS;
+}
 
 #include "svt_hip_internal.h"
 
@@ -2624,6 +2807,7 @@ int svt_hip_me_launch(SvtHipContext *ctx, SvtHipLane *lane, const MeKernelParams
         if (ctx->me_waves_per_cu && per_cu > ctx->me_waves_per_cu) per_cu = ctx->me_waves_per_cu; // the caller leaves room for kernels of another stream
         uint32_t grid = (uint32_t)ctx->num_cus * per_cu;
         if ((flags & 1u) && grid > (uint32_t)ctx->num_cus * kListWavesPerCu) grid = (uint32_t)ctx->num_cus * kListWavesPerCu; // list kernels: their lists are short (edge blocks)
+        if (ctx->me_max_waves && grid > ctx->me_max_waves) grid = ctx->me_max_waves;
         if (grid > total) grid = total;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, lane->stream, d_hdr, d_par, flags);
     };
@@ -2709,5 +2893,11 @@ extern "C" int svt_hip_me_dense_counters(SvtHipContext *ctx, unsigned long long 
 extern "C" int svt_hip_context_set_me_waves_per_cu(SvtHipContext *ctx, uint32_t waves) {
     if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
     ctx->me_waves_per_cu = waves;
+    return SVT_HIP_OK;
+}
+
+extern "C" int svt_hip_context_set_me_max_waves(SvtHipContext *ctx, uint32_t waves) {
+    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
+    ctx->me_max_waves = waves;
     return SVT_HIP_OK;
 }

@@ -61,6 +61,7 @@ struct SvtHipContext {
     void       *tpl_group_host;        // their pinned staging copies
     hipEvent_t  tpl_group_done[4];     // recorded behind the last launch that reads slot i (SVT_HIP_TPL_GROUP_RING)
     int         tpl_group_next;
+    uint32_t    me_max_waves;          // 0: no limit; else the most persistent waves an ME kernel is launched with (svt_hip_context_set_me_max_waves)
 };
 
 struct SvtHipPaPicture {
