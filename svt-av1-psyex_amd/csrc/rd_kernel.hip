@@ -67,6 +67,38 @@ __host__ __device__ constexpr int rd_blocks_per_wave(int ts) { return 64 / rd_la
 __host__ __device__ constexpr int rd_bounded_btf(int ts) {
     return ((rd_lanes_per_block(ts) == 32 && tx_wide(ts) != tx_high(ts)) || (tx_wide(ts) == 64 && tx_high(ts) == 16)) ? 3 : 2;
 }
+// The inverse passes of a size may have a third, clamp-free tier (ipass_clamp_free, txfm_core.h) beside the bounded and the general one.  It is
+// one more copy of both unrolled passes, and only 64x64 pays for it (-12.6 % per launch with the input clamps below).  16x16 and 32x32 measured
+// SLOWER with it, +7.6 % and +20 % (32x32 executes 11 instructions per pixel fewer, but its allocation at the 128-register limit goes from 2 to 28
+// spilled registers and VALU busy falls from 95 to 69 %; 16x16 executes more): profiles/r13_rd_clampfree_before_after.txt.  SVT_RD_CLAMP_FREE: 0 no
+// size, 1 64x64, 2 the square 16 / 32 / 64-point sizes (the build that was measured).
+#ifndef SVT_RD_CLAMP_FREE
+#define SVT_RD_CLAMP_FREE 1
+#endif
+#ifndef SVT_RD_SKIP_ENTRY_CLAMPS
+#define SVT_RD_SKIP_ENTRY_CLAMPS 1 /* the input clamps of both inverse passes run only in a wave whose largest raw input is outside their range */
+#endif
+#ifndef SVT_RD_PAIR_RESIDUAL_MAX
+#define SVT_RD_PAIR_RESIDUAL_MAX 1 /* the residual loop tracks its extremes per pair of samples */
+#endif
+#ifndef SVT_RD_ROW_BOUND_FROM_QUANT
+#define SVT_RD_ROW_BOUND_FROM_QUANT 1 /* a lean-quantizer wave whose bound M on |dqcoeff| passes the clamp-free test skips measuring the row input */
+#endif
+__host__ __device__ constexpr bool rd_clamp_free_tier(int ts) {
+    return tx_wide(ts) == tx_high(ts) && (SVT_RD_CLAMP_FREE == 1 ? tx_wide(ts) == 64 : SVT_RD_CLAMP_FREE == 2 && tx_wide(ts) >= 16);
+}
+// The rectangular 32-lane layouts spill more with the input clamps in a branch of their own (16x32: 3 -> 10 registers); they and 64x16 clamp on load.
+__host__ __device__ constexpr bool rd_skip_entry_clamps(int ts) { return SVT_RD_SKIP_ENTRY_CLAMPS && rd_bounded_btf(ts) == 2; }
+#ifdef SVT_RD_TIER_STATS
+// diagnostic build only: waves of rd_tx_kernel by the tier of their inverse row pass x that of their column pass (0 general, 1 bounded, 2 clamp-free),
+// and [9] the waves whose row tier came from the quantizer's bound; svt_hip_rd_batch prints and clears them after every launch
+__device__ unsigned int g_rd_tier_stats[10];
+#endif
+// the tier of an inverse pass: 2 clamp-free, 1 bounded butterflies, 0 general
+template <bool FREE> __device__ __forceinline__ int ipass_tier(uint32_t wave_max_abs_input, int n, int clamp_bits) {
+    if (FREE && ipass_clamp_free(wave_max_abs_input, n, clamp_bits)) return 2;
+    return ipass_fits_18_bits(wave_max_abs_input, n) ? 1 : 0;
+}
 __host__ __device__ constexpr int rd_waves_per_simd(int ts) {
     return rd_lanes_per_block(ts) == 64 ? SVT_RD_WAVES_64 : rd_lanes_per_block(ts) == 32 ? SVT_RD_WAVES_32 : SVT_RD_WAVES_16;
 }
@@ -76,6 +108,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     constexpr bool kShift32 = LW != 32; // bounded passes round-shift in 32 bits (measured: 64x64 -4 %; the 32-lane layout, at its 128-register limit, spills on it: +12 %)
     constexpr bool kFoldInv = LW != 32 || SVT_RD_FOLD_INV_32LANE; // the inverse DCT's last stage round-shifts (in 32 bits, in every layout)
     constexpr int kBtf = rd_bounded_btf(TS);
+    constexpr bool kFree = rd_clamp_free_tier(TS), kSkipEntry = rd_skip_entry_clamps(TS);
     constexpr int PA = W + 1, PB = WP + 1; // row pitches (dwords) of the full block and of the packed coefficients
     constexpr int ROW_CLAMP = BD == 8 ? 16 : 18, COL_CLAMP = 16; // svt_av1_gen_inv_stage_range, inv_transforms.c:42-80
     constexpr bool RECT = (W == 2 * H || H == 2 * W);
@@ -119,11 +152,18 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
                 const int i = l + (it0 + j) * LW;
                 if (it0 + j < NIT && i < RPR * H) {
                     const int r = i / RPR, c = (i - r * RPR) * RUN;
+                    static_assert(RUN % 2 == 0, "the extremes are taken per pair of samples");
 #pragma unroll
-                    for (int k = 0; k < RUN; k++) {
-                        const int32_t d = (int16_t)((int16_t)sv[j][k] - (int16_t)pv[j][k]);
-                        A[r * PA + c + k] = d;
-                        rhl.take(d);
+                    for (int k = 0; k < RUN; k += 2) {
+                        const int32_t d0 = (int16_t)((int16_t)sv[j][k] - (int16_t)pv[j][k]), d1 = (int16_t)((int16_t)sv[j][k + 1] - (int16_t)pv[j][k + 1]);
+                        A[r * PA + c + k]     = d0;
+                        A[r * PA + c + k + 1] = d1;
+#if SVT_RD_PAIR_RESIDUAL_MAX
+                        rhl.take(d0, d1);
+#else
+                        rhl.take(d0);
+                        rhl.take(d1);
+#endif
                     }
                 }
             }
@@ -227,6 +267,9 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     //   NP / LW squares sum without overflow in 32 bits, one v_mad_*24 each; M < 2^16 keeps dq * sg and qv * dequant within 24 x 24 -> 32 bits.
     constexpr int LS = tx_log_scale(TS), KT = LS == 2 ? 4 : 3;
     bool lane_lean = fast_q && q_out != nullptr && log_scale == LS;
+    // M bounds every |dqcoeff| of the lane's block, and with the rectangular sizes' 2896 / 4096 scaling every input of its inverse row pass:
+    // where that passes the clamp-free test in every lane of a lean wave, the row pass's tier is known without a look at its input
+    bool lane_row_free = false;
     {
         const int32_t  rndm = rnd_c[0] > rnd_c[1] ? rnd_c[0] : rnd_c[1], sm = q.quant_shift[0] > q.quant_shift[1] ? q.quant_shift[0] : q.quant_shift[1];
         const int32_t  dm = q.dequant[0] > q.dequant[1] ? q.dequant[0] : q.dequant[1], qm2 = (q.quant[0] > q.quant[1] ? q.quant[0] : q.quant[1]) + 65536;
@@ -237,8 +280,11 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         const u64 dqmax = (qvmax * (u64)(uint32_t)(nonneg ? dm : 0)) >> LS;
         const u64 M = dqmax > comax_w ? dqmax : (u64)comax_w;
         lane_lean = lane_lean && nonneg && tmax < (1u << (18 - KT)) && M < (1u << 16) && M * M * (NP / LW) < (1ull << 32);
+        if constexpr (kFree && SVT_RD_ROW_BOUND_FROM_QUANT)
+            lane_row_free = lane_lean && ipass_clamp_free((uint32_t)(RECT ? (M * 2896 + 2048) >> 12 : M), W, ROW_CLAMP); // M < 2^16 behind lane_lean
     }
     const bool lean_q = __all(lane_lean);
+    const bool row_free_q = kFree && SVT_RD_ROW_BOUND_FROM_QUANT && __all(lane_row_free); // implies lean_q
     if (lean_q) {
         static_assert(NP % LW == 0, "every lane of a block walks the same number of coefficients");
         constexpr int kScanAhead = NP / LW < SVT_RD_SCAN_AHEAD ? ((NP / LW) & ~1) : SVT_RD_SCAN_AHEAD; // as in the loop below
@@ -432,35 +478,54 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     __syncthreads();
     // inverse rows (inv_txfm2d_add_c, inv_transforms.c:2497-2511): discarded frequencies are zero
     int32_t xr[W];
+    // The reference clamps the input of the row pass to bd + 8 bits and that of the column pass to 16.  Both magnitudes are taken of the RAW values:
+    // a clamp only shrinks them, so the raw maximum bounds the clamped data in every test below, and the clamp itself runs only in a wave
+    // whose raw maximum is outside its range (a wave-uniform branch; such a wave is never in the clamp-free tier).
     uint32_t irmax = 0; // largest |row-pass input| of this lane
     if (l < H) {
 #pragma unroll
         for (int c = 0; c < W; c++) {
             int32_t v = (l < HP && c < WP) ? A[l * PB + c] : 0;
             if constexpr (RECT) v = rshift64((i64)v * 2896, 12);
-            xr[c] = clampv(v, BD + 8);
+            xr[c] = kSkipEntry ? v : clampv(v, BD + 8);
         }
-        irmax = vec_max_abs<W>(xr);
+        if (!row_free_q) irmax = vec_max_abs<W>(xr);
     }
-    const bool fast_irow = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(irmax)), W); // wave-uniform
+    const uint32_t irmax_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(irmax)); // wave-uniform, as everything decided from it
+    const int irow_tier = row_free_q ? 2 : ipass_tier<kFree>(irmax_w, W, ROW_CLAMP);
     uint32_t icmax = 0; // largest |row-pass output|: the column pass's input
     if (l < H) {
-        if (fast_irow) inv_1d_bounded<W, ROW_CLAMP, kShift32, kFoldInv, kBtf>(xr, ht, c_inv_shift0[TS]);
+        if (kSkipEntry && irmax_w >= (1u << (BD + 7))) {
+#pragma unroll
+            for (int c = 0; c < W; c++) xr[c] = clampv(xr[c], BD + 8);
+        }
+        if (irow_tier == 2) inv_1d_bounded<W, -1, kShift32, kFoldInv, kBtf>(xr, ht, c_inv_shift0[TS]);
+        else if (irow_tier == 1) inv_1d_bounded<W, ROW_CLAMP, kShift32, kFoldInv, kBtf>(xr, ht, c_inv_shift0[TS]);
         else { inv_1d<W, ROW_CLAMP, 1>(xr, ht); shift_vec<W, kShift32>(xr, c_inv_shift0[TS]); }
 #pragma unroll
         for (int c = 0; c < W; c++) A[l * PA + c] = xr[c];
         icmax = vec_max_abs<W>(xr);
     }
-    const bool fast_icol = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(icmax)), H);
+    const uint32_t icmax_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(icmax));
+    const int icol_tier = ipass_tier<kFree>(icmax_w, H, COL_CLAMP);
+#ifdef SVT_RD_TIER_STATS
+    if (lane == 0) { atomicAdd(&g_rd_tier_stats[irow_tier * 3 + icol_tier], 1u); if (row_free_q) atomicAdd(&g_rd_tier_stats[9], 1u); }
+#endif
     __syncthreads();
     // inverse columns + reconstruction + SSE (:2513-2534; svt_spatial_full_distortion_kernel / 16-bit variant)
     u64 sse = 0;
     if (l < W) {
         int32_t x[H];
         const int ic = lr ? W - 1 - l : l;
+        constexpr int kColIn = BD + 6 > 16 ? BD + 6 : 16;
 #pragma unroll
-        for (int r = 0; r < H; r++) x[r] = (r < HP) ? clampv(A[r * PA + ic], BD + 6 > 16 ? BD + 6 : 16) : 0; // rows >= 32 of a 64-row block are exactly zero after the row pass: constants, so the network prunes itself
-        if (fast_icol) inv_1d_bounded<H, COL_CLAMP, kShift32, kFoldInv, kBtf>(x, vt, -4);
+        for (int r = 0; r < H; r++) x[r] = (r < HP) ? (kSkipEntry ? A[r * PA + ic] : clampv(A[r * PA + ic], kColIn)) : 0; // rows >= 32 of a 64-row block are exactly zero after the row pass: constants, so the network prunes itself
+        if (kSkipEntry && icmax_w >= (1u << (kColIn - 1))) {
+#pragma unroll
+            for (int r = 0; r < HP; r++) x[r] = clampv(x[r], kColIn);
+        }
+        if (icol_tier == 2) inv_1d_bounded<H, -1, kShift32, kFoldInv, kBtf>(x, vt, -4);
+        else if (icol_tier == 1) inv_1d_bounded<H, COL_CLAMP, kShift32, kFoldInv, kBtf>(x, vt, -4);
         else { inv_1d<H, COL_CLAMP, 1>(x, vt); shift_vec<H, kShift32>(x, -4); }
         // residual (with the vertical flip undone) back to LDS, row-major: the reconstruction below moves whole runs
 #pragma unroll
@@ -527,6 +592,7 @@ template <int TS, int BD, typename Pix> __global__ void __launch_bounds__(64, rd
     constexpr int LW = rd_lanes_per_block(TS), BPW = rd_blocks_per_wave(TS);
     constexpr bool kShift32 = LW != 32, kFoldInv = LW != 32 || SVT_RD_FOLD_INV_32LANE;
     constexpr int kBtf = rd_bounded_btf(TS);
+    constexpr bool kFree = rd_clamp_free_tier(TS), kSkipEntry = rd_skip_entry_clamps(TS);
     constexpr int PA = W + 1, PB = WP + 1;
     constexpr int ROW_CLAMP = BD == 8 ? 16 : 18, COL_CLAMP = 16;
     constexpr bool RECT = (W == 2 * H || H == 2 * W);
@@ -549,27 +615,40 @@ template <int TS, int BD, typename Pix> __global__ void __launch_bounds__(64, rd
         for (int c = 0; c < W; c++) {
             int32_t v = (l < HP && c < WP) ? A[l * PB + c] : 0;
             if constexpr (RECT) v = rshift64((i64)v * 2896, 12);
-            xr[c] = clampv(v, BD + 8);
+            xr[c] = kSkipEntry ? v : clampv(v, BD + 8); // magnitudes of the raw values, clamps where a wave needs them: as in rd_tx_kernel
         }
         irmax = vec_max_abs<W>(xr);
     }
-    const bool fast_irow = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(irmax)), W); // wave-uniform
+    const uint32_t irmax_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(irmax)); // wave-uniform
+    const int irow_tier = ipass_tier<kFree>(irmax_w, W, ROW_CLAMP);
     uint32_t icmax = 0; // largest |row-pass output|: the column pass's input
     if (l < H) {
-        if (fast_irow) inv_1d_bounded<W, ROW_CLAMP, kShift32, kFoldInv, kBtf>(xr, ht, c_inv_shift0[TS]);
+        if (kSkipEntry && irmax_w >= (1u << (BD + 7))) {
+#pragma unroll
+            for (int c = 0; c < W; c++) xr[c] = clampv(xr[c], BD + 8);
+        }
+        if (irow_tier == 2) inv_1d_bounded<W, -1, kShift32, kFoldInv, kBtf>(xr, ht, c_inv_shift0[TS]);
+        else if (irow_tier == 1) inv_1d_bounded<W, ROW_CLAMP, kShift32, kFoldInv, kBtf>(xr, ht, c_inv_shift0[TS]);
         else { inv_1d<W, ROW_CLAMP, 1>(xr, ht); shift_vec<W, kShift32>(xr, c_inv_shift0[TS]); }
 #pragma unroll
         for (int c = 0; c < W; c++) A[l * PA + c] = xr[c];
         icmax = vec_max_abs<W>(xr);
     }
-    const bool fast_icol = ipass_fits_18_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(icmax)), H);
+    const uint32_t icmax_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(icmax));
+    const int icol_tier = ipass_tier<kFree>(icmax_w, H, COL_CLAMP);
     __syncthreads();
     if (l < W) { // inverse columns (:2513-2534)
         int32_t x[H];
         const int ic = lr ? W - 1 - l : l;
+        constexpr int kColIn = BD + 6 > 16 ? BD + 6 : 16;
 #pragma unroll
-        for (int r = 0; r < H; r++) x[r] = (r < HP) ? clampv(A[r * PA + ic], BD + 6 > 16 ? BD + 6 : 16) : 0;
-        if (fast_icol) inv_1d_bounded<H, COL_CLAMP, kShift32, kFoldInv, kBtf>(x, vt, -4);
+        for (int r = 0; r < H; r++) x[r] = (r < HP) ? (kSkipEntry ? A[r * PA + ic] : clampv(A[r * PA + ic], kColIn)) : 0;
+        if (kSkipEntry && icmax_w >= (1u << (kColIn - 1))) {
+#pragma unroll
+            for (int r = 0; r < HP; r++) x[r] = clampv(x[r], kColIn);
+        }
+        if (icol_tier == 2) inv_1d_bounded<H, -1, kShift32, kFoldInv, kBtf>(x, vt, -4);
+        else if (icol_tier == 1) inv_1d_bounded<H, COL_CLAMP, kShift32, kFoldInv, kBtf>(x, vt, -4);
         else { inv_1d<H, COL_CLAMP, 1>(x, vt); shift_vec<H, kShift32>(x, -4); }
 #pragma unroll
         for (int r = 0; r < H; r++) A[r * PA + l] = x[ud ? H - 1 - r : r];
@@ -735,7 +814,15 @@ int svt_hip_rd_batch(SvtHipContext *ctx, const SvtHipRdBatchDesc *d) {
     p.tx_size = d->tx_size;
     if (p.tx_size < 0 || p.tx_size >= 19) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "tx_size %d", p.tx_size);
     for (int k = 0; k < 3; k++) p.iscan[k] = ctx->iscan_dev + ((size_t)p.tx_size * 3 + k) * 1024;
-    return d->bit_depth == 8 ? launch_size<8>(ctx, p) : launch_size<10>(ctx, p);
+    const int rc = d->bit_depth == 8 ? launch_size<8>(ctx, p) : launch_size<10>(ctx, p);
+#ifdef SVT_RD_TIER_STATS
+    unsigned int st[10] = {0}, zero[10] = {0};
+    if (hipStreamSynchronize(ctx->stream) == hipSuccess && hipMemcpyFromSymbol(st, HIP_SYMBOL(g_rd_tier_stats), sizeof(st)) == hipSuccess &&
+        hipMemcpyToSymbol(HIP_SYMBOL(g_rd_tier_stats), zero, sizeof(zero)) == hipSuccess)
+        fprintf(stderr, "rd_tier_stats tx_size %d jobs %u  row x col (0 general, 1 bounded, 2 clamp-free): %u %u %u | %u %u %u | %u %u %u  row tier from the quantizer: %u\n",
+                p.tx_size, d->n_jobs, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9]);
+#endif
+    return rc;
 }
 
 } // extern "C"

@@ -260,6 +260,8 @@ template <int N, int FM> __device__ __forceinline__ void fdct_core(int32_t *x, c
 // out_s > 0 (the outermost call of a bounded pass): the pass is followed by svt_av1_round_shift_array_c(.., out_s), and the last stage does it.
 // With r = 2^(out_s-1): (clamp(a +- b, lo, hi) + r) >> out_s == clamp(a + r +- b, lo + r, hi + r) >> out_s -- adding r commutes with the clamp --
 // so t = a + r is shared by the pair: seven instructions for two outputs instead of eight.  |a|, |b| < 2^18 behind the stage clamps.
+// CLAMP < 0: the caller has shown that no node of the pass leaves the reference's clamp range (ipass_clamp_free), so every clamp_value is the
+// identity and none is computed: the sums and differences are plain, the folded last stage is t = a + r; (t +- b) >> out_s.
 template <int N, int CLAMP, int IM> __device__ __forceinline__ void idct_core(int32_t *x, const int32_t *c, const Btf &bit, int out_s = 0) {
     if constexpr (N == 2) {
         const int32_t a = x[0], b = x[1];
@@ -273,7 +275,10 @@ template <int N, int CLAMP, int IM> __device__ __forceinline__ void idct_core(in
 #pragma unroll
         for (int i = 0; i < M; i++) {
             const int32_t a = x[i], b = x[N - 1 - i];
-            if (out_s > 0) {
+            if constexpr (CLAMP < 0) { // no node of the pass leaves the clamp range (ipass_clamp_free): every clamp is the identity
+                if (out_s > 0) { const int32_t t = a + (1 << (out_s - 1)); x[i] = (t + b) >> out_s; x[N - 1 - i] = (t - b) >> out_s; }
+                else { x[i] = a + b; x[N - 1 - i] = a - b; }
+            } else if (out_s > 0) {
                 const int32_t r = 1 << (out_s - 1), lo = -(1 << (CLAMP - 1)) + r, hi = (1 << (CLAMP - 1)) - 1 + r, t = a + r;
                 x[i]         = max(min(t + b, hi), lo) >> out_s;
                 x[N - 1 - i] = max(min(t - b, hi), lo) >> out_s;
@@ -415,13 +420,24 @@ template <int N, int CLAMP, int IM> __device__ __forceinline__ void inv_1d(int32
 // every node of an inverse pass is a sum of at most N pass inputs with weights of magnitude <= 1 (the stage clamps only shrink it): below 2^18
 // when N x the largest |input| is
 __device__ __forceinline__ bool ipass_fits_18_bits(uint32_t wave_max_abs_input, int n) { return (unsigned long long)wave_max_abs_input * (unsigned)n < (1u << 18); }
+// The clamp-free tier.  Every node of an n-point inverse pass (DCT, ADST 8 / 16) is a linear map of the pass inputs plus what the half_btfs
+// upstream of it rounded: |node| <= G_n max|input| + e_n, with G_n the largest L1 norm of any node's weights (the 12-bit cosines taken as
+// they are, the 64-point passes over their 32 live inputs) and e_n the largest accumulated rounding (each half_btf adds at most 1/2 and
+// scales what its operands carry by its weights' magnitudes).  While that stays below 2^(clamp_bits - 1) every clamp_value of the pass
+// is the identity, the butterflies' operands stay below 2^17, and the pass may run with CLAMP < 0.  tests/test_inv_clamp_bounds.py
+// derives both tables from the flow graphs (G_n = 2.72, 5.28, 10.38, 20.57, 28.66; here in 64ths, rounded up) and checks them.
+__host__ __device__ constexpr int inv_gain64(int n) { return n == 4 ? 175 : n == 8 ? 339 : n == 16 ? 665 : n == 32 ? 1317 : 1835; }
+__host__ __device__ constexpr int inv_slack(int n) { return n == 4 ? 1 : n == 8 ? 6 : n == 16 ? 16 : n == 32 ? 24 : 63; }
+__device__ __forceinline__ bool ipass_clamp_free(uint32_t wave_max_abs_input, int n, int clamp_bits) {
+    return (u64)wave_max_abs_input * (unsigned)inv_gain64(n) + 64u * (unsigned)inv_slack(n) < ((u64)64 << (clamp_bits - 1));
+}
 // largest magnitude of a vector: the largest and the smallest element are tracked instead (one v_max3_i32 / v_min3_i32 per PAIR of elements
 // each; |x| first would be two instructions per element before the max)
 struct HiLo {
     int32_t hi = 0, lo = 0;
     __device__ __forceinline__ void take(int32_t a, int32_t b) { hi = max(max(hi, a), b); lo = min(min(lo, a), b); }
     __device__ __forceinline__ void take(int32_t a) { hi = max(hi, a); lo = min(lo, a); }
-    __device__ __forceinline__ uint32_t max_abs() const { return (uint32_t)max(hi, -lo); }
+    __device__ __forceinline__ uint32_t max_abs() const { return max((uint32_t)hi, 0u - (uint32_t)lo); } // hi >= 0 >= lo; unsigned, so that INT32_MIN counts as 2^31
 };
 template <int N> __device__ __forceinline__ uint32_t vec_max_abs(const int32_t *x) {
     HiLo m;
@@ -481,7 +497,7 @@ template <int N, int CLAMP, bool SAFE32, bool FOLD, int BM = 2> __device__ __for
     if (type == 3) { identity<N>(x); shift_vec<N, SAFE32>(x, sh); }
     else if (type == 0) {
         permute_brev<N>(x);
-        if constexpr (FOLD && SVT_TX_FOLD_INV && (CLAMP > 16 || !SAFE32)) idct_core<N, CLAMP, 2>(x, c, btf_bounded(12), -sh);
+        if constexpr (FOLD && SVT_TX_FOLD_INV && (CLAMP < 0 || CLAMP > 16 || !SAFE32)) idct_core<N, CLAMP, 2>(x, c, btf_bounded(12), -sh);
         else { idct_core<N, CLAMP, 2>(x, c, btf_bounded(12)); shift_vec<N, SAFE32>(x, sh); }
     } else {
         if constexpr (N == 4) adst4(x, 12, true);

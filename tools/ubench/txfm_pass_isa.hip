@@ -46,3 +46,10 @@ template __global__ void inv_dct_pass<32, 32, 18, -2, false>(const int32_t *, in
 template __global__ void inv_dct_pass<32, 32, 16, -4, false>(const int32_t *, int32_t *);
 template __global__ void inv_dct_pass<64, 32, 18, -2, true>(const int32_t *, int32_t *);
 template __global__ void inv_dct_pass<64, 32, 16, -4, true>(const int32_t *, int32_t *);
+// the same six inverse passes in the clamp-free tier (CLAMP < 0: ipass_clamp_free holds for the wave), rows (-2) then columns (-4)
+template __global__ void inv_dct_pass<16, 16, -1, -2, true>(const int32_t *, int32_t *);
+template __global__ void inv_dct_pass<16, 16, -1, -4, true>(const int32_t *, int32_t *);
+template __global__ void inv_dct_pass<32, 32, -1, -2, false>(const int32_t *, int32_t *);
+template __global__ void inv_dct_pass<32, 32, -1, -4, false>(const int32_t *, int32_t *);
+template __global__ void inv_dct_pass<64, 32, -1, -2, true>(const int32_t *, int32_t *);
+template __global__ void inv_dct_pass<64, 32, -1, -4, true>(const int32_t *, int32_t *);
