@@ -510,3 +510,65 @@ WARP_PRED_JOB_DTYPE = [("dst_offset", "<u4"), ("p_col", "<i2"), ("p_row", "<i2")
                        ("comp_mode", "u1"), ("fwd_offset", "u1"), ("bck_offset", "u1"), ("model_index", "<u4", (2,)), ("model", WARP_MODEL_DTYPE, (2,))]
 WARP_MODEL_JOB_DTYPE = [("pts", "<i4", (16,)), ("pts_inref", "<i4", (16,)), ("blk_org_x", "<u2"), ("blk_org_y", "<u2"), ("bwidth", "u1"), ("bheight", "u1"),
                         ("n_samples", "u1"), ("flags", "u1"), ("mv", "<i2", (2,)), ("mv_index", "<u4")]
+
+
+# ---- include/svt_hip_mask.h ----
+MASK_WEDGE, MASK_DIFFWTD = 0, 1
+MASK_PARAMS_FROM_ARRAY = 4
+MASK_OK, MASK_UNDEFINED = 0, 0xFF
+MASK_SEARCH_WEDGE, MASK_SEARCH_DIFFWTD, MASK_SEARCH_INTERINTRA = 0, 1, 2
+MASK_NO_RD = 0x7FFFFFFFFFFFFFFF  # rd_wedge when no wedge search ran (INT64_MAX)
+
+
+class MaskSearchResult(C.Structure):  # SvtHipMaskSearchResult
+    _fields_ = [("best_rd", C.c_int64), ("rd_wedge", C.c_int64), ("wedge_index", C.c_int8), ("wedge_sign", C.c_uint8), ("mask_type", C.c_uint8),
+                ("interintra_mode", C.c_uint8), ("use_wedge_interintra", C.c_uint8), ("exit", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class MaskedPredJob(C.Structure):  # SvtHipMaskedPredJob
+    _fields_ = [("pred", InterPredJob), ("comp_type", C.c_uint8), ("wedge_index", C.c_uint8), ("wedge_sign", C.c_uint8), ("mask_type", C.c_uint8),
+                ("luma_width", C.c_uint8), ("luma_height", C.c_uint8), ("reserved", C.c_uint8 * 2), ("mask_offset", C.c_uint32), ("result_index", C.c_uint32)]
+
+
+class MaskedPredDesc(C.Structure):  # SvtHipMaskedPredDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("ss_x", C.c_uint8), ("ss_y", C.c_uint8), ("n_refs", C.c_uint8), ("n_jobs", C.c_uint32),
+                ("refs", InterPredRef * INTER_PRED_MAX_REFS), ("dst", C.c_void_p), ("dst_stride", C.c_uint32), ("plane", C.c_uint8), ("reserved", C.c_uint8 * 3),
+                ("dst_samples", C.c_uint64), ("jobs", C.c_void_p), ("mv_array", C.c_void_p), ("n_mvs", C.c_uint32), ("n_results", C.c_uint32),
+                ("results", C.c_void_p), ("mask_buf", C.c_void_p), ("mask_bytes", C.c_uint64), ("status", C.c_void_p)]
+
+
+class InterIntraJob(C.Structure):  # SvtHipInterIntraJob
+    _fields_ = [("intra_offset", C.c_uint32 * 4), ("inter_offset", C.c_uint32), ("dst_offset", C.c_uint32), ("result_index", C.c_uint32), ("width", C.c_uint8),
+                ("height", C.c_uint8), ("luma_width", C.c_uint8), ("luma_height", C.c_uint8), ("interintra_mode", C.c_uint8), ("use_wedge", C.c_uint8),
+                ("wedge_index", C.c_uint8), ("wedge_sign", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class InterIntraDesc(C.Structure):  # SvtHipInterIntraDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("reserved", C.c_uint8 * 3), ("n_jobs", C.c_uint32), ("intra", C.c_void_p), ("inter", C.c_void_p), ("dst", C.c_void_p),
+                ("intra_stride", C.c_uint32), ("inter_stride", C.c_uint32), ("dst_stride", C.c_uint32), ("n_results", C.c_uint32),
+                ("intra_samples", C.c_uint64), ("inter_samples", C.c_uint64), ("dst_samples", C.c_uint64), ("jobs", C.c_void_p), ("results", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
+class MaskSearchJob(C.Structure):  # SvtHipMaskSearchJob
+    _fields_ = [("src_offset", C.c_uint32), ("pred0_offset", C.c_uint32), ("pred1_offset", C.c_uint32), ("intra_offset", C.c_uint32 * 4), ("width", C.c_uint8),
+                ("height", C.c_uint8), ("kind", C.c_uint8), ("ii_wedge_mode", C.c_uint8)]
+
+
+class MaskSearchDesc(C.Structure):  # SvtHipMaskSearchDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("pred0_to_pred1_mult", C.c_uint8), ("use_rate", C.c_uint8), ("use_rd_model", C.c_uint8), ("n_jobs", C.c_uint32),
+                ("src", C.c_void_p), ("pred0", C.c_void_p), ("pred1", C.c_void_p), ("intra", C.c_void_p), ("src_stride", C.c_uint32),
+                ("pred0_stride", C.c_uint32), ("pred1_stride", C.c_uint32), ("intra_stride", C.c_uint32), ("src_samples", C.c_uint64),
+                ("pred0_samples", C.c_uint64), ("pred1_samples", C.c_uint64), ("intra_samples", C.c_uint64), ("jobs", C.c_void_p), ("results", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
+MASK_SEARCH_RESULT_DTYPE = [("best_rd", "<i8"), ("rd_wedge", "<i8"), ("wedge_index", "i1"), ("wedge_sign", "u1"), ("mask_type", "u1"), ("interintra_mode", "u1"),
+                            ("use_wedge_interintra", "u1"), ("exit", "u1"), ("reserved", "u1", (2,))]
+MASKED_PRED_JOB_DTYPE = [("pred", INTER_PRED_JOB_DTYPE), ("comp_type", "u1"), ("wedge_index", "u1"), ("wedge_sign", "u1"), ("mask_type", "u1"), ("luma_width", "u1"),
+                         ("luma_height", "u1"), ("reserved", "u1", (2,)), ("mask_offset", "<u4"), ("result_index", "<u4")]
+INTERINTRA_JOB_DTYPE = [("intra_offset", "<u4", (4,)), ("inter_offset", "<u4"), ("dst_offset", "<u4"), ("result_index", "<u4"), ("width", "u1"), ("height", "u1"),
+                        ("luma_width", "u1"), ("luma_height", "u1"), ("interintra_mode", "u1"), ("use_wedge", "u1"), ("wedge_index", "u1"), ("wedge_sign", "u1"),
+                        ("flags", "u1"), ("reserved", "u1", (3,))]
+MASK_SEARCH_JOB_DTYPE = [("src_offset", "<u4"), ("pred0_offset", "<u4"), ("pred1_offset", "<u4"), ("intra_offset", "<u4", (4,)), ("width", "u1"), ("height", "u1"),
+                         ("kind", "u1"), ("ii_wedge_mode", "u1")]

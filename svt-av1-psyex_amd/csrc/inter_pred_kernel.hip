@@ -30,106 +30,11 @@
 #include "svt_hip_internal.h"
 #include "../../include/svt_hip_pred.h"
 #include "wave_ops.h"
+#include "convolve_core.h"
 
 namespace {
 
 constexpr int kWaves  = 4;
-constexpr int kWinU16 = 640; // (tile rows + 7) x (tile width + 8): 23 x 24 = 552, 39 x 16 = 624
-constexpr int kMidU16 = 368; // (tile rows + 7) x tile width: 23 x 16 = 368, 39 x 8 = 312
-
-// [0] sub_pel_filters_8, [1] sub_pel_filters_8smooth, [2] sub_pel_filters_8sharp, [3] bilinear_filters (InterpFilter's order), then the
-// tables of a dimension <= 4: [4] sub_pel_filters_4, [5] sub_pel_filters_4smooth
-__constant__ int16_t c_interp[6][16][8] = {
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 2, -6, 126, 8, -2, 0, 0}, {0, 2, -10, 122, 18, -4, 0, 0}, {0, 2, -12, 116, 28, -8, 2, 0},
-     {0, 2, -14, 110, 38, -10, 2, 0}, {0, 2, -14, 102, 48, -12, 2, 0}, {0, 2, -16, 94, 58, -12, 2, 0}, {0, 2, -14, 84, 66, -12, 2, 0},
-     {0, 2, -14, 76, 76, -14, 2, 0}, {0, 2, -12, 66, 84, -14, 2, 0}, {0, 2, -12, 58, 94, -16, 2, 0}, {0, 2, -12, 48, 102, -14, 2, 0},
-     {0, 2, -10, 38, 110, -14, 2, 0}, {0, 2, -8, 28, 116, -12, 2, 0}, {0, 0, -4, 18, 122, -10, 2, 0}, {0, 0, -2, 8, 126, -6, 2, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 2, 28, 62, 34, 2, 0, 0}, {0, 0, 26, 62, 36, 4, 0, 0}, {0, 0, 22, 62, 40, 4, 0, 0},
-     {0, 0, 20, 60, 42, 6, 0, 0}, {0, 0, 18, 58, 44, 8, 0, 0}, {0, 0, 16, 56, 46, 10, 0, 0}, {0, -2, 16, 54, 48, 12, 0, 0},
-     {0, -2, 14, 52, 52, 14, -2, 0}, {0, 0, 12, 48, 54, 16, -2, 0}, {0, 0, 10, 46, 56, 16, 0, 0}, {0, 0, 8, 44, 58, 18, 0, 0},
-     {0, 0, 6, 42, 60, 20, 0, 0}, {0, 0, 4, 40, 62, 22, 0, 0}, {0, 0, 4, 36, 62, 26, 0, 0}, {0, 0, 2, 34, 62, 28, 2, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {-2, 2, -6, 126, 8, -2, 2, 0}, {-2, 6, -12, 124, 16, -6, 4, -2}, {-2, 8, -18, 120, 26, -10, 6, -2},
-     {-4, 10, -22, 116, 38, -14, 6, -2}, {-4, 10, -22, 108, 48, -18, 8, -2}, {-4, 10, -24, 100, 60, -20, 8, -2}, {-4, 10, -24, 90, 70, -22, 10, -2},
-     {-4, 12, -24, 80, 80, -24, 12, -4}, {-2, 10, -22, 70, 90, -24, 10, -4}, {-2, 8, -20, 60, 100, -24, 10, -4}, {-2, 8, -18, 48, 108, -22, 10, -4},
-     {-2, 6, -14, 38, 116, -22, 10, -4}, {-2, 6, -10, 26, 120, -18, 8, -2}, {-2, 4, -6, 16, 124, -12, 6, -2}, {0, 2, -2, 8, 126, -6, 2, -2}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, 0, 120, 8, 0, 0, 0}, {0, 0, 0, 112, 16, 0, 0, 0}, {0, 0, 0, 104, 24, 0, 0, 0},
-     {0, 0, 0, 96, 32, 0, 0, 0}, {0, 0, 0, 88, 40, 0, 0, 0}, {0, 0, 0, 80, 48, 0, 0, 0}, {0, 0, 0, 72, 56, 0, 0, 0},
-     {0, 0, 0, 64, 64, 0, 0, 0}, {0, 0, 0, 56, 72, 0, 0, 0}, {0, 0, 0, 48, 80, 0, 0, 0}, {0, 0, 0, 40, 88, 0, 0, 0},
-     {0, 0, 0, 32, 96, 0, 0, 0}, {0, 0, 0, 24, 104, 0, 0, 0}, {0, 0, 0, 16, 112, 0, 0, 0}, {0, 0, 0, 8, 120, 0, 0, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, -4, 126, 8, -2, 0, 0}, {0, 0, -8, 122, 18, -4, 0, 0}, {0, 0, -10, 116, 28, -6, 0, 0},
-     {0, 0, -12, 110, 38, -8, 0, 0}, {0, 0, -12, 102, 48, -10, 0, 0}, {0, 0, -14, 94, 58, -10, 0, 0}, {0, 0, -12, 84, 66, -10, 0, 0},
-     {0, 0, -12, 76, 76, -12, 0, 0}, {0, 0, -10, 66, 84, -12, 0, 0}, {0, 0, -10, 58, 94, -14, 0, 0}, {0, 0, -10, 48, 102, -12, 0, 0},
-     {0, 0, -8, 38, 110, -12, 0, 0}, {0, 0, -6, 28, 116, -10, 0, 0}, {0, 0, -4, 18, 122, -8, 0, 0}, {0, 0, -2, 8, 126, -4, 0, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, 30, 62, 34, 2, 0, 0}, {0, 0, 26, 62, 36, 4, 0, 0}, {0, 0, 22, 62, 40, 4, 0, 0},
-     {0, 0, 20, 60, 42, 6, 0, 0}, {0, 0, 18, 58, 44, 8, 0, 0}, {0, 0, 16, 56, 46, 10, 0, 0}, {0, 0, 14, 54, 48, 12, 0, 0},
-     {0, 0, 12, 52, 52, 12, 0, 0}, {0, 0, 12, 48, 54, 14, 0, 0}, {0, 0, 10, 46, 56, 16, 0, 0}, {0, 0, 8, 44, 58, 18, 0, 0},
-     {0, 0, 6, 42, 60, 20, 0, 0}, {0, 0, 4, 40, 62, 22, 0, 0}, {0, 0, 4, 36, 62, 26, 0, 0}, {0, 0, 2, 34, 62, 30, 0, 0}}};
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); } // clamp(), Codec/definitions.h
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// av1_get_interp_filter_params_with_block_size: the table of a filter type on a dimension
-__device__ __forceinline__ int filter_table(int filter, int dim) {
-    if (dim <= 4 && (filter == 2 || filter == 0)) return 4;
-    if (dim <= 4 && filter == 1) return 5;
-    return filter;
-}
-
-__device__ __forceinline__ bool is_block_size(int w, int h) {
-    const bool pw = w >= 4 && w <= 128 && (w & (w - 1)) == 0, ph = h >= 4 && h <= 128 && (h & (h - 1)) == 0;
-    if (!pw || !ph) return false;
-    const int big = w > h ? w : h, small = w > h ? h : w;
-    return big == small || big == 2 * small || (big == 4 * small && big <= 64);
-}
-
-// what one reference of a job needs, all of it wave-uniform
-struct RefView {
-    const void *plane;
-    int stride, org_x, org_y, max_x, max_y;
-    int pos_x, pos_y; // of the block's first sample in the picture, after the clamp
-    int sx, sy;       // subpel phases
-};
-
-// compute_subpel_params, unscaled branch: the clamp, the position and the phases of one reference
-__device__ __forceinline__ RefView ref_view(const SvtHipInterPredDesc &d, const SvtHipInterPredJob &j, const SvtHipInterPredRef r, int mvr, int mvc) {
-    const int w = j.width, h = j.height, shx = 1 - d.ss_x, shy = 1 - d.ss_y;
-    int row = (int16_t)(mvr * (1 << shy)), col = (int16_t)(mvc * (1 << shx)); // the (int16_t) cast of clamp_mv_to_umv_border_sb
-    const int spel_left = (4 + w) << 4, spel_right = spel_left - 16, spel_top = (4 + h) << 4, spel_bottom = spel_top - 16;
-    const int min_col = (int)((uint32_t)j.mb_to_left_edge << shx) - spel_left, max_col = (int)((uint32_t)j.mb_to_right_edge << shx) + spel_right;
-    const int min_row = (int)((uint32_t)j.mb_to_top_edge << shy) - spel_top, max_row = (int)((uint32_t)j.mb_to_bottom_edge << shy) + spel_bottom;
-    col = (int16_t)clampi(col, min_col, max_col);
-    row = (int16_t)clampi(row, min_row, max_row);
-    RefView v;
-    v.plane = r.plane; v.stride = (int)r.stride; v.org_x = r.org_x; v.org_y = r.org_y;
-    v.max_x = (int)r.width - 1; v.max_y = (int)r.height - 1;
-    v.pos_x = j.org_x + (col >> 4); v.pos_y = j.org_y + (row >> 4);
-    v.sx = col & 15; v.sy = row & 15;
-    return v;
-}
-
-template <typename Px> __device__ __forceinline__ int sample(const RefView &r, int x, int y) {
-    const int cx = clampi(x + r.org_x, 0, r.max_x), cy = clampi(y + r.org_y, 0, r.max_y);
-    return ((const Px *)r.plane)[(size_t)cy * (size_t)r.stride + (size_t)cx];
-}
-
-// rows x cols samples from picture position (x0, y0) into win (row pitch ws)
-template <typename Px> __device__ __forceinline__ void stage(uint16_t *win, const RefView &r, int x0, int y0, int cols, int rows, int ws, int lane) {
-    const uint32_t magic = (65536u + (uint32_t)cols - 1) / (uint32_t)cols; // i / cols for i < 1024, cols <= 23: exact
-    const int n = rows * cols;
-    for (int i = lane; i < n; i += 64) {
-        const int y = (int)(((uint32_t)i * magic) >> 16), x = i - y * cols;
-        win[y * ws + x] = (uint16_t)sample<Px>(r, x0 + x, y0 + y);
-    }
-}
-
-__device__ __forceinline__ void load4u(const uint16_t *p, int *v) { // 8-byte aligned
-    const uint2 t = *(const uint2 *)p;
-    v[0] = (int)(t.x & 0xFFFFu); v[1] = (int)(t.x >> 16); v[2] = (int)(t.y & 0xFFFFu); v[3] = (int)(t.y >> 16);
-}
-__device__ __forceinline__ void load4s(const int16_t *p, int *v) {
-    const uint2 t = *(const uint2 *)p;
-    v[0] = (int)(int16_t)(t.x & 0xFFFFu); v[1] = (int)t.x >> 16; v[2] = (int)(int16_t)(t.y & 0xFFFFu); v[3] = (int)t.y >> 16;
-}
 
 template <bool HBD> __global__ __launch_bounds__(64 * kWaves) void inter_pred_kernel(const SvtHipInterPredDesc d) {
     using Px = typename std::conditional<HBD, uint16_t, uint8_t>::type;

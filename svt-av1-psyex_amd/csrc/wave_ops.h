@@ -1,7 +1,7 @@
 // wave_ops.h -- the wave-level primitives of the kernels (wave64), the one place they are defined.  A name says which form it is, because the
 // two forms return differently:
 //   butterfly (__shfl_xor)  wave_sum<T> wave_min<T> wave_max<T> group_sum<G> group_or<G> group_max<G>   the result in every lane (a VGPR)
-//   DPP, whole wave         wave_sum_dpp wave_min_dpp                                        a wave-uniform scalar (an SGPR), no LDS crossbar traffic
+//   DPP, whole wave         wave_sum_dpp wave_sum64_dpp wave_min_dpp                                        a wave-uniform scalar (an SGPR), no LDS crossbar traffic
 //   DPP, part of a wave     quad_sum oct_sum row16_sum_of_quads                              the result in every lane of the group
 // and wave_sync(), the barrier that orders one wave's own LDS traffic.
 #ifndef SVT_HIP_WAVE_OPS_H
@@ -61,6 +61,11 @@ __device__ __forceinline__ uint32_t wave_sum_dpp(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false); // row_bcast:15 -> rows 1, 3
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false); // row_bcast:31 -> rows 2, 3
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+// a 64-bit sum in three pieces of 24 / 24 / 16 bits, none of which can overflow its 32-bit sum over 64 lanes
+__device__ __forceinline__ uint64_t wave_sum64_dpp(uint64_t v) {
+    const uint64_t lo = wave_sum_dpp((uint32_t)v & 0xFFFFFFu), mid = wave_sum_dpp((uint32_t)(v >> 24) & 0xFFFFFFu), hi = wave_sum_dpp((uint32_t)(v >> 48));
+    return (hi << 48) + (mid << 24) + lo;
 }
 // minimum: a butterfly inside the 16-lane rows (min is idempotent, so the mirror patterns serve), then two row broadcasts
 template <int CTRL, int ROWS> __device__ __forceinline__ uint32_t dpp_min_step(uint32_t v) {
