@@ -39,7 +39,7 @@
  * Bit-exact with the reference's C path for 8-bit planes (uint8) and 10-bit planes (packed uint16).
  *
  * Out of scope: the curve-fit rate model and model_rd_for_sb_with_curvfit, masked compound on warped references
- * (av1_make_masked_warp_inter_predictor), scaled references, OBMC, 12-bit, and everything svt_hip_pred.h leaves out.
+ * (av1_make_masked_warp_inter_predictor), scaled references, 12-bit, OBMC (svt_hip_obmc.h), and everything svt_hip_pred.h leaves out.
  *
  * A job gets status 0xFF, and writes nothing else, when
  *   prediction  a wedge on a luma size without wedges; wedge_index >= 16, wedge_sign or mask_type > 1; comp_type > 1; DIFFWTD on a luma size

@@ -572,3 +572,76 @@ INTERINTRA_JOB_DTYPE = [("intra_offset", "<u4", (4,)), ("inter_offset", "<u4"), 
                         ("flags", "u1"), ("reserved", "u1", (3,))]
 MASK_SEARCH_JOB_DTYPE = [("src_offset", "<u4"), ("pred0_offset", "<u4"), ("pred1_offset", "<u4"), ("intra_offset", "<u4", (4,)), ("width", "u1"), ("height", "u1"),
                          ("kind", "u1"), ("ii_wedge_mode", "u1")]
+
+
+# ---- include/svt_hip_obmc.h ----
+OBMC_MAX_NEIGHBOURS = 4
+OBMC_MV_FROM_ARRAY = 1
+OBMC_OK, OBMC_UNDEFINED = 0, 0xFF
+
+
+class ObmcNeighbour(C.Structure):  # SvtHipObmcNeighbour
+    _fields_ = [("rel_pos", C.c_uint8), ("size", C.c_uint8), ("ref", C.c_uint8), ("filter_x", C.c_uint8), ("filter_y", C.c_uint8), ("flags", C.c_uint8),
+                ("mv", C.c_int16 * 2), ("reserved", C.c_uint16), ("mv_index", C.c_uint32)]
+
+
+class ObmcBlock(C.Structure):  # SvtHipObmcBlock
+    _fields_ = [("org_x", C.c_int16), ("org_y", C.c_int16), ("width", C.c_uint8), ("height", C.c_uint8), ("n_above", C.c_uint8), ("n_left", C.c_uint8),
+                ("mb_to_left_edge", C.c_int32), ("mb_to_right_edge", C.c_int32), ("mb_to_top_edge", C.c_int32), ("mb_to_bottom_edge", C.c_int32),
+                ("strip_offset", C.c_uint32), ("reserved", C.c_uint32), ("above", ObmcNeighbour * OBMC_MAX_NEIGHBOURS), ("left", ObmcNeighbour * OBMC_MAX_NEIGHBOURS)]
+
+
+class ObmcJob(C.Structure):  # SvtHipObmcJob
+    _fields_ = [("block", C.c_uint32), ("offset", C.c_uint32)]
+
+
+class ObmcNeighbourDesc(C.Structure):  # SvtHipObmcNeighbourDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("ss_x", C.c_uint8), ("ss_y", C.c_uint8), ("plane", C.c_uint8), ("n_refs", C.c_uint8), ("reserved", C.c_uint8 * 3),
+                ("n_jobs", C.c_uint32), ("n_blocks", C.c_uint32), ("refs", InterPredRef * INTER_PRED_MAX_REFS), ("blocks", C.c_void_p), ("jobs", C.c_void_p),
+                ("above", C.c_void_p), ("left", C.c_void_p), ("strip_samples", C.c_uint64), ("mv_array", C.c_void_p), ("n_mvs", C.c_uint32),
+                ("reserved2", C.c_uint32), ("status", C.c_void_p)]
+
+
+class ObmcBlendDesc(C.Structure):  # SvtHipObmcBlendDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("ss_x", C.c_uint8), ("ss_y", C.c_uint8), ("plane", C.c_uint8), ("n_jobs", C.c_uint32), ("n_blocks", C.c_uint32),
+                ("dst_stride", C.c_uint32), ("blocks", C.c_void_p), ("jobs", C.c_void_p), ("above", C.c_void_p), ("left", C.c_void_p),
+                ("strip_samples", C.c_uint64), ("dst", C.c_void_p), ("dst_samples", C.c_uint64), ("status", C.c_void_p)]
+
+
+class ObmcTargetDesc(C.Structure):  # SvtHipObmcTargetDesc
+    _fields_ = [("strip_bit_depth", C.c_uint8), ("reserved", C.c_uint8 * 3), ("n_jobs", C.c_uint32), ("n_blocks", C.c_uint32), ("src_stride", C.c_uint32),
+                ("blocks", C.c_void_p), ("jobs", C.c_void_p), ("above", C.c_void_p), ("left", C.c_void_p), ("strip_samples", C.c_uint64), ("src", C.c_void_p),
+                ("src_samples", C.c_uint64), ("wsrc", C.c_void_p), ("mask", C.c_void_p), ("out_values", C.c_uint64), ("status", C.c_void_p)]
+
+
+OBMC_NEIGHBOUR_DTYPE = [("rel_pos", "u1"), ("size", "u1"), ("ref", "u1"), ("filter_x", "u1"), ("filter_y", "u1"), ("flags", "u1"), ("mv", "<i2", (2,)),
+                        ("reserved", "<u2"), ("mv_index", "<u4")]
+OBMC_BLOCK_DTYPE = [("org_x", "<i2"), ("org_y", "<i2"), ("width", "u1"), ("height", "u1"), ("n_above", "u1"), ("n_left", "u1"), ("mb_to_left_edge", "<i4"),
+                    ("mb_to_right_edge", "<i4"), ("mb_to_top_edge", "<i4"), ("mb_to_bottom_edge", "<i4"), ("strip_offset", "<u4"), ("reserved", "<u4"),
+                    ("above", OBMC_NEIGHBOUR_DTYPE, (OBMC_MAX_NEIGHBOURS,)), ("left", OBMC_NEIGHBOUR_DTYPE, (OBMC_MAX_NEIGHBOURS,))]
+OBMC_JOB_DTYPE = [("block", "<u4"), ("offset", "<u4")]
+OBMC_MAX_FPEL_RANGE = 64
+
+
+class ObmcSearchJob(C.Structure):  # SvtHipObmcSearchJob
+    _fields_ = [("target_offset", C.c_uint32), ("ref_offset", C.c_uint32), ("width", C.c_uint8), ("height", C.c_uint8), ("reserved", C.c_uint8 * 2),
+                ("start_mv", Mv), ("ref_mv", Mv), ("col_min", C.c_int32), ("col_max", C.c_int32), ("row_min", C.c_int32), ("row_max", C.c_int32),
+                ("reserved2", C.c_uint32)]
+
+
+class ObmcSearchResult(C.Structure):  # SvtHipObmcSearchResult
+    _fields_ = [("fullpel_value", C.c_int32), ("besterr", C.c_uint32), ("distortion", C.c_int32), ("sse1", C.c_uint32), ("rate_mv", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+class ObmcSearchDesc(C.Structure):  # SvtHipObmcSearchDesc
+    _fields_ = [("ref_bit_depth", C.c_uint8), ("refine_level", C.c_uint8), ("fpel_search_diag", C.c_uint8), ("approx_inter_rate", C.c_uint8), ("allow_hp", C.c_uint8),
+                ("reserved", C.c_uint8 * 3), ("n_jobs", C.c_uint32), ("fpel_search_range", C.c_uint32), ("sadpb", C.c_int32), ("error_per_bit", C.c_int32),
+                ("ref_stride", C.c_uint32), ("reserved2", C.c_uint32), ("ref", C.c_void_p), ("ref_samples", C.c_uint64), ("wsrc", C.c_void_p), ("mask", C.c_void_p),
+                ("target_values", C.c_uint64), ("mvjcost", C.c_void_p), ("mvcost", C.c_void_p * 2), ("jobs", C.c_void_p), ("best_mv", C.c_void_p),
+                ("results", C.c_void_p), ("status", C.c_void_p)]
+
+
+OBMC_SEARCH_JOB_DTYPE = [("target_offset", "<u4"), ("ref_offset", "<u4"), ("width", "u1"), ("height", "u1"), ("reserved", "u1", (2,)), ("start_mv", "<i2", (2,)),
+                         ("ref_mv", "<i2", (2,)), ("col_min", "<i4"), ("col_max", "<i4"), ("row_min", "<i4"), ("row_max", "<i4"), ("reserved2", "<u4")]
+OBMC_SEARCH_RESULT_DTYPE = [("fullpel_value", "<i4"), ("besterr", "<u4"), ("distortion", "<i4"), ("sse1", "<u4"), ("rate_mv", "<i4"), ("reserved", "<u4")]

@@ -1,12 +1,13 @@
-// convolve_core.h -- what the sub-pel prediction kernels share (inter_pred_kernel.hip, mask_kernel.hip): the six interpolation filter tables,
-// the clamp / position rule of one reference, the clamped sample fetch, the staging of a tile's source window in LDS, and the compound
-// (CONV_BUF_TYPE) form of the per-reference quad computation.  The tables and the rule exist once.
+// convolve_core.h -- what the sub-pel prediction kernels share (inter_pred_kernel.hip, mask_kernel.hip, obmc_kernel.hip): the six interpolation
+// filter tables, the clamp / position rule of one reference, the clamped sample fetch, the staging of a tile's source window in LDS, and the
+// compound (CONV_BUF_TYPE) and single-reference forms of the per-reference quad computation.  The tables and the rule exist once.
 //
 // Reference functions restated (Source/Lib):
 //   compute_subpel_params (unscaled branch), clamp_mv_to_umv_border_sb, clamp_mv        Codec/enc_inter_prediction.c:3200-3211,30-50, Codec/inter_prediction.h:90-93
 //   av1_get_convolve_filter_params, av1_get_interp_filter_params_with_block_size        Codec/inter_prediction.h:137-153
 //   sub_pel_filters_8 / _4 / _8sharp / _8smooth / _4smooth, bilinear_filters             Codec/inter_prediction.c:223-254,1065-1129
 //   svt_av1_jnt_convolve_{2d_copy,x,y,2d}_c, svt_av1_highbd_jnt_convolve_*_c             Codec/inter_prediction.c:494-668,852-1035
+//   svt_av1_convolve_{2d_copy,x,y,2d}_sr_c, svt_av1_highbd_convolve_*_sr_c               Codec/inter_prediction.c:311-418,670-777
 // Every InterpFilterParams has taps = 8 (the 4-tap tables are 8 wide with zero ends), so fo_horiz = fo_vert = 3 throughout.
 #ifndef SVT_HIP_CONVOLVE_CORE_H
 #define SVT_HIP_CONVOLVE_CORE_H
@@ -131,6 +132,18 @@ __device__ __forceinline__ TileWalk tile_walk(int w, int h, int lane) {
     return t;
 }
 
+// tile_walk for strips that are no block sizes (obmc_kernel.hip), with a guard: at most 32 rows to a tile, which keeps every tile's window and
+// intermediate inside the LDS slices whatever the strip -- the bound lives here, beside the slices' sizes.  With the 14 luma sizes the OBMC
+// batches accept no 4-wide strip is higher than 32 rows (8x32 luma left, 16x64 chroma left), so the cap does not fire today
+constexpr int kFitRows = 32;
+static_assert((kFitRows + 7) * (4 + 8) <= kWinU16 && (kFitRows + 7) * (8 + 8) <= kWinU16 && (16 + 7) * (16 + 8) <= kWinU16, "a tile's window fits its LDS slice");
+static_assert((kFitRows + 7) * 8 <= kMidU16 && (16 + 7) * 16 <= kMidU16, "a tile's intermediate fits its LDS slice");
+__device__ __forceinline__ TileWalk tile_walk_fit(int w, int h, int lane) {
+    TileWalk t = tile_walk(w, h, lane);
+    if (t.TH > kFitRows) { t.TH = kFitRows; t.active = lane < t.qpr * kFitRows; } // only a 4-wide tile is higher: qpr = 1
+    return t;
+}
+
 // One reference of a compound on one tile: the lane's quad of CONV_BUF_TYPE values, as svt_av1_jnt_convolve_{2d_copy,x,y,2d}_c and the
 // highbd forms store them with do_average = 0 (round_0 = 3, round_1 = 7): res[i] in 0..65535.  (bx, by): the tile's first sample in the
 // picture; win / mid: the wave's LDS slices (kWinU16 / kMidU16).  Inactive lanes take part in the staging and get res = 0.
@@ -211,6 +224,92 @@ template <bool HBD> __device__ __forceinline__ void compound_quad(const RefView 
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) res[i] = (int)(uint16_t)(((sum[i] * 16 + 64) >> 7) + ro);
+        }
+    }
+}
+
+// A single reference on one tile: the lane's quad of samples, as svt_av1_convolve_{2d_copy,x,y,2d}_sr_c and the highbd forms store them
+// (round_0 = 3, round_1 = 11, each variant with its own rounding), clipped to the depth.  Arguments as compound_quad's; the window may be any
+// tile with (TH + 7) * (TW + 8) <= kWinU16 and (TH + 7) * TW <= kMidU16.  Inactive lanes take part in the staging and get res = 0.
+template <bool HBD> __device__ __forceinline__ void single_quad(const RefView &r, int tabx, int taby, const TileWalk &t, int bx, int by, uint16_t *win,
+                                                                int16_t *mid, int lane, int *res) {
+    using Px = typename std::conditional<HBD, uint16_t, uint8_t>::type;
+    constexpr int bd = HBD ? 10 : 8, px_max = (1 << bd) - 1;
+    const int  TW = t.TW, TH = t.TH, qx = t.qx, qy = t.qy;
+    const bool fx = r.sx != 0, fy = r.sy != 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) res[i] = 0;
+    if (!fx && !fy) { // svt_av1_convolve_2d_copy_sr_c
+        if (t.active)
+#pragma unroll
+            for (int i = 0; i < 4; i++) res[i] = sample<Px>(r, bx + qx + i, by + qy);
+        return;
+    }
+    const int ws = TW + 8, mx = fx ? 3 : 0, my = fy ? 3 : 0;
+    wave_sync(); // the previous reads of win are done
+    stage<Px>(win, r, bx - mx, by - my, TW + (fx ? 7 : 0), TH + (fy ? 7 : 0), ws, lane);
+    wave_sync();
+    int tx8[8], ty8[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) { tx8[k] = c_interp[tabx][r.sx][k]; ty8[k] = c_interp[taby][r.sy][k]; }
+    if (fx && fy) { // the horizontal pass of *_2d_sr: im_block, (TH + 7) rows
+        const int units = (TH + 7) << t.qsh;
+        for (int u = lane; u < units; u += 64) {
+            const int rr = u >> t.qsh, cc = (u & (t.qpr - 1)) << 2;
+            int in[12];
+            load4u(win + rr * ws + cc, in); load4u(win + rr * ws + cc + 4, in + 4); load4u(win + rr * ws + cc + 8, in + 8);
+            uint32_t o[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                int sum = 1 << (bd + 6);
+#pragma unroll
+                for (int k = 0; k < 8; k++) sum += tx8[k] * in[i + k];
+                o[i] = (uint32_t)(uint16_t)(int16_t)((sum + 4) >> 3);
+            }
+            *(uint2 *)(mid + rr * TW + cc) = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+        }
+        wave_sync();
+        if (t.active) {
+            int sum[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) sum[i] = 1 << (bd + 11);
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                int v[4];
+                load4s(mid + (qy + k) * TW + qx, v);
+#pragma unroll
+                for (int i = 0; i < 4; i++) sum[i] += ty8[k] * v[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) { // round_1 = 11, bits = 0; the 8-bit function holds res in an int16_t
+                const int v = ((sum[i] + 1024) >> 11) - ((1 << bd) + (1 << (bd - 1)));
+                res[i] = clampi(HBD ? v : (int)(int16_t)(uint16_t)v, 0, px_max);
+            }
+        }
+    } else if (fx) { // *_x_sr
+        if (t.active) {
+            int in[12];
+            load4u(win + qy * ws + qx, in); load4u(win + qy * ws + qx + 4, in + 4); load4u(win + qy * ws + qx + 8, in + 8);
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                int sum = 0;
+#pragma unroll
+                for (int k = 0; k < 8; k++) sum += tx8[k] * in[i + k];
+                res[i] = clampi((((sum + 4) >> 3) + 8) >> 4, 0, px_max);
+            }
+        }
+    } else { // *_y_sr
+        if (t.active) {
+            int sum[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                int v[4];
+                load4u(win + (qy + k) * ws + qx, v);
+#pragma unroll
+                for (int i = 0; i < 4; i++) sum[i] += ty8[k] * v[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) res[i] = clampi((sum[i] + 64) >> 7, 0, px_max);
         }
     }
 }
