@@ -645,3 +645,45 @@ class ObmcSearchDesc(C.Structure):  # SvtHipObmcSearchDesc
 OBMC_SEARCH_JOB_DTYPE = [("target_offset", "<u4"), ("ref_offset", "<u4"), ("width", "u1"), ("height", "u1"), ("reserved", "u1", (2,)), ("start_mv", "<i2", (2,)),
                          ("ref_mv", "<i2", (2,)), ("col_min", "<i4"), ("col_max", "<i4"), ("row_min", "<i4"), ("row_max", "<i4"), ("reserved2", "<u4")]
 OBMC_SEARCH_RESULT_DTYPE = [("fullpel_value", "<i4"), ("besterr", "<u4"), ("distortion", "<i4"), ("sse1", "<u4"), ("rate_mv", "<i4"), ("reserved", "<u4")]
+
+
+# ---- include/svt_hip_ifs.h ----
+IFS_PAIRS = 9
+IFS_CONTEXTS = 16
+IFS_MODEL_ENTRIES = 104
+IFS_OK, IFS_UNDEFINED = 0, 0xFF
+IFS_SKIPPED = 0xFFFFFFFFFFFFFFFF  # rd / sse of a pair the search skipped
+
+
+class IfsJob(C.Structure):  # SvtHipIfsJob
+    _fields_ = [("pred", InterPredJob), ("src_offset", C.c_uint32), ("pred_ctx", C.c_uint8 * 2), ("reserved", C.c_uint8 * 2)]
+
+
+class IfsResult(C.Structure):  # SvtHipIfsResult
+    _fields_ = [("best_rd", C.c_uint64), ("interp_filters", C.c_uint32), ("switchable_rate", C.c_int32), ("filter_x", C.c_uint8), ("filter_y", C.c_uint8),
+                ("winner", C.c_uint8), ("reserved", C.c_uint8 * 5)]
+
+
+class IfsDesc(C.Structure):  # SvtHipIfsDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("n_refs", C.c_uint8), ("enable_dual_filter", C.c_uint8), ("subsampled_distortion", C.c_uint8),
+                ("skip_sse_rd_model", C.c_uint8), ("spy_rd", C.c_uint8), ("reserved", C.c_uint8 * 2), ("n_jobs", C.c_uint32), ("n_mvs", C.c_uint32),
+                ("refs", InterPredRef * INTER_PRED_MAX_REFS), ("src", C.c_void_p), ("src_stride", C.c_uint32), ("dst_stride", C.c_uint32),
+                ("src_samples", C.c_uint64), ("dst", C.c_void_p), ("dst_samples", C.c_uint64), ("jobs", C.c_void_p), ("mv_array", C.c_void_p),
+                ("quantizer", C.c_int32), ("lambda_", C.c_uint32), ("smooth_bias_pct", C.c_uint32), ("reserved2", C.c_uint32), ("psy_rd", C.c_double),
+                ("switchable_interp_fac_bits", C.c_void_p), ("results", C.c_void_p), ("rd", C.c_void_p), ("sse", C.c_void_p), ("status", C.c_void_p)]
+
+
+class IfsPatch(C.Structure):  # SvtHipIfsPatch
+    _fields_ = [("result_index", C.c_uint32), ("record_index", C.c_uint32)]
+
+
+class IfsScatterDesc(C.Structure):  # SvtHipIfsScatterDesc
+    _fields_ = [("n_patches", C.c_uint32), ("n_results", C.c_uint32), ("n_records", C.c_uint32), ("record_stride", C.c_uint32), ("filter_x_offset", C.c_uint32),
+                ("reserved", C.c_uint32), ("patches", C.c_void_p), ("results", C.c_void_p), ("result_status", C.c_void_p), ("base", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
+IFS_JOB_DTYPE = [("pred", INTER_PRED_JOB_DTYPE), ("src_offset", "<u4"), ("pred_ctx", "u1", (2,)), ("reserved", "u1", (2,))]
+IFS_RESULT_DTYPE = [("best_rd", "<u8"), ("interp_filters", "<u4"), ("switchable_rate", "<i4"), ("filter_x", "u1"), ("filter_y", "u1"), ("winner", "u1"),
+                    ("reserved", "u1", (5,))]
+IFS_PATCH_DTYPE = [("result_index", "<u4"), ("record_index", "<u4")]
