@@ -27,7 +27,8 @@
  * arithmetic of svt_av1_predict_intra_block, and get_filt_type (whether the above or the left neighbour is smooth), are table logic that stays
  * with the encoder.
  *
- * Out of scope: palette, intra-BC, the inter-intra blend, 12-bit, the availability derivation above, pointer-level leaves for the intra rtcd
+ * Palette is svt_hip_palette_search_batch / svt_hip_palette_pred_batch (svt_hip_palette.h), which write the same prediction plane.
+ * Out of scope: intra-BC, the inter-intra blend, 12-bit, the availability derivation above, pointer-level leaves for the intra rtcd
  * entries (one call per block; the batch is the boundary), and svt_hip_tpl_dispense at TPL level 1 (its open-loop path upsamples the edges but
  * predicts with upsample 0: another contract).  Chroma-from-luma is svt_hip_cfl_pred_batch (svt_hip_cfl.h), which reads the DC plane this batch
  * writes.

@@ -687,3 +687,52 @@ IFS_JOB_DTYPE = [("pred", INTER_PRED_JOB_DTYPE), ("src_offset", "<u4"), ("pred_c
 IFS_RESULT_DTYPE = [("best_rd", "<u8"), ("interp_filters", "<u4"), ("switchable_rate", "<i4"), ("filter_x", "u1"), ("filter_y", "u1"), ("winner", "u1"),
                     ("reserved", "u1", (5,))]
 IFS_PATCH_DTYPE = [("result_index", "<u4"), ("record_index", "<u4")]
+
+
+# ---- include/svt_hip_palette.h ----
+PALETTE_MAX_CANDS = 14
+PALETTE_MAX_SIZE = 8
+PALETTE_MAX_CACHE = 16
+PALETTE_BSIZE_CTXS = 7
+PALETTE_MODE_CTXS = 3
+PALETTE_OK, PALETTE_UNDEFINED = 0, 0xFF
+
+
+class PaletteJob(C.Structure):  # SvtHipPaletteJob
+    _fields_ = [("src_offset", C.c_uint32), ("map_offset", C.c_uint32), ("width", C.c_uint8), ("height", C.c_uint8), ("rows", C.c_uint8), ("cols", C.c_uint8),
+                ("n_cache", C.c_uint8), ("bsize_ctx", C.c_uint8), ("mode_ctx", C.c_uint8), ("reserved", C.c_uint8), ("color_cache", C.c_uint16 * PALETTE_MAX_CACHE)]
+
+
+class PaletteCand(C.Structure):  # SvtHipPaletteCand
+    _fields_ = [("size", C.c_uint8), ("first_index", C.c_uint8), ("colors", C.c_uint16 * PALETTE_MAX_SIZE), ("top_over", C.c_uint8), ("reserved", C.c_uint8),
+                ("color_cost", C.c_int32), ("map_cost", C.c_int32), ("index0_cost", C.c_int32), ("size_cost", C.c_int32), ("rate", C.c_int32)]
+
+
+class PaletteResult(C.Structure):  # SvtHipPaletteResult
+    _fields_ = [("n_colors", C.c_uint32), ("n_cands", C.c_uint32), ("cands", PaletteCand * PALETTE_MAX_CANDS)]
+
+
+class PaletteDesc(C.Structure):  # SvtHipPaletteDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("cost_bit_depth", C.c_uint8), ("dominant_color_step", C.c_uint8), ("reduce_palette_cost_precision", C.c_uint8),
+                ("n_jobs", C.c_uint32), ("src", C.c_void_p), ("src_stride", C.c_uint32), ("reserved", C.c_uint32), ("src_samples", C.c_uint64),
+                ("palette_ycolor_fac_bitss", C.c_void_p), ("palette_ysize_fac_bits", C.c_void_p), ("palette_ymode_fac_bits", C.c_void_p), ("jobs", C.c_void_p),
+                ("results", C.c_void_p), ("status", C.c_void_p), ("color_maps", C.c_void_p), ("map_bytes", C.c_uint64)]
+
+
+class PalettePredJob(C.Structure):  # SvtHipPalettePredJob
+    _fields_ = [("search_index", C.c_uint32), ("cand_index", C.c_uint32), ("dst_offset", C.c_uint32), ("map_offset", C.c_uint32)]
+
+
+class PalettePredDesc(C.Structure):  # SvtHipPalettePredDesc
+    _fields_ = [("bit_depth", C.c_uint8), ("reserved", C.c_uint8 * 3), ("n_jobs", C.c_uint32), ("n_search_jobs", C.c_uint32), ("src_stride", C.c_uint32),
+                ("src", C.c_void_p), ("src_samples", C.c_uint64), ("dst", C.c_void_p), ("dst_stride", C.c_uint32), ("reserved2", C.c_uint32),
+                ("dst_samples", C.c_uint64), ("search_jobs", C.c_void_p), ("search_results", C.c_void_p), ("search_status", C.c_void_p), ("jobs", C.c_void_p),
+                ("status", C.c_void_p), ("color_map", C.c_void_p), ("map_bytes", C.c_uint64)]
+
+
+PALETTE_JOB_DTYPE = [("src_offset", "<u4"), ("map_offset", "<u4"), ("width", "u1"), ("height", "u1"), ("rows", "u1"), ("cols", "u1"), ("n_cache", "u1"),
+                     ("bsize_ctx", "u1"), ("mode_ctx", "u1"), ("reserved", "u1"), ("color_cache", "<u2", (PALETTE_MAX_CACHE,))]
+PALETTE_CAND_DTYPE = [("size", "u1"), ("first_index", "u1"), ("colors", "<u2", (PALETTE_MAX_SIZE,)), ("top_over", "u1"), ("reserved", "u1"), ("color_cost", "<i4"),
+                      ("map_cost", "<i4"), ("index0_cost", "<i4"), ("size_cost", "<i4"), ("rate", "<i4")]
+PALETTE_RESULT_DTYPE = [("n_colors", "<u4"), ("n_cands", "<u4"), ("cands", PALETTE_CAND_DTYPE, (PALETTE_MAX_CANDS,))]
+PALETTE_PRED_JOB_DTYPE = [("search_index", "<u4"), ("cand_index", "<u4"), ("dst_offset", "<u4"), ("map_offset", "<u4")]
