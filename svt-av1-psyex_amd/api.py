@@ -50,6 +50,24 @@ def lib():
     return _lib
 
 
+def check_desc(name, d):
+    """Calls the library's *_check_desc entry `name` on the descriptor `d`; raises SvtHipError when it is refused."""
+    L = lib()
+    rc = getattr(L, name)(C.byref(d))
+    if rc:
+        raise SvtHipError(f"{name}: {ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+
+
+def ptr(t):
+    """The device address of a tensor, or None (a null pointer in a descriptor) for None."""
+    return t.data_ptr() if t is not None else None
+
+
+def samples(t, bit_depth):
+    """How many samples of `bit_depth` a tensor holds, whatever its dtype."""
+    return t.numel() * t.element_size() // (2 if bit_depth > 8 else 1)
+
+
 def config_from_preset(enc_mode, width, height, qp=35, temporal_layer_index=1, hierarchical_levels=4, sc_class1=0,
                        rtc_tune=0, fps=30):
     """SvtHipMeConfig of a CLI preset (restates svt_aom_sig_deriv_me, Codec/enc_mode_config.c:681-833)."""

@@ -12,10 +12,7 @@ ALPHAS_FULL = list(range(-16, 17))  # the alpha search's list: slot k is alpha_q
 
 def check_desc(d):
     """svt_hip_cfl_pred_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = api.lib()
-    rc = L.svt_hip_cfl_pred_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_cfl_pred_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+    api.check_desc("svt_hip_cfl_pred_check_desc", d)
 
 
 def pred_desc(bit_depth, width, height, alphas, luma, luma_stride, luma_width, luma_height, planes, slot_stride, jobs, n_jobs, status, ac=None):

@@ -20,7 +20,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
-#include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_cfl.h"
 #include "wave_ops.h"
 
@@ -277,7 +277,6 @@ __global__ __launch_bounds__(64) void cfl_pick_alpha_kernel(const SvtHipCflPickD
 
 extern "C" {
 
-#define BAD(...) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, __VA_ARGS__)
 int svt_hip_cfl_pred_check_desc(const SvtHipCflPredDesc *d) {
     if (!d) BAD("svt_hip_cfl_pred_check_desc: null descriptor");
     if (!d->luma || !d->jobs || !d->status || !d->plane[0].dc || !d->plane[0].dst || !d->plane[1].dc || !d->plane[1].dst)
@@ -314,7 +313,14 @@ int svt_hip_cfl_pred_check_desc(const SvtHipCflPredDesc *d) {
     }
     return SVT_HIP_OK;
 }
-#undef BAD
+
+// svt_hip_cfl_pick_alpha_batch has no check_desc entry: what it refuses
+static int cfl_pick_alpha_check(const SvtHipCflPickDesc *d) {
+    if (!d->bits || !d->dist || !d->mode_bits || !d->alpha_fac_bits || !d->best_rd || !d->cfl_alpha_idx || !d->cfl_alpha_signs || !d->status)
+        BAD("svt_hip_cfl_pick_alpha_batch: a mandatory pointer is null");
+    if (d->itr_th > 16 || d->n_mag == 0 || d->n_mag > 16) BAD("svt_hip_cfl_pick_alpha_batch: itr_th %u (0 .. 16), n_mag %u (1 .. 16)", d->itr_th, d->n_mag);
+    return SVT_HIP_OK;
+}
 
 size_t svt_hip_cfl_layout(int what, int field) {
 #define D(f) offsetof(SvtHipCflPredDesc, f)
@@ -331,39 +337,21 @@ size_t svt_hip_cfl_layout(int what, int field) {
 #undef J
 #undef P
 #undef K
-    const size_t *tab[4]  = {desc, job, plane, pick};
-    const size_t  n[4]    = {sizeof(desc) / sizeof(desc[0]), sizeof(job) / sizeof(job[0]), sizeof(plane) / sizeof(plane[0]), sizeof(pick) / sizeof(pick[0])};
-    const size_t  size[4] = {sizeof(SvtHipCflPredDesc), sizeof(SvtHipCflPredJob), sizeof(SvtHipCflPlane), sizeof(SvtHipCflPickDesc)};
-    if (what < 0 || what > 3) return (size_t)-1;
-    if (field < 0) return size[what];
-    return (size_t)field < n[what] ? tab[what][field] : (size_t)-1;
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipCflPredDesc>(desc), layout_row<SvtHipCflPredJob>(job), layout_row<SvtHipCflPlane>(plane),
+                                    layout_row<SvtHipCflPickDesc>(pick)};
+    return layout_lookup(rows, what, field);
 }
 
 int svt_hip_cfl_pred_batch(SvtHipContext *ctx, const SvtHipCflPredDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_cfl_pred_batch: null context or descriptor");
-    const int rc = svt_hip_cfl_pred_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->bit_depth == 10) launch_pred_w<true>(ctx, *d);
-    else launch_pred_w<false>(ctx, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_cfl_pred_batch", ctx, d, svt_hip_cfl_pred_check_desc, &SvtHipCflPredDesc::n_jobs, [=] {
+        if (d->bit_depth == 10) launch_pred_w<true>(ctx, *d);
+        else launch_pred_w<false>(ctx, *d);
+    });
 }
 
 int svt_hip_cfl_pick_alpha_batch(SvtHipContext *ctx, const SvtHipCflPickDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_cfl_pick_alpha_batch: null context or descriptor");
-    if (!d->bits || !d->dist || !d->mode_bits || !d->alpha_fac_bits || !d->best_rd || !d->cfl_alpha_idx || !d->cfl_alpha_signs || !d->status)
-        return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_cfl_pick_alpha_batch: a mandatory pointer is null");
-    if (d->itr_th > 16 || d->n_mag == 0 || d->n_mag > 16)
-        return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_cfl_pick_alpha_batch: itr_th %u (0 .. 16), n_mag %u (1 .. 16)", d->itr_th, d->n_mag);
-    if (d->n_blocks == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    hipLaunchKernelGGL(cfl_pick_alpha_kernel, dim3((d->n_blocks + 63u) / 64u), dim3(64), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_cfl_pick_alpha_batch", ctx, d, cfl_pick_alpha_check, &SvtHipCflPickDesc::n_blocks,
+                         [=] { hipLaunchKernelGGL(cfl_pick_alpha_kernel, dim3(ceil_div(d->n_blocks, 64)), dim3(64), 0, ctx->stream, *d); });
 }
 
 } // extern "C"

@@ -31,7 +31,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
-#include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_ifs.h"
 #include "wave_ops.h"
 #include "convolve_core.h"
@@ -441,21 +441,13 @@ __global__ __launch_bounds__(256) void ifs_scatter_kernel(const SvtHipIfsScatter
 
 extern "C" {
 
-#define BAD(...) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, __VA_ARGS__)
 int svt_hip_ifs_check_desc(const SvtHipIfsDesc *d) {
     if (!d) BAD("svt_hip_ifs_check_desc: null descriptor");
     if (!d->src || !d->jobs || !d->results || !d->status || !d->switchable_interp_fac_bits)
         BAD("svt_hip_ifs_check_desc: a mandatory pointer (src, jobs, results, status, switchable_interp_fac_bits) is null");
     if (d->bit_depth != 8 && d->bit_depth != 10) BAD("svt_hip_ifs_check_desc: bit_depth %u (8 or 10)", d->bit_depth);
-    if (d->n_refs == 0 || d->n_refs > SVT_HIP_INTER_PRED_MAX_REFS) BAD("svt_hip_ifs_check_desc: %u reference planes (1..%d)", d->n_refs, SVT_HIP_INTER_PRED_MAX_REFS);
-    for (unsigned i = 0; i < d->n_refs; i++) {
-        const SvtHipInterPredRef *r = &d->refs[i];
-        if (!r->plane) BAD("svt_hip_ifs_check_desc: reference %u: null plane", i);
-        if (r->stride == 0 || r->width == 0 || r->height == 0 || r->stride < r->width)
-            BAD("svt_hip_ifs_check_desc: reference %u: stride %u, padded size %u x %u (stride and size non-zero, stride >= width)", i, r->stride, r->width, r->height);
-        if (r->org_x >= r->width || r->org_y >= r->height)
-            BAD("svt_hip_ifs_check_desc: reference %u: origin (%u, %u) outside the padded plane %u x %u", i, r->org_x, r->org_y, r->width, r->height);
-    }
+    const int rc = svt_hip_check_inter_pred_refs("svt_hip_ifs_check_desc", d->refs, d->n_refs);
+    if (rc) return rc;
     if (d->src_stride == 0 || d->src_samples == 0) BAD("svt_hip_ifs_check_desc: src_stride %u / src_samples %llu is zero", d->src_stride, (unsigned long long)d->src_samples);
     if (d->dst && (d->dst_stride == 0 || d->dst_samples == 0))
         BAD("svt_hip_ifs_check_desc: dst with dst_stride %u / dst_samples %llu zero", d->dst_stride, (unsigned long long)d->dst_samples);
@@ -464,7 +456,15 @@ int svt_hip_ifs_check_desc(const SvtHipIfsDesc *d) {
     if (d->smooth_bias_pct > 1000) BAD("svt_hip_ifs_check_desc: smooth_bias_pct %u (0: off, else a percentage up to 1000)", d->smooth_bias_pct);
     return SVT_HIP_OK;
 }
-#undef BAD
+
+// svt_hip_ifs_scatter_filters has no check_desc entry: what it refuses
+static int ifs_scatter_check(const SvtHipIfsScatterDesc *d) {
+    if (!d->patches || !d->results || !d->result_status || !d->base || !d->status)
+        BAD("svt_hip_ifs_scatter_filters: a pointer (patches, results, result_status, base, status) is null");
+    if (d->record_stride == 0 || (uint64_t)d->filter_x_offset + 2 > d->record_stride)
+        BAD("svt_hip_ifs_scatter_filters: record_stride %u, filter_x_offset %u (the two bytes lie inside a record)", d->record_stride, d->filter_x_offset);
+    return SVT_HIP_OK;
+}
 
 const int32_t *svt_hip_ifs_model_table(int which) { return which >= 0 && which < 3 ? h_model[which] : nullptr; }
 
@@ -488,42 +488,20 @@ size_t svt_hip_ifs_layout(int what, int field) {
 #undef R
 #undef P
 #undef S
-    const size_t *tab[5]  = {desc, job, res, pat, sca};
-    const size_t  n[5]    = {sizeof(desc) / sizeof(desc[0]), sizeof(job) / sizeof(job[0]), sizeof(res) / sizeof(res[0]), sizeof(pat) / sizeof(pat[0]),
-                             sizeof(sca) / sizeof(sca[0])};
-    const size_t  size[5] = {sizeof(SvtHipIfsDesc), sizeof(SvtHipIfsJob), sizeof(SvtHipIfsResult), sizeof(SvtHipIfsPatch), sizeof(SvtHipIfsScatterDesc)};
-    if (what < 0 || what > 4) return (size_t)-1;
-    if (field < 0) return size[what];
-    return (size_t)field < n[what] ? tab[what][field] : (size_t)-1;
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipIfsDesc>(desc), layout_row<SvtHipIfsJob>(job), layout_row<SvtHipIfsResult>(res), layout_row<SvtHipIfsPatch>(pat),
+                                    layout_row<SvtHipIfsScatterDesc>(sca)};
+    return layout_lookup(rows, what, field);
 }
 
 int svt_hip_ifs_batch(SvtHipContext *ctx, const SvtHipIfsDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ifs_batch: null context or descriptor");
-    const int rc = svt_hip_ifs_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    const uint32_t grid = (d->n_jobs + (uint32_t)kWaves - 1) / (uint32_t)kWaves;
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->bit_depth == 10) hipLaunchKernelGGL(ifs_kernel<true>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(ifs_kernel<false>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_ifs_batch", ctx, d, svt_hip_ifs_check_desc, &SvtHipIfsDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, ifs_kernel<true>, ifs_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0, ctx->stream, *d);
+    });
 }
 
 int svt_hip_ifs_scatter_filters(SvtHipContext *ctx, const SvtHipIfsScatterDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ifs_scatter_filters: null context or descriptor");
-    if (!d->patches || !d->results || !d->result_status || !d->base || !d->status)
-        return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ifs_scatter_filters: a pointer (patches, results, result_status, base, status) is null");
-    if (d->record_stride == 0 || (uint64_t)d->filter_x_offset + 2 > d->record_stride)
-        return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ifs_scatter_filters: record_stride %u, filter_x_offset %u (the two bytes lie inside a record)",
-                            d->record_stride, d->filter_x_offset);
-    if (d->n_patches == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    hipLaunchKernelGGL(ifs_scatter_kernel, dim3((d->n_patches + 255u) / 256u), dim3(256), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_ifs_scatter_filters", ctx, d, ifs_scatter_check, &SvtHipIfsScatterDesc::n_patches,
+                         [=] { hipLaunchKernelGGL(ifs_scatter_kernel, dim3(ceil_div(d->n_patches, 256)), dim3(256), 0, ctx->stream, *d); });
 }
 
 } // extern "C"

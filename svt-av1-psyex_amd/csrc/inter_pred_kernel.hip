@@ -27,7 +27,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
-#include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_pred.h"
 #include "wave_ops.h"
 #include "convolve_core.h"
@@ -206,28 +206,17 @@ template <bool HBD> __global__ __launch_bounds__(64 * kWaves) void inter_pred_ke
 
 extern "C" {
 
-#define BAD(...) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, __VA_ARGS__)
 int svt_hip_inter_pred_check_desc(const SvtHipInterPredDesc *d) {
     if (!d) BAD("svt_hip_inter_pred_check_desc: null descriptor");
     if (!d->dst || !d->jobs || !d->status) BAD("svt_hip_inter_pred_check_desc: a mandatory pointer (dst, jobs, status) is null");
     if (d->bit_depth != 8 && d->bit_depth != 10) BAD("svt_hip_inter_pred_check_desc: bit_depth %u (8 or 10)", d->bit_depth);
     if (d->ss_x > 1 || d->ss_y > 1) BAD("svt_hip_inter_pred_check_desc: ss_x %u / ss_y %u (0 or 1)", d->ss_x, d->ss_y);
-    if (d->n_refs == 0 || d->n_refs > SVT_HIP_INTER_PRED_MAX_REFS)
-        BAD("svt_hip_inter_pred_check_desc: %u reference planes (1..%d)", d->n_refs, SVT_HIP_INTER_PRED_MAX_REFS);
-    for (unsigned i = 0; i < d->n_refs; i++) {
-        const SvtHipInterPredRef *r = &d->refs[i];
-        if (!r->plane) BAD("svt_hip_inter_pred_check_desc: reference %u: null plane", i);
-        if (r->stride == 0 || r->width == 0 || r->height == 0 || r->stride < r->width)
-            BAD("svt_hip_inter_pred_check_desc: reference %u: stride %u, padded size %u x %u (stride and size non-zero, stride >= width)", i, r->stride,
-                r->width, r->height);
-        if (r->org_x >= r->width || r->org_y >= r->height)
-            BAD("svt_hip_inter_pred_check_desc: reference %u: origin (%u, %u) outside the padded plane %u x %u", i, r->org_x, r->org_y, r->width, r->height);
-    }
+    const int rc = svt_hip_check_inter_pred_refs("svt_hip_inter_pred_check_desc", d->refs, d->n_refs);
+    if (rc) return rc;
     if (d->dst_stride == 0 || d->dst_samples == 0) BAD("svt_hip_inter_pred_check_desc: dst_stride %u / dst_samples %llu is zero", d->dst_stride, (unsigned long long)d->dst_samples);
     if (d->n_mvs && !d->mv_array) BAD("svt_hip_inter_pred_check_desc: n_mvs %u without mv_array", d->n_mvs);
     return SVT_HIP_OK;
 }
-#undef BAD
 
 size_t svt_hip_inter_pred_layout(int what, int field) {
 #define D(f) offsetof(SvtHipInterPredDesc, f)
@@ -242,26 +231,15 @@ size_t svt_hip_inter_pred_layout(int what, int field) {
 #undef D
 #undef J
 #undef R
-    const size_t *tab[3]  = {desc, job, ref};
-    const size_t  n[3]    = {sizeof(desc) / sizeof(desc[0]), sizeof(job) / sizeof(job[0]), sizeof(ref) / sizeof(ref[0])};
-    const size_t  size[3] = {sizeof(SvtHipInterPredDesc), sizeof(SvtHipInterPredJob), sizeof(SvtHipInterPredRef)};
-    if (what < 0 || what > 2) return (size_t)-1;
-    if (field < 0) return size[what];
-    return (size_t)field < n[what] ? tab[what][field] : (size_t)-1;
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipInterPredDesc>(desc), layout_row<SvtHipInterPredJob>(job), layout_row<SvtHipInterPredRef>(ref)};
+    return layout_lookup(rows, what, field);
 }
 
 int svt_hip_inter_pred_batch(SvtHipContext *ctx, const SvtHipInterPredDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_inter_pred_batch: null context or descriptor");
-    const int rc = svt_hip_inter_pred_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    const uint32_t grid = (d->n_jobs + (uint32_t)kWaves - 1) / (uint32_t)kWaves;
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->bit_depth == 10) hipLaunchKernelGGL(inter_pred_kernel<true>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(inter_pred_kernel<false>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_inter_pred_batch", ctx, d, svt_hip_inter_pred_check_desc, &SvtHipInterPredDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, inter_pred_kernel<true>, inter_pred_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
 }
 
 } // extern "C"

@@ -24,7 +24,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
-#include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_intra.h"
 #include "wave_ops.h"
 
@@ -347,7 +347,6 @@ template <bool HBD> __global__ __launch_bounds__(64 * kWaves) void intra_pred_ke
 
 extern "C" {
 
-#define BAD(...) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, __VA_ARGS__)
 int svt_hip_intra_pred_check_desc(const SvtHipIntraPredDesc *d) {
     if (!d) BAD("svt_hip_intra_pred_check_desc: null descriptor");
     if (!d->nbr || !d->dst || !d->jobs || !d->status) BAD("svt_hip_intra_pred_check_desc: a mandatory pointer (nbr, dst, jobs, status) is null");
@@ -363,7 +362,6 @@ int svt_hip_intra_pred_check_desc(const SvtHipIntraPredDesc *d) {
     if (d0 < n1 && n0 < d1) BAD("svt_hip_intra_pred_check_desc: the destination range overlaps the neighbour plane (a batch must not read what it writes)");
     return SVT_HIP_OK;
 }
-#undef BAD
 
 size_t svt_hip_intra_pred_layout(int what, int field) {
 #define D(f) offsetof(SvtHipIntraPredDesc, f)
@@ -374,26 +372,15 @@ size_t svt_hip_intra_pred_layout(int what, int field) {
                                   J(n_left_px), J(n_bottomleft_px), J(filt_type), J(reserved)};
 #undef D
 #undef J
-    const size_t *tab[2]  = {desc, job};
-    const size_t  n[2]    = {sizeof(desc) / sizeof(desc[0]), sizeof(job) / sizeof(job[0])};
-    const size_t  size[2] = {sizeof(SvtHipIntraPredDesc), sizeof(SvtHipIntraPredJob)};
-    if (what < 0 || what > 1) return (size_t)-1;
-    if (field < 0) return size[what];
-    return (size_t)field < n[what] ? tab[what][field] : (size_t)-1;
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipIntraPredDesc>(desc), layout_row<SvtHipIntraPredJob>(job)};
+    return layout_lookup(rows, what, field);
 }
 
 int svt_hip_intra_pred_batch(SvtHipContext *ctx, const SvtHipIntraPredDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_intra_pred_batch: null context or descriptor");
-    const int rc = svt_hip_intra_pred_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    const uint32_t grid = (d->n_jobs + (uint32_t)kWaves - 1) / (uint32_t)kWaves;
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->bit_depth == 10) hipLaunchKernelGGL(intra_pred_kernel<true>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(intra_pred_kernel<false>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_intra_pred_batch", ctx, d, svt_hip_intra_pred_check_desc, &SvtHipIntraPredDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, intra_pred_kernel<true>, intra_pred_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
 }
 
 } // extern "C"

@@ -27,7 +27,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
-#include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_mask.h"
 #include "wave_ops.h"
 #include "convolve_core.h"
@@ -540,7 +540,6 @@ extern "C" {
 const uint8_t *svt_hip_wedge_primaries(void) { return &kWedgeHost.prim[0][0][0]; }
 const uint8_t *svt_hip_wedge_signflip(void) { return &kWedgeHost.flip[0][0]; }
 
-#define BAD(...) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, __VA_ARGS__)
 int svt_hip_masked_pred_check_desc(const SvtHipMaskedPredDesc *d) {
     if (!d) BAD("svt_hip_masked_pred_check_desc: null descriptor");
     if (!d->dst || !d->jobs || !d->status) BAD("svt_hip_masked_pred_check_desc: a mandatory pointer (dst, jobs, status) is null");
@@ -548,17 +547,8 @@ int svt_hip_masked_pred_check_desc(const SvtHipMaskedPredDesc *d) {
     if (d->ss_x > 1 || d->ss_y > 1) BAD("svt_hip_masked_pred_check_desc: ss_x %u / ss_y %u (0 or 1)", d->ss_x, d->ss_y);
     if (d->plane > 2) BAD("svt_hip_masked_pred_check_desc: plane %u (0..2)", d->plane);
     if (d->plane == 0 && (d->ss_x || d->ss_y)) BAD("svt_hip_masked_pred_check_desc: a luma batch with ss_x %u / ss_y %u", d->ss_x, d->ss_y);
-    if (d->n_refs == 0 || d->n_refs > SVT_HIP_INTER_PRED_MAX_REFS)
-        BAD("svt_hip_masked_pred_check_desc: %u reference planes (1..%d)", d->n_refs, SVT_HIP_INTER_PRED_MAX_REFS);
-    for (unsigned i = 0; i < d->n_refs; i++) {
-        const SvtHipInterPredRef *r = &d->refs[i];
-        if (!r->plane) BAD("svt_hip_masked_pred_check_desc: reference %u: null plane", i);
-        if (r->stride == 0 || r->width == 0 || r->height == 0 || r->stride < r->width)
-            BAD("svt_hip_masked_pred_check_desc: reference %u: stride %u, padded size %u x %u (stride and size non-zero, stride >= width)", i, r->stride,
-                r->width, r->height);
-        if (r->org_x >= r->width || r->org_y >= r->height)
-            BAD("svt_hip_masked_pred_check_desc: reference %u: origin (%u, %u) outside the padded plane %u x %u", i, r->org_x, r->org_y, r->width, r->height);
-    }
+    const int rc = svt_hip_check_inter_pred_refs("svt_hip_masked_pred_check_desc", d->refs, d->n_refs);
+    if (rc) return rc;
     if (d->dst_stride == 0 || d->dst_samples == 0) BAD("svt_hip_masked_pred_check_desc: dst_stride %u / dst_samples %llu is zero", d->dst_stride, (unsigned long long)d->dst_samples);
     if (d->n_mvs && !d->mv_array) BAD("svt_hip_masked_pred_check_desc: n_mvs %u without mv_array", d->n_mvs);
     if (d->n_results && !d->results) BAD("svt_hip_masked_pred_check_desc: n_results %u without results", d->n_results);
@@ -590,14 +580,6 @@ int svt_hip_mask_search_check_desc(const SvtHipMaskSearchDesc *d) {
     if (d->intra && (d->intra_stride == 0 || d->intra_samples == 0)) BAD("svt_hip_mask_search_check_desc: intra with a zero stride or sample count");
     return SVT_HIP_OK;
 }
-#undef BAD
-
-static size_t layout_of(const size_t *const *tab, const size_t *n, const size_t *size, int count, int what, int field) {
-    if (what < 0 || what >= count) return (size_t)-1;
-    if (field < 0) return size[what];
-    return (size_t)field < n[what] ? tab[what][field] : (size_t)-1;
-}
-#define COUNT(a) (sizeof(a) / sizeof(a[0]))
 
 size_t svt_hip_masked_pred_layout(int what, int field) {
 #define D(f) offsetof(SvtHipMaskedPredDesc, f)
@@ -612,10 +594,8 @@ size_t svt_hip_masked_pred_layout(int what, int field) {
 #undef D
 #undef J
 #undef R
-    const size_t *tab[3]  = {desc, job, res};
-    const size_t  n[3]    = {COUNT(desc), COUNT(job), COUNT(res)};
-    const size_t  size[3] = {sizeof(SvtHipMaskedPredDesc), sizeof(SvtHipMaskedPredJob), sizeof(SvtHipMaskSearchResult)};
-    return layout_of(tab, n, size, 3, what, field);
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipMaskedPredDesc>(desc), layout_row<SvtHipMaskedPredJob>(job), layout_row<SvtHipMaskSearchResult>(res)};
+    return layout_lookup(rows, what, field);
 }
 
 size_t svt_hip_interintra_blend_layout(int what, int field) {
@@ -627,10 +607,8 @@ size_t svt_hip_interintra_blend_layout(int what, int field) {
                                   J(interintra_mode), J(use_wedge), J(wedge_index), J(wedge_sign), J(flags), J(reserved)};
 #undef D
 #undef J
-    const size_t *tab[2]  = {desc, job};
-    const size_t  n[2]    = {COUNT(desc), COUNT(job)};
-    const size_t  size[2] = {sizeof(SvtHipInterIntraDesc), sizeof(SvtHipInterIntraJob)};
-    return layout_of(tab, n, size, 2, what, field);
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipInterIntraDesc>(desc), layout_row<SvtHipInterIntraJob>(job)};
+    return layout_lookup(rows, what, field);
 }
 
 size_t svt_hip_mask_search_layout(int what, int field) {
@@ -642,31 +620,28 @@ size_t svt_hip_mask_search_layout(int what, int field) {
     static const size_t job[]  = {J(src_offset), J(pred0_offset), J(pred1_offset), J(intra_offset), J(width), J(height), J(kind), J(ii_wedge_mode)};
 #undef D
 #undef J
-    const size_t *tab[2]  = {desc, job};
-    const size_t  n[2]    = {COUNT(desc), COUNT(job)};
-    const size_t  size[2] = {sizeof(SvtHipMaskSearchDesc), sizeof(SvtHipMaskSearchJob)};
-    return layout_of(tab, n, size, 2, what, field);
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipMaskSearchDesc>(desc), layout_row<SvtHipMaskSearchJob>(job)};
+    return layout_lookup(rows, what, field);
 }
-#undef COUNT
+int svt_hip_masked_pred_batch(SvtHipContext *ctx, const SvtHipMaskedPredDesc *d) {
+    return enqueue_batch("svt_hip_masked_pred_batch", ctx, d, svt_hip_masked_pred_check_desc, &SvtHipMaskedPredDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, masked_pred_kernel<true>, masked_pred_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
+}
 
-#define LAUNCH(name, kernel, check)                                                                                                        \
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, name ": null context or descriptor");                            \
-    const int rc = check(d);                                                                                                               \
-    if (rc) return rc;                                                                                                                     \
-    if (d->n_jobs == 0) return SVT_HIP_OK;                                                                                                 \
-    hipSetDevice(ctx->device);                                                                                                             \
-    const uint32_t grid = (d->n_jobs + (uint32_t)kWaves - 1) / (uint32_t)kWaves;                                                           \
-    std::lock_guard<std::mutex> lock(ctx->async_mu);                                                                                       \
-    if (d->bit_depth == 10) hipLaunchKernelGGL(kernel<true>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);                          \
-    else hipLaunchKernelGGL(kernel<false>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);                                            \
-    SVT_HIP_CHECK(ctx, hipGetLastError());                                                                                                 \
-    return SVT_HIP_OK;
-
-int svt_hip_masked_pred_batch(SvtHipContext *ctx, const SvtHipMaskedPredDesc *d) { LAUNCH("svt_hip_masked_pred_batch", masked_pred_kernel, svt_hip_masked_pred_check_desc) }
 int svt_hip_interintra_blend_batch(SvtHipContext *ctx, const SvtHipInterIntraDesc *d) {
-    LAUNCH("svt_hip_interintra_blend_batch", interintra_blend_kernel, svt_hip_interintra_blend_check_desc)
+    return enqueue_batch("svt_hip_interintra_blend_batch", ctx, d, svt_hip_interintra_blend_check_desc, &SvtHipInterIntraDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, interintra_blend_kernel<true>, interintra_blend_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
 }
-int svt_hip_mask_search_batch(SvtHipContext *ctx, const SvtHipMaskSearchDesc *d) { LAUNCH("svt_hip_mask_search_batch", mask_search_kernel, svt_hip_mask_search_check_desc) }
-#undef LAUNCH
+
+int svt_hip_mask_search_batch(SvtHipContext *ctx, const SvtHipMaskSearchDesc *d) {
+    return enqueue_batch("svt_hip_mask_search_batch", ctx, d, svt_hip_mask_search_check_desc, &SvtHipMaskSearchDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, mask_search_kernel<true>, mask_search_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
+}
 
 } // extern "C"

@@ -28,7 +28,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
-#include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_obmc.h"
 #include "wave_ops.h"
 #include "convolve_core.h"
@@ -490,7 +490,6 @@ __global__ void __launch_bounds__(64) obmc_search_kernel(const SvtHipObmcSearchD
 
 extern "C" {
 
-#define BAD(...) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, __VA_ARGS__)
 int svt_hip_obmc_neighbour_check_desc(const SvtHipObmcNeighbourDesc *d) {
     if (!d) BAD("svt_hip_obmc_neighbour_check_desc: null descriptor");
     if (!d->blocks || !d->jobs || !d->above || !d->left || !d->status)
@@ -499,17 +498,8 @@ int svt_hip_obmc_neighbour_check_desc(const SvtHipObmcNeighbourDesc *d) {
     if (d->ss_x > 1 || d->ss_y > 1) BAD("svt_hip_obmc_neighbour_check_desc: ss_x %u / ss_y %u (0 or 1)", d->ss_x, d->ss_y);
     if (d->plane > 2) BAD("svt_hip_obmc_neighbour_check_desc: plane %u (0 luma, 1 Cb, 2 Cr)", d->plane);
     if (d->plane == 0 && (d->ss_x || d->ss_y)) BAD("svt_hip_obmc_neighbour_check_desc: a luma batch with sub-sampling %u / %u", d->ss_x, d->ss_y);
-    if (d->n_refs == 0 || d->n_refs > SVT_HIP_INTER_PRED_MAX_REFS)
-        BAD("svt_hip_obmc_neighbour_check_desc: %u reference planes (1..%d)", d->n_refs, SVT_HIP_INTER_PRED_MAX_REFS);
-    for (unsigned i = 0; i < d->n_refs; i++) {
-        const SvtHipInterPredRef *r = &d->refs[i];
-        if (!r->plane) BAD("svt_hip_obmc_neighbour_check_desc: reference %u: null plane", i);
-        if (r->stride == 0 || r->width == 0 || r->height == 0 || r->stride < r->width)
-            BAD("svt_hip_obmc_neighbour_check_desc: reference %u: stride %u, padded size %u x %u (stride and size non-zero, stride >= width)", i, r->stride,
-                r->width, r->height);
-        if (r->org_x >= r->width || r->org_y >= r->height)
-            BAD("svt_hip_obmc_neighbour_check_desc: reference %u: origin (%u, %u) outside the padded plane %u x %u", i, r->org_x, r->org_y, r->width, r->height);
-    }
+    const int rc = svt_hip_check_inter_pred_refs("svt_hip_obmc_neighbour_check_desc", d->refs, d->n_refs);
+    if (rc) return rc;
     if (d->n_blocks == 0 || d->strip_samples == 0)
         BAD("svt_hip_obmc_neighbour_check_desc: n_blocks %u / strip_samples %llu is zero", d->n_blocks, (unsigned long long)d->strip_samples);
     if (d->n_mvs && !d->mv_array) BAD("svt_hip_obmc_neighbour_check_desc: n_mvs %u without mv_array", d->n_mvs);
@@ -556,7 +546,6 @@ int svt_hip_obmc_search_check_desc(const SvtHipObmcSearchDesc *d) {
             (unsigned long long)d->target_values);
     return SVT_HIP_OK;
 }
-#undef BAD
 
 size_t svt_hip_obmc_layout(int what, int field) {
 #define N(f) offsetof(SvtHipObmcNeighbourDesc, f)
@@ -593,72 +582,38 @@ size_t svt_hip_obmc_layout(int what, int field) {
 #undef K
 #undef H
 #undef J
-    const size_t *tab[9]  = {nbd, bld, tgd, blk, nbr, job, sed, sej, ser};
-    const size_t  n[9]    = {sizeof(nbd) / sizeof(size_t), sizeof(bld) / sizeof(size_t), sizeof(tgd) / sizeof(size_t), sizeof(blk) / sizeof(size_t),
-                             sizeof(nbr) / sizeof(size_t), sizeof(job) / sizeof(size_t), sizeof(sed) / sizeof(size_t), sizeof(sej) / sizeof(size_t),
-                             sizeof(ser) / sizeof(size_t)};
-    const size_t  size[9] = {sizeof(SvtHipObmcNeighbourDesc), sizeof(SvtHipObmcBlendDesc), sizeof(SvtHipObmcTargetDesc), sizeof(SvtHipObmcBlock),
-                             sizeof(SvtHipObmcNeighbour), sizeof(SvtHipObmcJob), sizeof(SvtHipObmcSearchDesc), sizeof(SvtHipObmcSearchJob),
-                             sizeof(SvtHipObmcSearchResult)};
-    if (what < 0 || what > 8) return (size_t)-1;
-    if (field < 0) return size[what];
-    return (size_t)field < n[what] ? tab[what][field] : (size_t)-1;
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipObmcNeighbourDesc>(nbd), layout_row<SvtHipObmcBlendDesc>(bld),  layout_row<SvtHipObmcTargetDesc>(tgd),
+                                    layout_row<SvtHipObmcBlock>(blk),         layout_row<SvtHipObmcNeighbour>(nbr),  layout_row<SvtHipObmcJob>(job),
+                                    layout_row<SvtHipObmcSearchDesc>(sed),    layout_row<SvtHipObmcSearchJob>(sej),  layout_row<SvtHipObmcSearchResult>(ser)};
+    return layout_lookup(rows, what, field);
 }
 
 const uint8_t *svt_hip_obmc_masks(void) { return h_obmc_mask; }
 
 int svt_hip_obmc_neighbour_batch(SvtHipContext *ctx, const SvtHipObmcNeighbourDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_obmc_neighbour_batch: null context or descriptor");
-    const int rc = svt_hip_obmc_neighbour_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    const uint32_t grid = (d->n_jobs + (uint32_t)kWaves - 1) / (uint32_t)kWaves;
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->bit_depth == 10) hipLaunchKernelGGL(obmc_neighbour_kernel<true>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(obmc_neighbour_kernel<false>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_obmc_neighbour_batch", ctx, d, svt_hip_obmc_neighbour_check_desc, &SvtHipObmcNeighbourDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, obmc_neighbour_kernel<true>, obmc_neighbour_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
 }
 
 int svt_hip_obmc_blend_batch(SvtHipContext *ctx, const SvtHipObmcBlendDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_obmc_blend_batch: null context or descriptor");
-    const int rc = svt_hip_obmc_blend_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    const uint32_t grid = (d->n_jobs + (uint32_t)kWaves - 1) / (uint32_t)kWaves;
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->bit_depth == 10) hipLaunchKernelGGL(obmc_blend_kernel<true>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(obmc_blend_kernel<false>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_obmc_blend_batch", ctx, d, svt_hip_obmc_blend_check_desc, &SvtHipObmcBlendDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, obmc_blend_kernel<true>, obmc_blend_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
 }
 
 int svt_hip_obmc_target_batch(SvtHipContext *ctx, const SvtHipObmcTargetDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_obmc_target_batch: null context or descriptor");
-    const int rc = svt_hip_obmc_target_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    const uint32_t grid = (d->n_jobs + (uint32_t)kWaves - 1) / (uint32_t)kWaves;
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->strip_bit_depth == 10) hipLaunchKernelGGL(obmc_target_kernel<true>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(obmc_target_kernel<false>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_obmc_target_batch", ctx, d, svt_hip_obmc_target_check_desc, &SvtHipObmcTargetDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->strip_bit_depth, obmc_target_kernel<true>, obmc_target_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
 }
 
 int svt_hip_obmc_search_batch(SvtHipContext *ctx, const SvtHipObmcSearchDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_obmc_search_batch: null context or descriptor");
-    const int rc = svt_hip_obmc_search_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    hipLaunchKernelGGL(obmc_search_kernel, dim3(d->n_jobs), dim3(64), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_obmc_search_batch", ctx, d, svt_hip_obmc_search_check_desc, &SvtHipObmcSearchDesc::n_jobs,
+                         [=] { hipLaunchKernelGGL(obmc_search_kernel, dim3(d->n_jobs), dim3(64), 0, ctx->stream, *d); });
 }
 
 } // extern "C"

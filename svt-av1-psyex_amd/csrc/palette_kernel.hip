@@ -27,7 +27,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
-#include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_palette.h"
 #include "wave_ops.h"
 
@@ -453,7 +453,6 @@ template <bool HBD> __global__ __launch_bounds__(64 * kWaves) void palette_pred_
 
 extern "C" {
 
-#define BAD(...) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, __VA_ARGS__)
 int svt_hip_palette_check_desc(const SvtHipPaletteDesc *d) {
     if (!d) BAD("svt_hip_palette_check_desc: null descriptor");
     if (!d->src || !d->jobs || !d->results || !d->status || !d->palette_ycolor_fac_bitss || !d->palette_ysize_fac_bits || !d->palette_ymode_fac_bits)
@@ -481,7 +480,6 @@ int svt_hip_palette_pred_check_desc(const SvtHipPalettePredDesc *d) {
     if (d->color_map && d->map_bytes == 0) BAD("svt_hip_palette_pred_check_desc: color_map with map_bytes zero");
     return SVT_HIP_OK;
 }
-#undef BAD
 
 size_t svt_hip_palette_layout(int what, int field) {
 #define D(f) offsetof(SvtHipPaletteDesc, f)
@@ -507,43 +505,23 @@ size_t svt_hip_palette_layout(int what, int field) {
 #undef R
 #undef P
 #undef Q
-#define N(a) (sizeof(a) / sizeof(a[0]))
-    const size_t *tab[6]  = {desc, job, cand, res, pjob, pdes};
-    const size_t  n[6]    = {N(desc), N(job), N(cand), N(res), N(pjob), N(pdes)};
-#undef N
-    const size_t  size[6] = {sizeof(SvtHipPaletteDesc), sizeof(SvtHipPaletteJob), sizeof(SvtHipPaletteCand), sizeof(SvtHipPaletteResult),
-                             sizeof(SvtHipPalettePredJob), sizeof(SvtHipPalettePredDesc)};
-    if (what < 0 || what > 5) return (size_t)-1;
-    if (field < 0) return size[what];
-    return (size_t)field < n[what] ? tab[what][field] : (size_t)-1;
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipPaletteDesc>(desc),  layout_row<SvtHipPaletteJob>(job),     layout_row<SvtHipPaletteCand>(cand),
+                                    layout_row<SvtHipPaletteResult>(res), layout_row<SvtHipPalettePredJob>(pjob), layout_row<SvtHipPalettePredDesc>(pdes)};
+    return layout_lookup(rows, what, field);
 }
 
 int svt_hip_palette_search_batch(SvtHipContext *ctx, const SvtHipPaletteDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_palette_search_batch: null context or descriptor");
-    const int rc = svt_hip_palette_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    const uint32_t grid = (d->n_jobs + (uint32_t)kWaves - 1) / (uint32_t)kWaves;
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->bit_depth == 10) hipLaunchKernelGGL(palette_search_kernel<true>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(palette_search_kernel<false>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_palette_search_batch", ctx, d, svt_hip_palette_check_desc, &SvtHipPaletteDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, palette_search_kernel<true>, palette_search_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
 }
 
 int svt_hip_palette_pred_batch(SvtHipContext *ctx, const SvtHipPalettePredDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_palette_pred_batch: null context or descriptor");
-    const int rc = svt_hip_palette_pred_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    const uint32_t grid = (d->n_jobs + (uint32_t)kWaves - 1) / (uint32_t)kWaves;
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->bit_depth == 10) hipLaunchKernelGGL(palette_pred_kernel<true>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(palette_pred_kernel<false>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_palette_pred_batch", ctx, d, svt_hip_palette_pred_check_desc, &SvtHipPalettePredDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, palette_pred_kernel<true>, palette_pred_kernel<false>), dim3(ceil_div(d->n_jobs, kWaves)), dim3(64 * kWaves), 0,
+                           ctx->stream, *d);
+    });
 }
 
 } // extern "C"

@@ -24,7 +24,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
-#include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_warp.h"
 #include "wave_ops.h"
 #include "mv_cost.h"
@@ -501,7 +501,6 @@ template <int WAVES> __global__ __launch_bounds__(64 * WAVES) void wm_refine_ker
 
 extern "C" {
 
-#define BAD(...) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, __VA_ARGS__)
 static int check_refs(const char *who, const SvtHipWarpRef *refs, int n_refs) {
     for (int i = 0; i < n_refs; i++) {
         const SvtHipWarpRef *r = &refs[i];
@@ -543,7 +542,13 @@ int svt_hip_wm_refine_check_desc(const SvtHipWmRefineDesc *d) {
     if (!d->approx_inter_rate && (!d->mvjcost || !d->mvcost[0] || !d->mvcost[1])) BAD("svt_hip_wm_refine_check_desc: a cost table is null and approx_inter_rate is not set");
     return SVT_HIP_OK;
 }
-#undef BAD
+
+// svt_hip_warp_model_batch has no check_desc entry: what it refuses
+static int warp_model_check(const SvtHipWarpModelDesc *d) {
+    if (!d->jobs || !d->models || !d->status) BAD("svt_hip_warp_model_batch: a mandatory pointer (jobs, models, status) is null");
+    if (d->n_mvs && !d->mv_array) BAD("svt_hip_warp_model_batch: n_mvs %u without mv_array", d->n_mvs);
+    return SVT_HIP_OK;
+}
 
 size_t svt_hip_warp_layout(int what, int field) {
 #define D(f) offsetof(SvtHipWarpPredDesc, f)
@@ -576,56 +581,31 @@ size_t svt_hip_warp_layout(int what, int field) {
 #undef K
 #undef F
 #undef G
-#define N(a) (sizeof(a) / sizeof((a)[0]))
-    const size_t *tab[8]  = {desc, job, ref, model, mdesc, mjob, rdesc, rjob};
-    const size_t  n[8]    = {N(desc), N(job), N(ref), N(model), N(mdesc), N(mjob), N(rdesc), N(rjob)};
-    const size_t  size[8] = {sizeof(SvtHipWarpPredDesc), sizeof(SvtHipWarpPredJob), sizeof(SvtHipWarpRef), sizeof(SvtHipWarpModel), sizeof(SvtHipWarpModelDesc),
-                             sizeof(SvtHipWarpModelJob), sizeof(SvtHipWmRefineDesc), sizeof(SvtHipWmRefineJob)};
-#undef N
-    if (what < 0 || what > 7) return (size_t)-1;
-    if (field < 0) return size[what];
-    return (size_t)field < n[what] ? tab[what][field] : (size_t)-1;
+    const SvtHipLayoutRow rows[] = {layout_row<SvtHipWarpPredDesc>(desc),   layout_row<SvtHipWarpPredJob>(job),   layout_row<SvtHipWarpRef>(ref),
+                                    layout_row<SvtHipWarpModel>(model),     layout_row<SvtHipWarpModelDesc>(mdesc), layout_row<SvtHipWarpModelJob>(mjob),
+                                    layout_row<SvtHipWmRefineDesc>(rdesc), layout_row<SvtHipWmRefineJob>(rjob)};
+    return layout_lookup(rows, what, field);
 }
 
 const int16_t  *svt_hip_warp_filter_table(void) { return &kTablesHost.filter[0][0]; }
 const uint16_t *svt_hip_warp_div_lut(void) { return kTablesHost.div_lut; }
 
 int svt_hip_warp_pred_batch(SvtHipContext *ctx, const SvtHipWarpPredDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_warp_pred_batch: null context or descriptor");
-    const int rc = svt_hip_warp_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->bit_depth == 10) hipLaunchKernelGGL(warp_pred_kernel<true>, dim3(d->n_jobs), dim3(64 * kWaves), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(warp_pred_kernel<false>, dim3(d->n_jobs), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_warp_pred_batch", ctx, d, svt_hip_warp_check_desc, &SvtHipWarpPredDesc::n_jobs, [=] {
+        hipLaunchKernelGGL(pick_hbd(d->bit_depth, warp_pred_kernel<true>, warp_pred_kernel<false>), dim3(d->n_jobs), dim3(64 * kWaves), 0, ctx->stream, *d);
+    });
 }
 
 int svt_hip_warp_model_batch(SvtHipContext *ctx, const SvtHipWarpModelDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_warp_model_batch: null context or descriptor");
-    if (!d->jobs || !d->models || !d->status) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_warp_model_batch: a mandatory pointer (jobs, models, status) is null");
-    if (d->n_mvs && !d->mv_array) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_warp_model_batch: n_mvs %u without mv_array", d->n_mvs);
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    hipLaunchKernelGGL(warp_model_kernel, dim3((d->n_jobs + 63u) / 64u), dim3(64), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_warp_model_batch", ctx, d, warp_model_check, &SvtHipWarpModelDesc::n_jobs,
+                         [=] { hipLaunchKernelGGL(warp_model_kernel, dim3(ceil_div(d->n_jobs, 64)), dim3(64), 0, ctx->stream, *d); });
 }
 
 int svt_hip_wm_refine_batch(SvtHipContext *ctx, const SvtHipWmRefineDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_wm_refine_batch: null context or descriptor");
-    const int rc = svt_hip_wm_refine_check_desc(d);
-    if (rc) return rc;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    if (d->waves_per_job == 1) hipLaunchKernelGGL(wm_refine_kernel<1>, dim3(d->n_jobs), dim3(64), 0, ctx->stream, *d);
-    else hipLaunchKernelGGL(wm_refine_kernel<kWaves>, dim3(d->n_jobs), dim3(64 * kWaves), 0, ctx->stream, *d);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_wm_refine_batch", ctx, d, svt_hip_wm_refine_check_desc, &SvtHipWmRefineDesc::n_jobs, [=] {
+        if (d->waves_per_job == 1) hipLaunchKernelGGL(wm_refine_kernel<1>, dim3(d->n_jobs), dim3(64), 0, ctx->stream, *d);
+        else hipLaunchKernelGGL(wm_refine_kernel<kWaves>, dim3(d->n_jobs), dim3(64 * kWaves), 0, ctx->stream, *d);
+    });
 }
 
 } // extern "C"

@@ -12,10 +12,7 @@ PARAMS = ("enable_dual_filter", "subsampled_distortion", "skip_sse_rd_model", "s
 
 def check_desc(d):
     """svt_hip_ifs_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = api.lib()
-    rc = L.svt_hip_ifs_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_ifs_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+    api.check_desc("svt_hip_ifs_check_desc", d)
 
 
 def model_tables():

@@ -9,10 +9,7 @@ from . import abi, api
 
 def check_desc(d):
     """svt_hip_intra_pred_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = api.lib()
-    rc = L.svt_hip_intra_pred_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_intra_pred_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+    api.check_desc("svt_hip_intra_pred_check_desc", d)
 
 
 def run_intra_pred_device(ctx, bit_depth, disable_edge_filter, nbr, nbr_stride, nbr_width, nbr_height, dst, dst_stride, jobs, n_jobs, status, dst_samples=None):

@@ -6,28 +6,22 @@ import ctypes as C
 import numpy as np
 
 from . import abi, api
+from .api import ptr as _ptr, samples as _samples
 
 WEDGE_SIZES = [(8, 8), (8, 16), (16, 8), (16, 16), (16, 32), (32, 16), (32, 32), (8, 32), (32, 8)]  # (width, height), the order of the sign-flip table
 
 
-def _check(name, d):
-    L = api.lib()
-    rc = getattr(L, name)(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"{name}: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
-
-
 def check_pred_desc(d):
     """svt_hip_masked_pred_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    _check("svt_hip_masked_pred_check_desc", d)
+    api.check_desc("svt_hip_masked_pred_check_desc", d)
 
 
 def check_blend_desc(d):
-    _check("svt_hip_interintra_blend_check_desc", d)
+    api.check_desc("svt_hip_interintra_blend_check_desc", d)
 
 
 def check_search_desc(d):
-    _check("svt_hip_mask_search_check_desc", d)
+    api.check_desc("svt_hip_mask_search_check_desc", d)
 
 
 def wedge_tables():
@@ -36,14 +30,6 @@ def wedge_tables():
     L.svt_hip_wedge_primaries.restype = C.POINTER(C.c_uint8 * (12 * 4096))
     L.svt_hip_wedge_signflip.restype = C.POINTER(C.c_uint8 * (9 * 16))
     return (np.array(L.svt_hip_wedge_primaries().contents, np.uint8).reshape(2, 6, 64, 64), np.array(L.svt_hip_wedge_signflip().contents, np.uint8).reshape(9, 16))
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _samples(t, bit_depth):
-    return t.numel() * t.element_size() // (2 if bit_depth > 8 else 1)
 
 
 def run_masked_pred_device(ctx, bit_depth, ss_x, ss_y, plane, refs, dst, dst_stride, jobs, n_jobs, status, mv_array=None, n_mvs=0, results=None, n_results=0,

@@ -6,26 +6,20 @@ import ctypes as C
 import numpy as np
 
 from . import abi, api
-
-
-def _check(name, d):
-    L = api.lib()
-    rc = getattr(L, name)(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"{name}: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+from .api import ptr as _ptr, samples as _samples
 
 
 def check_neighbour_desc(d):
     """svt_hip_obmc_neighbour_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    _check("svt_hip_obmc_neighbour_check_desc", d)
+    api.check_desc("svt_hip_obmc_neighbour_check_desc", d)
 
 
 def check_blend_desc(d):
-    _check("svt_hip_obmc_blend_check_desc", d)
+    api.check_desc("svt_hip_obmc_blend_check_desc", d)
 
 
 def check_target_desc(d):
-    _check("svt_hip_obmc_target_check_desc", d)
+    api.check_desc("svt_hip_obmc_target_check_desc", d)
 
 
 def masks():
@@ -33,14 +27,6 @@ def masks():
     L = api.lib()
     L.svt_hip_obmc_masks.restype = C.POINTER(C.c_uint8 * 64)
     return np.array(L.svt_hip_obmc_masks().contents, np.uint8)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _samples(t, bit_depth):
-    return t.numel() * t.element_size() // (2 if bit_depth > 8 else 1)
 
 
 def run_neighbour_device(ctx, bit_depth, ss_x, ss_y, plane, refs, blocks, n_blocks, jobs, n_jobs, above, left, status, mv_array=None, n_mvs=0, strip_samples=None):
@@ -152,7 +138,7 @@ def run_target_hip(ctx, strip_bit_depth, blocks, jobs, above, left, src, out_val
 
 
 def check_search_desc(d):
-    _check("svt_hip_obmc_search_check_desc", d)
+    api.check_desc("svt_hip_obmc_search_check_desc", d)
 
 
 MV_CENTRE = 1 << 14  # the cost tables hold the entries [-16384, 16384]; the descriptor points at the centre

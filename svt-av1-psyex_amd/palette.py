@@ -5,28 +5,19 @@ import ctypes as C
 import numpy as np
 
 from . import abi, api
+from .api import samples as _samples
 
 PARAMS = ("cost_bit_depth", "dominant_color_step", "reduce_palette_cost_precision")
 
 
 def check_desc(d):
     """svt_hip_palette_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = api.lib()
-    rc = L.svt_hip_palette_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_palette_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+    api.check_desc("svt_hip_palette_check_desc", d)
 
 
 def check_pred_desc(d):
     """svt_hip_palette_pred_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = api.lib()
-    rc = L.svt_hip_palette_pred_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_palette_pred_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
-
-
-def _samples(t, bit_depth):
-    return t.numel() * t.element_size() // (2 if bit_depth > 8 else 1)
+    api.check_desc("svt_hip_palette_pred_check_desc", d)
 
 
 def run_search_device(ctx, bit_depth, src, src_stride, jobs, n_jobs, tables, results, status, params, color_maps=None, src_samples=None, map_bytes=None):

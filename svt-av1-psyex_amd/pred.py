@@ -14,10 +14,7 @@ def plane_ref(tensor, stride, org_x, org_y, width, height):
 
 def check_desc(d):
     """svt_hip_inter_pred_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = api.lib()
-    rc = L.svt_hip_inter_pred_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_inter_pred_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+    api.check_desc("svt_hip_inter_pred_check_desc", d)
 
 
 def run_inter_pred_device(ctx, bit_depth, ss_x, ss_y, refs, dst, dst_stride, jobs, n_jobs, status, mv_array=None, n_mvs=0, dst_samples=None):

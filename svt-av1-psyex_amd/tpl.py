@@ -48,10 +48,7 @@ def make_desc(case, pad, cur, recon, refs, me, tpl_stats, tpl_src_stats):
 
 def check_desc(d):
     """svt_hip_tpl_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = _lib()
-    rc = L.svt_hip_tpl_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_tpl_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+    api.check_desc("svt_hip_tpl_check_desc", d)
 
 
 def upload_case(case):
@@ -135,10 +132,7 @@ def make_group_desc(win, stages, grids, outputs=None, dispense=None):
 
 def group_check_desc(d):
     """svt_hip_tpl_group_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = _group_lib()
-    rc = L.svt_hip_tpl_group_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_tpl_group_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+    api.check_desc("svt_hip_tpl_group_check_desc", d)
 
 
 def upload_window(win, n_beta, n_scaling, tail=4):

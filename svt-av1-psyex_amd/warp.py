@@ -16,10 +16,7 @@ def plane_ref(tensor, stride, org_x, org_y, width, height, rows):
 
 def check_desc(d):
     """svt_hip_warp_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = api.lib()
-    rc = L.svt_hip_warp_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_warp_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+    api.check_desc("svt_hip_warp_check_desc", d)
 
 
 def pred_desc(bit_depth, ss_x, ss_y, refs, dst, dst_stride, dst_samples, jobs, n_jobs, status, models=None, n_models=0):
@@ -123,10 +120,7 @@ def refine_desc(n_jobs, settings, refs, src, src_stride, src_samples, jobs, outs
 
 def check_refine_desc(d):
     """svt_hip_wm_refine_check_desc: raises api.SvtHipError when the descriptor is refused."""
-    L = api.lib()
-    rc = L.svt_hip_wm_refine_check_desc(C.byref(d))
-    if rc:
-        raise api.SvtHipError(f"svt_hip_wm_refine_check_desc: {api.ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
+    api.check_desc("svt_hip_wm_refine_check_desc", d)
 
 
 def run_wm_refine_device(ctx, settings, refs, src, src_stride, jobs, n_jobs, mv_array=None, n_mvs=0, cost_tables=None, waves_per_job=0, spare=0, fill=0,

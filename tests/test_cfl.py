@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 import cfl_cases as cc
+from abi_mirror import check_layout
+from batch_entry_cases import good_cfl_pick_desc, good_cfl_pred_desc as good_desc
 from svt_av1_psyex_amd import abi, api, cfl
 
 BAD_PARAM = 2
@@ -81,15 +83,7 @@ def test_the_cases_are_what_the_issue_lists():
 
 
 def test_struct_layouts_match_the_library():
-    L = api.lib()
-    L.svt_hip_cfl_layout.restype = C.c_size_t
-    for what, t in enumerate((abi.CflPredDesc, abi.CflPredJob, abi.CflPlane, abi.CflPickDesc)):
-        assert L.svt_hip_cfl_layout(what, -1) == C.sizeof(t), t.__name__
-        for i, (name, *_) in enumerate(t._fields_):
-            assert L.svt_hip_cfl_layout(what, i) == getattr(t, name).offset, (t.__name__, name)
-        assert L.svt_hip_cfl_layout(what, len(t._fields_)) == C.c_size_t(-1).value  # no member is left out of the mirror
-        assert C.sizeof(t) % 8 == 0
-    assert L.svt_hip_cfl_layout(4, -1) == C.c_size_t(-1).value
+    check_layout("svt_hip_cfl_layout", (abi.CflPredDesc, abi.CflPredJob, abi.CflPlane, abi.CflPickDesc), multiple_of_8=True)
     dt = np.dtype(abi.CFL_PRED_JOB_DTYPE)
     assert dt.itemsize == C.sizeof(abi.CflPredJob) and abi.CFL_PRED_JOB_DTYPE == cc.JOB_DTYPE
     for name, *_ in abi.CflPredJob._fields_:
@@ -97,13 +91,6 @@ def test_struct_layouts_match_the_library():
     assert (abi.CFL_OK, abi.CFL_UNDEFINED, abi.CFL_SLOTS, abi.CFL_MAX_MODE_COST) == (cc.ST_OK, cc.ST_UNDEFINED, cc.SLOTS, cc.MAX_MODE_COST)
     assert (abi.CFL_PICK_TRUNCATED, abi.CFL_PICK_UNDEFINED) == (cc.PICK_TRUNCATED, cc.PICK_UNDEFINED)
     assert cfl.ALPHAS_FULL == cc.ALPHAS_FULL
-
-
-def good_desc(bd=10, n_alpha=33):
-    p = 0x100000  # never dereferenced: the validation reads the descriptor alone
-    planes = [dict(dc=p + 0x100000 * (1 + q), dc_stride=128, dc_samples=128 * 72, dst=p + 0x1000000 * (1 + q), dst_stride=128, dst_samples=33 * 128 * 72)
-              for q in range(2)]
-    return cfl.pred_desc(bd, 8, 16, list(range(-16, 17))[:n_alpha], p, 256, 208, 144, planes, 128 * 72, p, 4, p, p + 8)
 
 
 def test_check_desc_accepts_a_good_descriptor():
@@ -168,9 +155,7 @@ def test_batch_rejects_a_bad_descriptor_without_a_gpu(bad):
 def test_pick_rejects_a_bad_descriptor_without_a_gpu(bad):
     L = api.lib()
     ctx = C.create_string_buffer(8192)
-    p = 0x100000
-    d = abi.CflPickDesc(n_blocks=3, lambda_=41000, itr_th=1, n_mag=16, dist_stride=1, bits=p, dist=p, mode_bits=p, alpha_fac_bits=p, best_rd=p, cfl_alpha_idx=p,
-                        cfl_alpha_signs=p, status=p)
+    d = good_cfl_pick_desc()
     if bad == "null_ctx":
         assert L.svt_hip_cfl_pick_alpha_batch(None, C.byref(d)) == BAD_PARAM
     elif bad == "null_desc":

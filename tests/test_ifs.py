@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 
 import ifs_cases as ic
+from abi_mirror import check_layout
+from batch_entry_cases import good_ifs_desc as valid_desc
 from svt_av1_psyex_amd import abi, api, ifs
 
 
@@ -53,15 +55,12 @@ def test_model_tables_equal_the_librarys():
     assert L.svt_hip_ifs_model_table(3) is None and L.svt_hip_ifs_model_table(-1) is None
 
 
-@pytest.mark.parametrize("what,struct", enumerate([abi.IfsDesc, abi.IfsJob, abi.IfsResult, abi.IfsPatch, abi.IfsScatterDesc]))
+STRUCTS = [abi.IfsDesc, abi.IfsJob, abi.IfsResult, abi.IfsPatch, abi.IfsScatterDesc]
+
+
+@pytest.mark.parametrize("what,struct", enumerate(STRUCTS))
 def test_struct_layouts_equal_the_librarys(what, struct):
-    L = api.lib()
-    L.svt_hip_ifs_layout.restype = C.c_size_t
-    assert L.svt_hip_ifs_layout(what, -1) == C.sizeof(struct)
-    for i, f in enumerate(struct._fields_):
-        assert L.svt_hip_ifs_layout(what, i) == getattr(struct, f[0]).offset, f[0]
-    assert L.svt_hip_ifs_layout(what, len(struct._fields_)) == C.c_size_t(-1).value
-    assert L.svt_hip_ifs_layout(5, -1) == C.c_size_t(-1).value
+    check_layout("svt_hip_ifs_layout", STRUCTS, only=(what,))
 
 
 def test_record_dtypes_equal_the_structs():
@@ -71,14 +70,6 @@ def test_record_dtypes_equal_the_structs():
         for name, *_ in struct._fields_:
             assert dt.fields[name][1] == getattr(struct, name).offset, name
     assert np.dtype(ic.JOB_DTYPE) == np.dtype(abi.IFS_JOB_DTYPE) and np.dtype(ic.RESULT_DTYPE) == np.dtype(abi.IFS_RESULT_DTYPE)
-
-
-def valid_desc():
-    d = abi.IfsDesc(bit_depth=8, n_refs=2, n_jobs=1, n_mvs=2, src=64, src_stride=256, dst_stride=256, src_samples=4096, dst=64, dst_samples=4096, jobs=64,
-                    mv_array=64, quantizer=400, lambda_=3000, smooth_bias_pct=130, psy_rd=1.0, switchable_interp_fac_bits=64, results=64, rd=64, sse=64, status=64)
-    for i in range(2):
-        d.refs[i] = abi.InterPredRef(plane=64, stride=512, org_x=160, org_y=160, width=512, height=448)
-    return d
 
 
 def test_check_desc_accepts_and_refuses():

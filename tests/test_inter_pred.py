@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 
 import inter_pred_cases as ip
+from abi_mirror import check_layout
+from batch_entry_cases import good_inter_pred_desc as good_desc
 from svt_av1_psyex_amd import abi, api, pred
 
 BAD_PARAM = 2
@@ -96,28 +98,13 @@ def test_the_cases_are_what_the_issue_lists():
 
 
 def test_struct_layouts_match_the_library():
-    L = api.lib()
-    L.svt_hip_inter_pred_layout.restype = C.c_size_t
-    for what, t in enumerate((abi.InterPredDesc, abi.InterPredJob, abi.InterPredRef)):
-        assert L.svt_hip_inter_pred_layout(what, -1) == C.sizeof(t), t.__name__
-        for i, (name, *_) in enumerate(t._fields_):
-            assert L.svt_hip_inter_pred_layout(what, i) == getattr(t, name).offset, (t.__name__, name)
-        assert L.svt_hip_inter_pred_layout(what, len(t._fields_)) == C.c_size_t(-1).value  # no member is left out of the mirror
-        assert C.sizeof(t) % 8 == 0
+    check_layout("svt_hip_inter_pred_layout", (abi.InterPredDesc, abi.InterPredJob, abi.InterPredRef), multiple_of_8=True)
     dt = np.dtype(abi.INTER_PRED_JOB_DTYPE)
     assert dt.itemsize == C.sizeof(abi.InterPredJob) and abi.INTER_PRED_JOB_DTYPE == ip.JOB_DTYPE
     for name, *_ in abi.InterPredJob._fields_:
         assert dt.fields[name][1] == getattr(abi.InterPredJob, name).offset, name
     assert (abi.INTER_PRED_NO_REF, abi.INTER_PRED_MV0_FROM_ARRAY, abi.INTER_PRED_MV1_FROM_ARRAY) == (ip.NO_REF, ip.MV0_FROM_ARRAY, ip.MV1_FROM_ARRAY)
     assert (abi.INTER_PRED_OK, abi.INTER_PRED_UNDEFINED) == (ip.ST_OK, ip.ST_UNDEFINED)
-
-
-def good_desc(n_refs=2):
-    p = 0x1000  # never dereferenced: the validation reads the descriptor alone
-    d = abi.InterPredDesc(bit_depth=10, ss_x=1, ss_y=1, n_refs=n_refs, n_jobs=4, dst=p, dst_stride=256, dst_samples=256 * 64, jobs=p, status=p)
-    for i in range(min(n_refs, abi.INTER_PRED_MAX_REFS)):
-        d.refs[i] = abi.InterPredRef(plane=p, stride=512, org_x=160, org_y=160, width=512, height=448)
-    return d
 
 
 def test_check_desc_accepts_a_good_descriptor():

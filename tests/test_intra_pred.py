@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 import intra_pred_cases as ic
+from abi_mirror import check_layout
+from batch_entry_cases import good_intra_pred_desc as good_desc
 from svt_av1_psyex_amd import abi, api, intra
 
 BAD_PARAM = 2
@@ -125,27 +127,13 @@ def test_filter_intra_anti_diagonals_are_independent(tx):
 
 
 def test_struct_layouts_match_the_library():
-    L = api.lib()
-    L.svt_hip_intra_pred_layout.restype = C.c_size_t
-    for what, t in enumerate((abi.IntraPredDesc, abi.IntraPredJob)):
-        assert L.svt_hip_intra_pred_layout(what, -1) == C.sizeof(t), t.__name__
-        for i, (name, *_) in enumerate(t._fields_):
-            assert L.svt_hip_intra_pred_layout(what, i) == getattr(t, name).offset, (t.__name__, name)
-        assert L.svt_hip_intra_pred_layout(what, len(t._fields_)) == C.c_size_t(-1).value  # no member is left out of the mirror
-        assert C.sizeof(t) % 8 == 0
-    assert L.svt_hip_intra_pred_layout(2, -1) == C.c_size_t(-1).value
+    check_layout("svt_hip_intra_pred_layout", (abi.IntraPredDesc, abi.IntraPredJob), multiple_of_8=True)
     dt = np.dtype(abi.INTRA_PRED_JOB_DTYPE)
     assert dt.itemsize == C.sizeof(abi.IntraPredJob) and abi.INTRA_PRED_JOB_DTYPE == ic.JOB_DTYPE
     for name, *_ in abi.IntraPredJob._fields_:
         assert dt.fields[name][1] == getattr(abi.IntraPredJob, name).offset, name
     assert (abi.INTRA_PRED_OK, abi.INTRA_PRED_UNDEFINED, abi.INTRA_PRED_NO_FILTER_INTRA) == (ic.ST_OK, ic.ST_UNDEFINED, ic.NO_FI)
     assert (list(abi.TX_W), list(abi.TX_H)) == (ic.TX_W, ic.TX_H)
-
-
-def good_desc(bd=10):
-    p = 0x100000  # never dereferenced: the validation reads the descriptor alone
-    return abi.IntraPredDesc(bit_depth=bd, disable_edge_filter=0, n_jobs=4, nbr=p, nbr_stride=256, nbr_width=208, nbr_height=144, dst=p + 0x100000,
-                             dst_stride=256, dst_samples=256 * 64, jobs=p, status=p)
 
 
 def test_check_desc_accepts_a_good_descriptor():

@@ -8,6 +8,8 @@ import pytest
 
 import inter_pred_cases as ip
 import mask_cases as mc
+from abi_mirror import check_layout
+from batch_entry_cases import good_interintra_blend_desc as good_blend_desc, good_mask_search_desc as good_search_desc, good_masked_pred_desc as good_pred_desc
 from svt_av1_psyex_amd import abi, api, mask
 
 BAD_PARAM = 2
@@ -136,19 +138,9 @@ def test_the_planted_search_inputs_meet_their_conditions():
 
 
 def test_struct_layouts_match_the_library():
-    L = api.lib()
-    groups = [("svt_hip_masked_pred_layout", (abi.MaskedPredDesc, abi.MaskedPredJob, abi.MaskSearchResult)),
-              ("svt_hip_interintra_blend_layout", (abi.InterIntraDesc, abi.InterIntraJob)), ("svt_hip_mask_search_layout", (abi.MaskSearchDesc, abi.MaskSearchJob))]
-    for fn, types in groups:
-        f = getattr(L, fn)
-        f.restype = C.c_size_t
-        for what, t in enumerate(types):
-            assert f(what, -1) == C.sizeof(t), t.__name__
-            for i, (name, *_) in enumerate(t._fields_):
-                assert f(what, i) == getattr(t, name).offset, (t.__name__, name)
-            assert f(what, len(t._fields_)) == C.c_size_t(-1).value  # no member is left out of the mirror
-            assert C.sizeof(t) % 8 == 0
-        assert f(len(types), -1) == C.c_size_t(-1).value
+    check_layout("svt_hip_masked_pred_layout", (abi.MaskedPredDesc, abi.MaskedPredJob, abi.MaskSearchResult), multiple_of_8=True)
+    check_layout("svt_hip_interintra_blend_layout", (abi.InterIntraDesc, abi.InterIntraJob), multiple_of_8=True)
+    check_layout("svt_hip_mask_search_layout", (abi.MaskSearchDesc, abi.MaskSearchJob), multiple_of_8=True)
     for dtype, t, mine in ((abi.MASKED_PRED_JOB_DTYPE, abi.MaskedPredJob, mc.PRED_JOB_DTYPE), (abi.INTERINTRA_JOB_DTYPE, abi.InterIntraJob, mc.BLEND_JOB_DTYPE),
                            (abi.MASK_SEARCH_JOB_DTYPE, abi.MaskSearchJob, mc.SEARCH_JOB_DTYPE), (abi.MASK_SEARCH_RESULT_DTYPE, abi.MaskSearchResult, mc.RESULT_DTYPE)):
         dt = np.dtype(dtype)
@@ -161,24 +153,6 @@ def test_struct_layouts_match_the_library():
 
 
 P = 0x1000  # never dereferenced: the validation reads the descriptor alone
-
-
-def good_pred_desc(plane=1):
-    d = abi.MaskedPredDesc(bit_depth=10, ss_x=plane and 1, ss_y=plane and 1, n_refs=2, n_jobs=4, dst=P, dst_stride=256, plane=plane, dst_samples=256 * 64, jobs=P,
-                           status=P, mask_buf=P, mask_bytes=4096)
-    for i in range(2):
-        d.refs[i] = abi.InterPredRef(plane=P, stride=512, org_x=160, org_y=160, width=512, height=448)
-    return d
-
-
-def good_blend_desc():
-    return abi.InterIntraDesc(bit_depth=8, n_jobs=3, intra=P, inter=P, dst=P, intra_stride=64, inter_stride=72, dst_stride=72, intra_samples=4096,
-                              inter_samples=4608, dst_samples=4608, jobs=P, status=P)
-
-
-def good_search_desc():
-    return abi.MaskSearchDesc(bit_depth=10, pred0_to_pred1_mult=4, n_jobs=3, src=P, pred0=P, pred1=P, intra=P, src_stride=64, pred0_stride=64, pred1_stride=64,
-                              intra_stride=64, src_samples=4096, pred0_samples=4096, pred1_samples=4096, intra_samples=4096, jobs=P, results=P, status=P)
 
 
 def test_check_desc_accepts_good_descriptors():

@@ -8,6 +8,8 @@ import pytest
 
 import inter_pred_cases as ip
 import obmc_cases as oc
+from abi_mirror import check_layout
+from batch_entry_cases import good_obmc_blend_desc as good_blend_desc, good_obmc_neighbour_desc as good_neighbour_desc, good_obmc_target_desc as good_target_desc
 from svt_av1_psyex_amd import abi, api, obmc
 
 BAD_PARAM = 2
@@ -93,16 +95,9 @@ def test_the_cases_are_what_the_issue_lists():
 
 
 def test_struct_layouts_match_the_library():
-    f = api.lib().svt_hip_obmc_layout
-    f.restype = C.c_size_t
-    types = (abi.ObmcNeighbourDesc, abi.ObmcBlendDesc, abi.ObmcTargetDesc, abi.ObmcBlock, abi.ObmcNeighbour, abi.ObmcJob)
-    for what, t in enumerate(types):
-        assert f(what, -1) == C.sizeof(t), t.__name__
-        for i, (name, *_) in enumerate(t._fields_):
-            assert f(what, i) == getattr(t, name).offset, (t.__name__, name)
-        assert f(what, len(t._fields_)) == C.c_size_t(-1).value  # no member is left out of the mirror
-        assert C.sizeof(t) % 8 == 0
-    assert f(9, -1) == C.c_size_t(-1).value  # 6 .. 8 are the search's (tests/test_obmc_search.py)
+    structs = (abi.ObmcNeighbourDesc, abi.ObmcBlendDesc, abi.ObmcTargetDesc, abi.ObmcBlock, abi.ObmcNeighbour, abi.ObmcJob, abi.ObmcSearchDesc, abi.ObmcSearchJob,
+               abi.ObmcSearchResult)
+    check_layout("svt_hip_obmc_layout", structs, only=range(6), multiple_of_8=True)  # 6 .. 8 are the search's (tests/test_obmc_search.py)
     for dtype, t, mine in ((abi.OBMC_BLOCK_DTYPE, abi.ObmcBlock, oc.BLOCK_DTYPE), (abi.OBMC_NEIGHBOUR_DTYPE, abi.ObmcNeighbour, oc.NB_DTYPE),
                            (abi.OBMC_JOB_DTYPE, abi.ObmcJob, oc.JOB_DTYPE)):
         dt = np.dtype(dtype)
@@ -113,24 +108,6 @@ def test_struct_layouts_match_the_library():
 
 
 P = 0x1000  # never dereferenced: the validation reads the descriptor alone
-
-
-def good_neighbour_desc(plane=1):
-    d = abi.ObmcNeighbourDesc(bit_depth=10, ss_x=plane and 1, ss_y=plane and 1, plane=plane, n_refs=2, n_jobs=4, n_blocks=4, blocks=P, jobs=P, above=P, left=P,
-                              strip_samples=4096, status=P)
-    for i in range(2):
-        d.refs[i] = abi.InterPredRef(plane=P, stride=256, org_x=80, org_y=80, width=256, height=224)
-    return d
-
-
-def good_blend_desc(plane=2):
-    return abi.ObmcBlendDesc(bit_depth=8, ss_x=plane and 1, ss_y=plane and 1, plane=plane, n_jobs=3, n_blocks=3, dst_stride=96, blocks=P, jobs=P, above=P, left=P,
-                             strip_samples=4096, dst=P, dst_samples=96 * 64, status=P)
-
-
-def good_target_desc():
-    return abi.ObmcTargetDesc(strip_bit_depth=10, n_jobs=3, n_blocks=3, src_stride=192, blocks=P, jobs=P, above=P, left=P, strip_samples=4096, src=P,
-                              src_samples=192 * 128, wsrc=P, mask=P, out_values=4096, status=P)
 
 
 def test_check_desc_accepts_good_descriptors():

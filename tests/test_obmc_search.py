@@ -8,6 +8,8 @@ import pytest
 
 import obmc_cases as oc
 import obmc_search_cases as sc
+from abi_mirror import check_layout
+from batch_entry_cases import good_obmc_search_desc as good_desc
 from svt_av1_psyex_amd import abi, api, obmc
 
 BAD_PARAM = 2
@@ -75,31 +77,15 @@ def test_every_search_read_lies_inside_the_plane_and_the_guard_is_tight():
 
 
 def test_struct_layouts_match_the_library():
-    f = api.lib().svt_hip_obmc_layout
-    f.restype = C.c_size_t
-    for what, t in ((6, abi.ObmcSearchDesc), (7, abi.ObmcSearchJob), (8, abi.ObmcSearchResult)):
-        assert f(what, -1) == C.sizeof(t), t.__name__
-        for i, (name, *_) in enumerate(t._fields_):
-            assert f(what, i) == getattr(t, name).offset, (t.__name__, name)
-        assert f(what, len(t._fields_)) == C.c_size_t(-1).value and C.sizeof(t) % 8 == 0
-    assert f(9, -1) == C.c_size_t(-1).value
+    structs = (abi.ObmcNeighbourDesc, abi.ObmcBlendDesc, abi.ObmcTargetDesc, abi.ObmcBlock, abi.ObmcNeighbour, abi.ObmcJob, abi.ObmcSearchDesc, abi.ObmcSearchJob,
+               abi.ObmcSearchResult)
+    check_layout("svt_hip_obmc_layout", structs, only=(6, 7, 8), multiple_of_8=True)  # 0 .. 5: tests/test_obmc.py
     for dtype, t, mine in ((abi.OBMC_SEARCH_JOB_DTYPE, abi.ObmcSearchJob, sc.JOB_DTYPE), (abi.OBMC_SEARCH_RESULT_DTYPE, abi.ObmcSearchResult, sc.RESULT_DTYPE)):
         dt = np.dtype(dtype)
         assert dt.itemsize == C.sizeof(t) and np.dtype(mine) == dt
         for name, *_ in t._fields_:
             off = getattr(t, name).offset
             assert dt.fields[name][1] == off, name
-
-
-P = 0x1000  # never dereferenced: the validation reads the descriptor alone
-
-
-def good_desc(light=0):
-    d = abi.ObmcSearchDesc(ref_bit_depth=8, refine_level=3, fpel_search_diag=1, approx_inter_rate=light, allow_hp=1, n_jobs=4, fpel_search_range=16, sadpb=40,
-                           error_per_bit=60, ref_stride=384, ref=P, ref_samples=384 * 320, wsrc=P, mask=P, target_values=4096, jobs=P, best_mv=P, results=P, status=P)
-    if not light:
-        d.mvjcost, d.mvcost[0], d.mvcost[1] = P, P, P
-    return d
 
 
 def test_check_desc_accepts_good_descriptors():

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 import palette_cases as pc
+from abi_mirror import check_layout
+from batch_entry_cases import good_palette_desc as valid_desc, good_palette_pred_desc as valid_pred_desc
 from svt_av1_psyex_amd import abi, api, palette
 
 
@@ -67,13 +69,7 @@ STRUCTS = [abi.PaletteDesc, abi.PaletteJob, abi.PaletteCand, abi.PaletteResult, 
 
 @pytest.mark.parametrize("what,struct", enumerate(STRUCTS))
 def test_struct_layouts_equal_the_librarys(what, struct):
-    L = api.lib()
-    L.svt_hip_palette_layout.restype = C.c_size_t
-    assert L.svt_hip_palette_layout(what, -1) == C.sizeof(struct)
-    for i, f in enumerate(struct._fields_):
-        assert L.svt_hip_palette_layout(what, i) == getattr(struct, f[0]).offset, f[0]
-    assert L.svt_hip_palette_layout(what, len(struct._fields_)) == C.c_size_t(-1).value
-    assert L.svt_hip_palette_layout(len(STRUCTS), -1) == C.c_size_t(-1).value and L.svt_hip_palette_layout(-1, -1) == C.c_size_t(-1).value
+    check_layout("svt_hip_palette_layout", STRUCTS, only=(what,))
 
 
 def test_record_dtypes_equal_the_structs():
@@ -86,17 +82,6 @@ def test_record_dtypes_equal_the_structs():
     assert np.dtype(pc.JOB_DTYPE) == np.dtype(abi.PALETTE_JOB_DTYPE) and np.dtype(pc.RESULT_DTYPE) == np.dtype(abi.PALETTE_RESULT_DTYPE)
     assert np.dtype(pc.PRED_JOB_DTYPE) == np.dtype(abi.PALETTE_PRED_JOB_DTYPE) and np.dtype(pc.CAND_DTYPE) == np.dtype(abi.PALETTE_CAND_DTYPE)
     assert (abi.PALETTE_MAX_CANDS, abi.PALETTE_MAX_SIZE, abi.PALETTE_MAX_CACHE) == (pc.MAX_CANDS, pc.MAX_SIZE, pc.MAX_CACHE)
-
-
-def valid_desc():
-    return abi.PaletteDesc(bit_depth=8, cost_bit_depth=10, dominant_color_step=2, reduce_palette_cost_precision=1, n_jobs=1, src=64, src_stride=256,
-                           src_samples=4096, palette_ycolor_fac_bitss=64, palette_ysize_fac_bits=64, palette_ymode_fac_bits=64, jobs=64, results=64, status=64,
-                           color_maps=64, map_bytes=4096)
-
-
-def valid_pred_desc():
-    return abi.PalettePredDesc(bit_depth=10, n_jobs=1, n_search_jobs=1, src_stride=256, src=64, src_samples=4096, dst=64, dst_stride=64, dst_samples=4096,
-                               search_jobs=64, search_results=64, search_status=64, jobs=64, status=64, color_map=64, map_bytes=4096)
 
 
 def test_check_desc_accepts_and_refuses():

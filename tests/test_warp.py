@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 import warp_cases as wc
+from abi_mirror import check_layout
+from batch_entry_cases import good_warp_model_desc, good_warp_pred_desc as good_desc, good_wm_refine_desc as good_refine_desc
 from svt_av1_psyex_amd import abi, api, warp
 
 BAD_PARAM = 2
@@ -125,15 +127,7 @@ MIRRORS = (abi.WarpPredDesc, abi.WarpPredJob, abi.WarpRef, abi.WarpModel, abi.Wa
 
 
 def test_struct_layouts_match_the_library():
-    L = api.lib()
-    L.svt_hip_warp_layout.restype = C.c_size_t
-    for what, t in enumerate(MIRRORS):
-        assert L.svt_hip_warp_layout(what, -1) == C.sizeof(t), t.__name__
-        for i, (name, *_) in enumerate(t._fields_):
-            assert L.svt_hip_warp_layout(what, i) == getattr(t, name).offset, (t.__name__, name)
-        assert L.svt_hip_warp_layout(what, len(t._fields_)) == C.c_size_t(-1).value  # no member is left out of the mirror
-        assert C.sizeof(t) % 8 == 0
-    assert L.svt_hip_warp_layout(len(MIRRORS), -1) == C.c_size_t(-1).value
+    check_layout("svt_hip_warp_layout", MIRRORS, multiple_of_8=True)
     for dtype, mirror, own in ((abi.WARP_MODEL_DTYPE, abi.WarpModel, wc.MODEL_DTYPE), (abi.WARP_PRED_JOB_DTYPE, abi.WarpPredJob, wc.PRED_JOB_DTYPE),
                                (abi.WARP_MODEL_JOB_DTYPE, abi.WarpModelJob, wc.MODEL_JOB_DTYPE), (abi.WM_REFINE_JOB_DTYPE, abi.WmRefineJob, wc.REFINE_JOB_DTYPE)):
         dt = np.dtype(dtype)
@@ -146,14 +140,6 @@ def test_struct_layouts_match_the_library():
 
 
 # ---- svt_hip_warp_check_desc ----
-P = 0x100000  # never dereferenced: the validations read the descriptors alone
-
-
-def good_desc(bd=10, n_refs=2):
-    refs = [abi.WarpRef(plane=P + 0x100000 * r, stride=160, org_x=16, org_y=8, width=128, height=96, rows=112) for r in range(n_refs)]
-    return warp.pred_desc(bd, 0, 0, refs, P * 64, 128, 128 * 128, P * 65, 5, P * 66, P * 67, 4)
-
-
 def spoil(d, bad):
     if bad.startswith("no_"):
         setattr(d, bad[3:], None)
@@ -215,7 +201,7 @@ def test_pred_batch_rejects_a_bad_descriptor_without_a_gpu(bad):
 def test_model_batch_rejects_a_bad_descriptor_without_a_gpu(bad):
     L = api.lib()
     ctx = C.create_string_buffer(8192)
-    d = abi.WarpModelDesc(n_jobs=3, n_mvs=2, jobs=P, mv_array=P, models=P, status=P)
+    d = good_warp_model_desc()
     if bad == "null_ctx":
         assert L.svt_hip_warp_model_batch(None, C.byref(d)) == BAD_PARAM
     elif bad == "null_desc":
@@ -226,13 +212,6 @@ def test_model_batch_rejects_a_bad_descriptor_without_a_gpu(bad):
 
 
 # ---- svt_hip_wm_refine_check_desc ----
-def good_refine_desc(light=0):
-    refs = [abi.WarpRef(plane=P, stride=160, org_x=16, org_y=8, width=128, height=96, rows=112)]
-    settings = dict(iterations=8, refine_diag=1, mv_prec_shift=1, shut_approx=0, lower_band_th=0, upper_band_th=65535, approx_inter_rate=light, error_per_bit=90)
-    outs = dict(best_mv=P * 3, best_cost=P * 4, n_checked=P * 5, status=P * 6)
-    return warp.refine_desc(4, settings, refs, P * 2, 128, 128 * 96, P * 7, outs, P * 8, 4, None if light else (P * 9, P * 10, P * 11))
-
-
 def test_refine_check_desc_accepts_a_good_descriptor():
     warp.check_refine_desc(good_refine_desc())
     warp.check_refine_desc(good_refine_desc(light=1))  # no cost table is needed
