@@ -212,6 +212,24 @@ int   svt_hip_context_set_me_counting(SvtHipContext *ctx, int on);
 /* out[0] = searches the per-block kernel took from the pre-pass, out[1] = searches it made itself although the pre-pass was
  * on (edge blocks, configurations the pre-pass does not cover), since the last call; waits for the context's streams. */
 int   svt_hip_me_dense_counters(SvtHipContext *ctx, unsigned long long out[2]);
+/* The pre-pass walks the reference rows of a unit (one block row, one segment of search rows, 64 lanes) either with its static walk -- full-height
+ * blocks, every search row, a segment of 16, 24, 32 ... rows, every live lane on a full octet of positions -- or with the generic one.  The switch
+ * (on by default; SVT_HIP_ME_DENSE_FAST=0 turns it off at context creation) sends every unit through the generic walk; results are identical either
+ * way.  With counting on, svt_hip_me_dense_path_counters returns out[2 p] = units that took path p and out[2 p + 1] = the (source row, search row)
+ * pairs their waves evaluated, since the last call: p = 0 the static walk; the generic walk because of 1 a partial last block row, 2
+ * prehme_skip_search_line, 3 fewer than 16 search rows, 4 a number of search rows that is no multiple of 8, 5 a live lane on a partial octet (the
+ * octet iterations of such a unit that were full count as pairs of path 0), 6 the switch.  out[2 SVT_HIP_ME_DENSE_PATHS + m - 2] = the units of
+ * path 0 with 8 m search rows, m = 2 .. 7; m = 8: with 64 and more. */
+#define SVT_HIP_ME_DENSE_PATHS 7
+int   svt_hip_context_set_me_dense_fast(SvtHipContext *ctx, int on);
+/* The pre-pass cuts its searches into units by the launch's size: segments of 48 search rows (areas above 64 rows) for a launch that fills the
+ * chip several times over, of 32 and of 16 rows for smaller ones.  plan = 1, 2, 3 forces the first, second, third of these whatever the size
+ * (tests: long units on a small picture); 0 (default) = by size.  Results are identical either way. */
+int   svt_hip_context_set_me_dense_plan(SvtHipContext *ctx, int plan);
+int   svt_hip_me_dense_path_counters(SvtHipContext *ctx, unsigned long long out[2 * SVT_HIP_ME_DENSE_PATHS + 7]);
+/* Diagnostics: the pre-pass's slot buffer of the context's most recent launch that had one: per (block, searched reference, kind) 16 bytes -- u64
+ * sad << 32 | y << 16 | x, u32 origin, u32 size.  *bytes receives its size; it is copied to `out` when `capacity` holds it.  Waits for the launch. */
+int   svt_hip_me_dense_slots(SvtHipContext *ctx, void *out, size_t capacity, size_t *bytes);
 
 /* ---- preset derivation (host only) ---- */
 /* Restates svt_aom_sig_deriv_me + svt_aom_sig_deriv_multi_processes' HME flags (enc_mode_config.c:138-833,1632-1642). */

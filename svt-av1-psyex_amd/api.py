@@ -168,6 +168,36 @@ class Context:
         self.check(lib().svt_hip_me_dense_counters(self._h, v), "svt_hip_me_dense_counters")
         return int(v[0]), int(v[1])
 
+    ME_DENSE_PATHS = ("fast", "partial_row", "skip_line", "short", "odd", "octet", "off")
+
+    def set_me_dense_fast(self, on):
+        """the pre-pass's static walk for units that allow it (svt_hip_context_set_me_dense_fast); on by default, results are identical either way"""
+        self.check(lib().svt_hip_context_set_me_dense_fast(self._h, 1 if on else 0), "svt_hip_context_set_me_dense_fast")
+
+    def set_me_dense_plan(self, plan):
+        """how the pre-pass cuts its searches into units (svt_hip_context_set_me_dense_plan): 0 by launch size (default), 1 long .. 3 fine units"""
+        self.check(lib().svt_hip_context_set_me_dense_plan(self._h, int(plan)), "svt_hip_context_set_me_dense_plan")
+
+    def me_dense_path_counters(self):
+        """{path: (units, (source row, search row) pairs of their waves)} of the pre-pass since the last call (svt_hip_me_dense_path_counters; needs
+        set_me_counting).  fast: the static walk; the others: the generic walk and why the unit took it; fast_rows: {search rows: static units}, 64 = 64 and more"""
+        n = len(self.ME_DENSE_PATHS)
+        v = (C.c_ulonglong * (2 * n + 7))()
+        self.check(lib().svt_hip_me_dense_path_counters(self._h, v), "svt_hip_me_dense_path_counters")
+        out = {name: (int(v[2 * i]), int(v[2 * i + 1])) for i, name in enumerate(self.ME_DENSE_PATHS)}
+        out["fast_rows"] = {8 * (m + 2): int(v[2 * n + m]) for m in range(7)}
+        return out
+
+    def me_dense_slots(self):
+        """the pre-pass's slot buffer of the most recent launch that had one (svt_hip_me_dense_slots): a structured array with key, org, size"""
+        L = lib()
+        n = C.c_size_t()
+        L.svt_hip_me_dense_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        self.check(L.svt_hip_me_dense_slots(self._h, None, 0, C.byref(n)), "svt_hip_me_dense_slots")
+        out = np.zeros(n.value // 16, dtype=[("key", "<u8"), ("org", "<u4"), ("size", "<u4")])
+        self.check(L.svt_hip_me_dense_slots(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)), "svt_hip_me_dense_slots")
+        return out
+
     # --- pictures -----------------------------------------------------------------------------------
     def upload(self, host_pyramid, device_pyramid=True):
         """HostPyramid -> HBM-resident pyramid.  device_pyramid=True builds 1/4 and 1/16 on the GPU."""

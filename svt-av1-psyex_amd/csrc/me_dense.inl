@@ -17,7 +17,12 @@
 //     (lanes of one block meet there), followed by one global atomic min per block: key = sad << 32 | y << 16 | x, the reference's "first
 //     minimum in raster order" (C_DEFAULT/compute_sad_c.c:58-101).
 //   * work = units: (entry = picture x searched reference x kind, b64 row, segment of search rows, chunk of 64 lanes); tall strips are
-//     cut into segments of about 48 search rows, wide ones give a lane several octets, so that units cost about the same.
+//     cut into segments of 48 search rows and a shorter last one, wide ones give a lane several octets, so that units cost about the same.
+//   * two walks.  The generic one tests every (reference row, source row) pair against the unit's bounds (wave-uniform scalar tests: 1.3
+//     scalar instructions per packed SAD).  A unit of a full-height block that searches every row of a segment of n = 8 m >= 16 rows, all live lanes
+//     on full octets, takes the STATIC walk instead: ramp-up (rows 0 .. 15, source rows 0 .. Rp / 2), a steady loop of 16 rows per trip
+//     (all 8 source rows; half a trip more when n = 8 mod 16), ramp-down (rows n .. n + 13) -- the valid pairs and the ring slots of each piece
+//     are compile-time numbers, the ramp-down's given n mod 16: the walk exists twice, for n = 0 and n = 8 mod 16.
 //
 // Exactly the searches svt_sad_loop_kernel would make: geometry from prehme_geometry / hme_level_geometry (shared with the per-block
 // kernel), blocks that are not a full 64 samples wide and searches with all 16 rows (hme_search_method 1) are left to the per-block kernel.
@@ -36,8 +41,33 @@ __device__ __forceinline__ u64 dense_group(const uint32_t (&wv)[6], const uint32
     return acc;
 }
 
+// One reference row of the static walk: source rows klo .. khi meet it (source row k at search row dd7 + 14 - 2 k); row 7 completes search row
+// dd7, which is folded into the lane's best.  `j` = the reference row's index mod 16.  With j and klo / khi compile-time numbers (the walk's
+// pieces are fully unrolled) every ring slot is a register number and the body holds no test; all 8 positions of the octet compete.
+__device__ __forceinline__ void dense_row(const uint32_t (&wv)[6], const uint32_t (&s)[8][4], u64 (&acc0)[16], u64 (&acc1)[16], int j, int klo, int khi, int dd7, uint32_t &best,
+                                          int &bestd) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if (k < klo || k > khi) continue;
+        const int sl = (j - 2 * k) & 15; // == search row mod 16
+        acc0[sl] = dense_group(wv, s[k], acc0[sl], 0);
+        acc1[sl] = dense_group(wv, s[k], acc1[sl], 1);
+        if (k == 7) {
+            const uint32_t a = (uint32_t)acc0[sl], b = (uint32_t)(acc0[sl] >> 32), cc = (uint32_t)acc1[sl], e2 = (uint32_t)(acc1[sl] >> 32);
+            const uint32_t m = umin(umin(umin(a << 16, (a & 0xFFFF0000u) | 1u), (b << 16) | 2u), umin(umin(umin((b & 0xFFFF0000u) | 3u, (cc << 16) | 4u), (cc & 0xFFFF0000u) | 5u),
+                                                                                                      umin((e2 << 16) | 6u, (e2 & 0xFFFF0000u) | 7u)));
+            if (m < (best & 0xFFFF0000u)) { best = m; bestd = dd7; } // strict `<` on the SAD: the first search row wins ties
+            acc0[sl] = 0; acc1[sl] = 0;
+        }
+    }
+}
+
 } // namespace
 
+// Behind each reference row of the static walk: the scheduler keeps a row's packed SADs and the next row's fetch where they were written
+#ifndef SVT_HIP_ME_DENSE_ROW_FENCE
+#define SVT_HIP_ME_DENSE_ROW_FENCE __builtin_amdgcn_sched_barrier(0)
+#endif
 #ifndef SVT_HIP_ME_DENSE_WAVES
 #define SVT_HIP_ME_DENSE_WAVES 3
 #endif
@@ -97,6 +127,10 @@ svt_hip_me_dense_kernel(const MeBatchHeader *__restrict__ ghdr, const MeKernelPa
     if (y_lo >= y_hi) return; // uniform
     const int n = y_hi - y_lo;
     const bool skip_even = kind < 2 && c.prehme_skip_search_line; // push_req: skip && bw == 16 && rows <= 16 -- always true for the blocks taken here
+    // the unit's walk (uniform): the static one serves full-height blocks, every search row, n = 8 m >= 16; the generic one the rest
+    const int why_generic = !hdr.dense_fast ? kMeDensePathOff : kfirst ? kMeDensePathPartialRow : skip_even ? kMeDensePathSkipLine : n < 16 ? kMeDensePathShort : (n & 7) ? kMeDensePathOdd : 0;
+    const bool unit_fast = why_generic == 0;
+    int n_fast_iter = 0; // octet iterations of the unit that took the static walk
 
     const size_t slot_idx = (((size_t)hdr.job_base[e.pic] + (size_t)by * (size_t)w64 + (size_t)bx) * hdr.n_slot + e.k) * SVT_HIP_ME_DENSE_KINDS + (size_t)kind;
     if (active && oslot == 0 && seg == 0) { // the geometry the key is valid for; doubles as the slot's "filled" mark
@@ -124,9 +158,6 @@ svt_hip_me_dense_kernel(const MeBatchHeader *__restrict__ ghdr, const MeKernelPa
     const int Rp_begin = 2 * kfirst, Rp_end = n - 1 + 14;
 
     u64 lane_best = ~0ull;
-    u64 acc0[16], acc1[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) { acc0[i] = 0; acc1[i] = 0; }
 
     const int n_oct_iter = (int)(((uint32_t)e.noct + (uint32_t)nos - 1u) / (uint32_t)nos); // uniform
     typedef uint32_t V2U __attribute__((ext_vector_type(2), aligned(1)));
@@ -148,6 +179,9 @@ svt_hip_me_dense_kernel(const MeBatchHeader *__restrict__ ghdr, const MeKernelPa
         const bool all_full = __all(nvalid == 8);
         const uint32_t loff = octet_off(oi);
         uint32_t best = 0xFFFFFFFFu; // sad << 16 | position in the octet
+        u64 acc0[16], acc1[16]; // the ring (a walk leaves it zero; set here, it is not carried from one walk into the other's registers)
+#pragma unroll
+        for (int i = 0; i < 16; i++) { acc0[i] = 0; acc1[i] = 0; }
         int      bestd = 0;
         V4U  bufa[2];
         uint2 bufb[2];
@@ -163,6 +197,51 @@ svt_hip_me_dense_kernel(const MeBatchHeader *__restrict__ ghdr, const MeKernelPa
             nfa = *reinterpret_cast<GV4U *>(a);
             nfb = *reinterpret_cast<GV2U *>(a + 16);
         }
+        const bool fast = unit_fast && __all(nvalid == 8 || nvalid == 0); // uniform
+        // The static walk of a full-height block over n = 8 m >= 16 search rows: which source rows meet reference row Rp is known at compile
+        // time in each of its pieces, and so is every ring slot (given n mod 16), so no row of it is guarded.  Lanes that are not live walk
+        // along unmasked; what they find is dropped behind the walk.  HALF: n = 8 mod 16 (two copies of the walk: a ring that is tested
+        // half-way down would be carried through the test in twice its registers).
+        auto static_walk = [&](bool HALF) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < 16; j++) { // ramp-up: reference rows 0 .. 15 meet source rows 0 .. min(7, Rp / 2)
+                fetch((j + 1) & 1, j + 1);
+                const uint32_t wv[6] = {bufa[j & 1].x, bufa[j & 1].y, bufa[j & 1].z, bufa[j & 1].w, bufb[j & 1].x, bufb[j & 1].y};
+                dense_row(wv, s, acc0, acc1, j, 0, j < 14 ? j >> 1 : 7, j - 14, best, bestd);
+                SVT_HIP_ME_DENSE_ROW_FENCE;
+            }
+            int R0 = 16;
+            for (; R0 + 16 <= n; R0 += 16) { // steady: every reference row meets all 8 source rows
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    fetch((j + 1) & 1, R0 + j + 1);
+                    const uint32_t wv[6] = {bufa[j & 1].x, bufa[j & 1].y, bufa[j & 1].z, bufa[j & 1].w, bufb[j & 1].x, bufb[j & 1].y};
+                    dense_row(wv, s, acc0, acc1, j, 0, 7, R0 + j - 14, best, bestd);
+                    SVT_HIP_ME_DENSE_ROW_FENCE;
+                }
+            }
+            if (HALF) { // half a steady trip
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    fetch((j + 1) & 1, R0 + j + 1);
+                    const uint32_t wv[6] = {bufa[j & 1].x, bufa[j & 1].y, bufa[j & 1].z, bufa[j & 1].w, bufb[j & 1].x, bufb[j & 1].y};
+                    dense_row(wv, s, acc0, acc1, j, 0, 7, R0 + j - 14, best, bestd);
+                    SVT_HIP_ME_DENSE_ROW_FENCE;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 14; j++) { // ramp-down: reference rows n .. n + 13 meet source rows (Rp - n) / 2 + 1 .. 7; ring slots from n mod 16 on
+                if (j < 13) fetch((j + 1) & 1, n + j + 1);
+                const uint32_t wv[6] = {bufa[j & 1].x, bufa[j & 1].y, bufa[j & 1].z, bufa[j & 1].w, bufb[j & 1].x, bufb[j & 1].y};
+                dense_row(wv, s, acc0, acc1, (HALF ? 8 : 0) + j, (j >> 1) + 1, 7, n + j - 14, best, bestd);
+                SVT_HIP_ME_DENSE_ROW_FENCE;
+            }
+            if (!live) best = 0xFFFFFFFFu;
+            n_fast_iter++;
+        };
+        if (fast && !(n & 8)) static_walk(false);
+        else if (fast) static_walk(true);
+        else
         for (int it = 0; it * 16 <= Rp_end; it++) {
 #pragma unroll
             for (int j = 0; j < 16; j++) {
@@ -198,6 +277,18 @@ svt_hip_me_dense_kernel(const MeBatchHeader *__restrict__ ghdr, const MeKernelPa
             const u64 key = ((u64)(best >> 16) << 32) | ((u64)(uint32_t)(y_lo + bestd) << 16) | (u64)(uint32_t)(8 * o + (int)(best & 7u));
             lane_best = key < lane_best ? key : lane_best;
         }
+    }
+
+    if (hdr.count_dense) { // svt_hip_me_dense_path_counters (uniform): one atomic instruction per wave -- lane 2 p adds the unit to path p, lane 2 p + 1 its pairs
+        const int gen_path  = unit_fast ? kMeDensePathOctet : why_generic, n_gen_iter = n_oct_iter - n_fast_iter;
+        const int unit_path = n_gen_iter ? gen_path : kMeDensePathFast;
+        const unsigned long long pairs = (unsigned long long)((skip_even ? (n + (y_lo & 1)) >> 1 : n) * nrows); // (source row, search row) pairs of one octet iteration
+        unsigned long long v = 0;
+        if (lane == 2 * unit_path) v = 1;
+        else if (lane == 2 * kMeDensePathFast + 1) v = pairs * (unsigned long long)n_fast_iter;
+        else if (lane == 2 * gen_path + 1) v = pairs * (unsigned long long)n_gen_iter;
+        else if (lane == 2 * kMeDensePaths + imin(n >> 3, 8) - 2) v = unit_path == kMeDensePathFast; // static units by n / 8: 2 .. 7, 8 and more
+        if (v) atomicAdd(reinterpret_cast<unsigned long long *>(hdr.queue_head + SVT_HIP_ME_DENSE_PATH_WORD) + lane, v);
     }
 
     // ---- the lanes of a block meet in LDS; one global atomic min per block and unit ----
@@ -248,8 +339,10 @@ uint32_t dense_plan_with(const MeKernelParams *params, const uint32_t *n_jobs, u
                     memset(&e, 0, sizeof(e));
                     e.pic = (uint16_t)pi; e.li = (uint8_t)li; e.ri = (uint8_t)ri; e.k = (uint8_t)((li ? r0n : 0) + ri); e.kind = (uint8_t)kind;
                     e.noct = (uint16_t)((sa_w + 7) >> 3);
+                    // an area taller than seg_max: segments of seg_rows search rows (a multiple of 8: the static walk takes them) and one shorter
+                    // last segment for the remainder -- the kernel cuts [seg * seg_len, min(sa_h, (seg + 1) * seg_len))
                     e.n_seg = (uint16_t)(sa_h <= seg_max ? 1 : (sa_h + seg_rows - 1) / seg_rows);
-                    e.seg_len = (uint16_t)((sa_h + e.n_seg - 1) / e.n_seg);
+                    e.seg_len = (uint16_t)(e.n_seg == 1 ? sa_h : seg_rows);
                     const uint32_t groups = (uint32_t)e.noct * e.seg_len * 8u; // of one block
                     uint32_t nos = (groups + target_groups - 1) / target_groups;
                     nos = nos < 1 ? 1 : (nos > e.noct ? e.noct : nos);
@@ -281,10 +374,13 @@ uint32_t dense_plan_with(const MeKernelParams *params, const uint32_t *n_jobs, u
 
 // A launch of many blocks gets long units (384 groups per lane: few waves' worth of set-up per |a-b|); a launch of few blocks -- a rank's band
 // at 8 GPUs, a single small picture -- would leave most of the chip's resident waves without a unit that way, so it is cut finer.
-uint32_t dense_plan(const MeKernelParams *params, const uint32_t *n_jobs, uint32_t n_pictures, MeDenseEntry *ent, uint32_t *units, uint32_t resident_waves) {
-    uint32_t n = dense_plan_with(params, n_jobs, n_pictures, ent, units, kDenseTargetGroups, 64, 48);
-    if (*units && *units < 3u * resident_waves) n = dense_plan_with(params, n_jobs, n_pictures, ent, units, kDenseTargetGroups / 2, 32, 24);
-    if (*units && *units < 3u * resident_waves) n = dense_plan_with(params, n_jobs, n_pictures, ent, units, kDenseTargetGroups / 4, 16, 16);
+// `forced`: 1 .. 3 = the long, the middle, the fine plan whatever the launch's size (svt_hip_context_set_me_dense_plan); 0 = by size.
+uint32_t dense_plan(const MeKernelParams *params, const uint32_t *n_jobs, uint32_t n_pictures, MeDenseEntry *ent, uint32_t *units, uint32_t resident_waves, int forced) {
+    uint32_t n = 0;
+    *units = 0;
+    if (forced <= 1) n = dense_plan_with(params, n_jobs, n_pictures, ent, units, kDenseTargetGroups, 64, 48);
+    if (forced == 2 || (!forced && *units && *units < 3u * resident_waves)) n = dense_plan_with(params, n_jobs, n_pictures, ent, units, kDenseTargetGroups / 2, 32, 32);
+    if (forced == 3 || (!forced && *units && *units < 3u * resident_waves)) n = dense_plan_with(params, n_jobs, n_pictures, ent, units, kDenseTargetGroups / 4, 16, 16);
     return n;
 }
 

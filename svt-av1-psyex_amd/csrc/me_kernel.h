@@ -114,6 +114,12 @@ struct MeKernelParams {
 // Dense pre-pass (me_dense.inl): one slot per (global job index, searched (list, reference) pair, kind)
 #define SVT_HIP_ME_DENSE_KINDS 6   /* two pre-HME strips + 2 x 2 level-0 regions */
 #define SVT_HIP_ME_COUNTER_WORD 112 /* u32 index into a lane's queue_head block: two u64 counters (dense slots taken / not found) */
+/* The walk a unit of the pre-pass took (me_dense.inl): the static one, or the generic one and why.  Per path two u64 counters (units, (source
+ * row, search row) pairs per wave), then seven more (static units of 16, 24 .. 56, 64 and more search rows), from u32 index
+ * SVT_HIP_ME_DENSE_PATH_WORD of the lane's queue_head block (svt_hip_me_dense_path_counters) */
+enum { kMeDensePathFast, kMeDensePathPartialRow, kMeDensePathSkipLine, kMeDensePathShort, kMeDensePathOdd, kMeDensePathOctet, kMeDensePathOff, kMeDensePaths };
+#define SVT_HIP_ME_DENSE_PATH_WORD 116
+#define SVT_HIP_ME_DENSE_PATH_COUNTERS (2 * kMeDensePaths + 7)
 struct MeDenseSlot {
     unsigned long long key;  // sad << 32 | y << 16 | x (search indices), ~0 when no position was evaluated / not computed
     uint32_t           org;  // (uint16)ox | (uint16)oy << 16: displacement of search index (0, 0)
@@ -135,7 +141,7 @@ struct MeDenseEntry {
 #define SVT_HIP_ME_STAGE_BYTES 2560
 #define SVT_HIP_ME_JOB_DEFERRED 1u /* a search the pre-pass did not make: the whole-pipeline kernel makes the block (list 0) */
 /* u32 indices into a lane's queue_head block (2 KiB): [0, 8) the one-kernel form's band-queue counters, [16, 112) the profiling build's phase
- * sums, [112, 116) the dense counters, [200, 206) the three lists' cursors / counts */
+ * sums, [112, 116) the dense counters, [116, 158) the pre-pass's path counters, [200, 206) the three lists' cursors / counts */
 #define SVT_HIP_ME_LIST_CURSOR(l) (200 + 2 * (l))
 #define SVT_HIP_ME_LIST_COUNT(l) (201 + 2 * (l))
 #define SVT_HIP_ME_QUEUE_BLOCK_BYTES 2048
@@ -161,6 +167,7 @@ struct MeBatchHeader {
     MeDenseSlot *dense;   // results of the dense pre-pass, [job_base[n_pictures]][n_slot][SVT_HIP_ME_DENSE_KINDS]; null: no pre-pass
     uint32_t  n_dense_entries, n_dense_units;
     uint32_t  count_dense; // the waves add their taken / own-search counts to the lane's counters (svt_hip_context_set_me_counting; two atomics per wave, serialised at the memory side: ~0.1 ms of a launch of 4096 waves)
+    uint32_t  dense_fast;  // the pre-pass takes its static walk where a unit allows it (svt_hip_context_set_me_dense_fast)
     // staged launches (null otherwise): per job SVT_HIP_ME_STAGE_BYTES of travelling state, a flag word; three job lists (0: deferred to the
     // whole-pipeline kernel, 1 / 2: level-1 / level-2 searches in the staged form)
     uint8_t   *stage;
@@ -169,6 +176,7 @@ struct MeBatchHeader {
 };
 #ifdef __cplusplus
 static_assert(sizeof(MeBatchHeader) <= SVT_HIP_ME_HEADER_BYTES, "header size");
+static_assert(SVT_HIP_ME_DENSE_PATH_WORD % 2 == 0 && SVT_HIP_ME_DENSE_PATH_WORD + 2 * SVT_HIP_ME_DENSE_PATH_COUNTERS <= SVT_HIP_ME_LIST_CURSOR(0), "path counters");
 #endif
 // A lane's parameter block (device copy and the pinned ring): header, SVT_HIP_ME_MAX_PICTURES parameter blocks, the dense entry table
 #define SVT_HIP_ME_ENTRIES_OFFSET (SVT_HIP_ME_HEADER_BYTES + sizeof(MeKernelParams) * SVT_HIP_ME_MAX_PICTURES)

@@ -2731,7 +2731,7 @@ int svt_hip_me_launch(SvtHipContext *ctx, SvtHipLane *lane, const MeKernelParams
     // the dense pre-pass: entries, the slot buffer (one slot per job, searched reference and kind; 0xFF = "not filled")
     static thread_local MeDenseEntry entries[SVT_HIP_ME_DENSE_MAX_ENTRIES];
     uint32_t n_entries = 0, n_units = 0;
-    if (ctx->me_dense) n_entries = dense_plan(params, n_jobs, n_pictures, entries, &n_units, (uint32_t)ctx->num_cus * 4u * SVT_HIP_ME_DENSE_WAVES);
+    if (ctx->me_dense) n_entries = dense_plan(params, n_jobs, n_pictures, entries, &n_units, (uint32_t)ctx->num_cus * 4u * SVT_HIP_ME_DENSE_WAVES, ctx->me_dense_plan);
     auto grow = [&](void **buf, size_t *have, size_t need) -> int { // a lane's device buffers grow on demand (earlier launches of the lane may still read the old one)
         if (need <= *have) return SVT_HIP_OK;
         if (*buf) {
@@ -2750,6 +2750,9 @@ int svt_hip_me_launch(SvtHipContext *ctx, SvtHipLane *lane, const MeKernelParams
         hdr.dense = static_cast<MeDenseSlot *>(lane->dense);
         hdr.n_dense_entries = n_entries; hdr.n_dense_units = n_units;
         hdr.count_dense = ctx->me_counting ? 1u : 0u;
+        hdr.dense_fast  = ctx->me_dense_fast ? 1u : 0u;
+        lane->dense_used = need;
+        lane->dense_seq  = __atomic_add_fetch(&ctx->me_dense_seq, 1ull, __ATOMIC_RELAXED);
     }
     // With a pre-pass the per-block pipeline runs STAGED: small kernels cut at its searches, a block's state travelling through HBM between them
     // (a launch of few blocks is bound by latency, not by throughput: the chain of nine short kernels costs it more than it gains)
@@ -2761,7 +2764,7 @@ int svt_hip_me_launch(SvtHipContext *ctx, SvtHipLane *lane, const MeKernelParams
         hdr.stage     = base;
         hdr.job_flags = reinterpret_cast<uint32_t *>(base + stage_bytes);
         hdr.lists[0] = reinterpret_cast<uint32_t *>(base + stage_bytes + words); // the deferred blocks
-        SVT_HIP_CHECK(ctx, hipMemsetAsync(lane->queue_head + 128, 0, SVT_HIP_ME_QUEUE_BLOCK_BYTES - 128 * sizeof(uint32_t), lane->stream)); // the staged kernels' counters and the lists
+        SVT_HIP_CHECK(ctx, hipMemsetAsync(lane->queue_head + SVT_HIP_ME_LIST_CURSOR(0), 0, SVT_HIP_ME_QUEUE_BLOCK_BYTES - SVT_HIP_ME_LIST_CURSOR(0) * sizeof(uint32_t), lane->stream)); // the lists' cursors and counts
     }
     if (!ctx->me_attr_set) { // per context = per device; racing first calls set the same value
         const void *kernels[] = {reinterpret_cast<const void *>(svt_hip_me_b64_kernel),  reinterpret_cast<const void *>(svt_hip_me_mid1_kernel), reinterpret_cast<const void *>(svt_hip_me_s1_kernel),
@@ -2887,6 +2890,54 @@ extern "C" int svt_hip_me_dense_counters(SvtHipContext *ctx, unsigned long long 
         SVT_HIP_CHECK(ctx, hipMemset(l.queue_head + SVT_HIP_ME_COUNTER_WORD, 0, sizeof(v)));
         out[0] += v[0]; out[1] += v[1];
     }
+    return SVT_HIP_OK;
+}
+
+extern "C" int svt_hip_context_set_me_dense_fast(SvtHipContext *ctx, int on) {
+    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
+    ctx->me_dense_fast = on != 0;
+    return SVT_HIP_OK;
+}
+
+extern "C" int svt_hip_context_set_me_dense_plan(SvtHipContext *ctx, int plan) {
+    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
+    if (plan < 0 || plan > 3) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_context_set_me_dense_plan: %d is not 0 (by launch size), 1 (long units), 2 or 3 (fine units)", plan);
+    ctx->me_dense_plan = plan;
+    return SVT_HIP_OK;
+}
+
+// Diagnostics: the units of the pre-pass by the walk they took, and the (source row, search row) pairs of their waves, since the last call
+extern "C" int svt_hip_me_dense_path_counters(SvtHipContext *ctx, unsigned long long out[2 * SVT_HIP_ME_DENSE_PATHS + 7]) {
+    static_assert(SVT_HIP_ME_DENSE_PATHS == kMeDensePaths, "paths");
+    if (!ctx || !out) return SVT_HIP_ERR_BAD_PARAM;
+    memset(out, 0, SVT_HIP_ME_DENSE_PATH_COUNTERS * sizeof(out[0]));
+    hipSetDevice(ctx->device);
+    for (int i = 0; i < SVT_HIP_LANES; i++) {
+        SvtHipLane &l = ctx->lane[i];
+        if (!l.ready) continue;
+        unsigned long long v[SVT_HIP_ME_DENSE_PATH_COUNTERS];
+        SVT_HIP_CHECK(ctx, hipStreamSynchronize(l.stream));
+        SVT_HIP_CHECK(ctx, hipMemcpy(v, l.queue_head + SVT_HIP_ME_DENSE_PATH_WORD, sizeof(v), hipMemcpyDeviceToHost));
+        SVT_HIP_CHECK(ctx, hipMemset(l.queue_head + SVT_HIP_ME_DENSE_PATH_WORD, 0, sizeof(v)));
+        for (int k = 0; k < SVT_HIP_ME_DENSE_PATH_COUNTERS; k++) out[k] += v[k];
+    }
+    return SVT_HIP_OK;
+}
+
+// Diagnostics: the slot buffer of the context's most recent launch with a pre-pass (waits for that launch).  *bytes = its size; the slots are
+// copied when they fit `capacity`.
+extern "C" int svt_hip_me_dense_slots(SvtHipContext *ctx, void *out, size_t capacity, size_t *bytes) {
+    if (!ctx || !bytes) return SVT_HIP_ERR_BAD_PARAM;
+    *bytes = 0;
+    hipSetDevice(ctx->device);
+    const SvtHipLane *last = nullptr;
+    for (int i = 0; i < SVT_HIP_LANES; i++)
+        if (ctx->lane[i].ready && ctx->lane[i].dense_seq && (!last || ctx->lane[i].dense_seq > last->dense_seq)) last = &ctx->lane[i];
+    if (!last) return SVT_HIP_OK;
+    *bytes = last->dense_used;
+    if (!out || capacity < last->dense_used) return SVT_HIP_OK;
+    SVT_HIP_CHECK(ctx, hipStreamSynchronize(last->stream));
+    SVT_HIP_CHECK(ctx, hipMemcpy(out, last->dense, last->dense_used, hipMemcpyDeviceToHost));
     return SVT_HIP_OK;
 }
 

@@ -123,6 +123,7 @@ int svt_hip_context_create(SvtHipContext **out, int device) {
     ctx->device  = device;
     ctx->num_cus = prop.multiProcessorCount;
     { const char *e = getenv("SVT_HIP_ME_DENSE"); ctx->me_dense = !(e && e[0] == '0'); }
+    { const char *e = getenv("SVT_HIP_ME_DENSE_FAST"); ctx->me_dense_fast = !(e && e[0] == '0'); }
     { const char *e = getenv("SVT_HIP_ME_STAGED"); ctx->me_staged = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1; }
     // lane 0 (the asynchronous entries' stream) and this device's transform tables exist from the start; the borrowed
     // lanes are made when a synchronous entry first needs one

@@ -30,6 +30,8 @@ struct SvtHipLane {
     size_t      scratch_bytes;
     void       *dense;       // slots of the ME dense pre-pass (me_dense.inl), grown on demand
     size_t      dense_bytes;
+    size_t      dense_used;  // bytes of `dense` the lane's last launch with a pre-pass filled, and that launch's number in the context (svt_hip_me_dense_slots)
+    unsigned long long dense_seq;
     void       *stage;       // staged ME launches: the blocks' travelling records, flag words and the three job lists
     size_t      stage_bytes;
     hipEvent_t  me_mark[SVT_HIP_ME_CHAIN_KERNELS + 1]; // svt_hip_context_set_me_timing: events around the kernels of the last ME launch (created on first use)
@@ -61,6 +63,9 @@ struct SvtHipContext {
     void       *tpl_group_host;        // their pinned staging copies
     hipEvent_t  tpl_group_done[4];     // recorded behind the last launch that reads slot i (SVT_HIP_TPL_GROUP_RING)
     int         tpl_group_next;
+    bool        me_dense_fast;         // the pre-pass takes its static walk where a unit allows it (svt_hip_context_set_me_dense_fast)
+    int         me_dense_plan;         // 0: the pre-pass's units are sized by the launch; 1 .. 3: long / middle / fine units (svt_hip_context_set_me_dense_plan)
+    unsigned long long me_dense_seq;   // launches with a pre-pass so far
     uint32_t    me_max_waves;          // 0: no limit; else the most persistent waves an ME kernel is launched with (svt_hip_context_set_me_max_waves)
 };
 
