@@ -380,6 +380,16 @@ typedef struct SvtHipRdoqDesc {
 int    svt_hip_rdoq_batch(SvtHipContext *ctx, const SvtHipRdoqDesc *d);
 size_t svt_hip_rdoq_desc_size(void); /* sizeof(SvtHipRdoqDesc) as compiled */
 
+/* The launch of svt_hip_coeff_rate_batch and svt_hip_rdoq_batch.  Both pack the jobs of a batch into waves (four jobs of 16 coefficients, two
+ * of 32, one of any other size: a pack) and launch at most 2048 workgroups of four waves; wave v of workgroup b takes the packs b * 4 + v,
+ * b * 4 + v + grid * 4, ... -- more than one of them (a second "trip") once a batch holds more than grid * 4 packs.
+ * svt_hip_context_set_lvmap_max_grid lowers (or raises) that limit of 2048 for the context's later batches; 0 restores it.  The results do
+ * not depend on it: it is there so that a small batch can walk the loop as a picture-sized one does.
+ * svt_hip_lvmap_plan is host arithmetic alone (no context, no device): what a batch of n_jobs jobs of tx_size would launch under the limit
+ * max_grid (0: 2048) -- the workgroups, the packs and the jobs per pack.  Non-zero for tx_size >= 19 or a null output. */
+int svt_hip_context_set_lvmap_max_grid(SvtHipContext *ctx, uint32_t max_grid);
+int svt_hip_lvmap_plan(uint32_t tx_size, uint32_t n_jobs, uint32_t max_grid, uint32_t *grid, uint32_t *n_packs, uint32_t *jobs_per_pack);
+
 /* Full-pel motion-compensated prediction from ME results: every 16x16 PU copies the block of `ref` displaced by its
  * best integer MV (sb_best_mv = SvtHipMeResults.sb_best_mv, device pointer; list / ref_idx select the reference).
  * ref / pred are device planes of `bit_depth` 8 (uint8) or 10 (uint16), strides in samples, no padding needed

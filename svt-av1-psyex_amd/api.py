@@ -58,6 +58,15 @@ def check_desc(name, d):
         raise SvtHipError(f"{name}: {ERRORS.get(rc, rc)}: {L.svt_hip_last_error(None).decode()}")
 
 
+def lvmap_plan(tx_size, n_jobs, max_grid=0):
+    """(workgroups, packs, jobs per pack) of a rate / RDOQ batch of n_jobs jobs under the limit max_grid (svt_hip_lvmap_plan; host arithmetic, no GPU)"""
+    grid, n_packs, jobs_per_pack = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc = lib().svt_hip_lvmap_plan(C.c_uint32(tx_size), C.c_uint32(n_jobs), C.c_uint32(max_grid), C.byref(grid), C.byref(n_packs), C.byref(jobs_per_pack))
+    if rc:
+        raise SvtHipError(f"svt_hip_lvmap_plan: {ERRORS.get(rc, rc)}: {lib().svt_hip_last_error(None).decode()}")
+    return grid.value, n_packs.value, jobs_per_pack.value
+
+
 def ptr(t):
     """The device address of a tensor, or None (a null pointer in a descriptor) for None."""
     return t.data_ptr() if t is not None else None
@@ -145,6 +154,11 @@ class Context:
     def set_me_max_waves(self, waves):
         """upper limit of the persistent ME waves of a whole launch (svt_hip_context_set_me_max_waves); 0: none"""
         self.check(lib().svt_hip_context_set_me_max_waves(self._h, int(waves)), "svt_hip_context_set_me_max_waves")
+
+    def set_lvmap_max_grid(self, max_grid):
+        """upper limit of the workgroups of a rate / RDOQ batch (svt_hip_context_set_lvmap_max_grid); 0: the default of 2048.  Results are identical
+        either way: a small limit makes the waves of a small batch take several packs in turn, as they do on a picture-sized one"""
+        self.check(lib().svt_hip_context_set_lvmap_max_grid(self._h, int(max_grid)), "svt_hip_context_set_lvmap_max_grid")
 
     def set_me_timing(self, on):
         """ME launches record events around the kernels of their chain (svt_hip_context_set_me_timing)"""

@@ -205,6 +205,22 @@ extern "C" {
 size_t svt_hip_coeff_rate_desc_size(void) { return sizeof(SvtHipCoeffRateDesc); }
 size_t svt_hip_rate_tables_size(void) { return sizeof(SvtHipRateTables); }
 
+// the launch of the rate and RDOQ batches (lvmap_grid), for a caller or a test that wants to know how many trips a wave makes
+int svt_hip_lvmap_plan(uint32_t tx_size, uint32_t n_jobs, uint32_t max_grid, uint32_t *grid, uint32_t *n_packs, uint32_t *jobs_per_pack) {
+    if (tx_size >= SVT_HIP_TX_SIZES_ALL || !grid || !n_packs || !jobs_per_pack)
+        return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_lvmap_plan: tx_size %u (below 19) or a null output", tx_size);
+    const LvMapGeom g = lvmap_geom((int)tx_size);
+    *grid          = lvmap_grid(g, n_jobs, max_grid, *n_packs); // no jobs: no packs and no launch
+    *jobs_per_pack = (uint32_t)g.jobs_per_wave;
+    return SVT_HIP_OK;
+}
+
+int svt_hip_context_set_lvmap_max_grid(SvtHipContext *ctx, uint32_t max_grid) {
+    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
+    ctx->lvmap_max_grid = max_grid;
+    return SVT_HIP_OK;
+}
+
 int svt_hip_coeff_rate_batch(SvtHipContext *ctx, const SvtHipCoeffRateDesc *d) {
     if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: null context or descriptor");
     if (d->tx_size >= SVT_HIP_TX_SIZES_ALL || d->plane_type > 1)
@@ -232,7 +248,7 @@ int svt_hip_coeff_rate_batch(SvtHipContext *ctx, const SvtHipCoeffRateDesc *d) {
     p.g = g;
     for (int inter = 0; inter < 2; inter++) p.ext_set[inter] = ext_tx_set(ts, inter, d->reduced_tx_set != 0);
     p.c_div = d->mds_fast_coeff_est_level > d->mds_subres_step ? (uint32_t)(d->mds_fast_coeff_est_level - d->mds_subres_step) : 1u;
-    const uint32_t grid = lvmap_grid(g, d->n_jobs, p.n_packs);
+    const uint32_t grid = lvmap_grid(g, d->n_jobs, ctx->lvmap_max_grid, p.n_packs);
     std::lock_guard<std::mutex> lock(ctx->async_mu); // the winners' launch follows its own costs' when several threads enqueue
     if (d->n_jobs) {
         switch (g.n) {

@@ -52,11 +52,12 @@ inline LvMapGeom lvmap_geom(int ts) {
     g.jobs_per_wave = g.n >= 64 ? 1 : 64 / g.n;
     return g;
 }
-// the packs of n_jobs jobs, and the grid that walks them wave-strided
-inline uint32_t lvmap_grid(const LvMapGeom &g, uint32_t n_jobs, uint32_t &n_packs) {
-    n_packs = (n_jobs + (uint32_t)g.jobs_per_wave - 1) / (uint32_t)g.jobs_per_wave;
-    const uint32_t grid = (n_packs + kWaves - 1) / kWaves;
-    return grid < (uint32_t)kMaxGrid ? grid : (uint32_t)kMaxGrid;
+// the packs of n_jobs jobs, and the grid of at most max_grid workgroups (0: kMaxGrid) that walks them wave-strided
+inline uint32_t lvmap_grid(const LvMapGeom &g, uint32_t n_jobs, uint32_t max_grid, uint32_t &n_packs) {
+    const uint32_t jpw = (uint32_t)g.jobs_per_wave;
+    n_packs = n_jobs / jpw + (n_jobs % jpw != 0); // no sum that could wrap
+    const uint32_t grid = n_packs / kWaves + (n_packs % kWaves != 0), cap = max_grid ? max_grid : (uint32_t)kMaxGrid;
+    return grid < cap ? grid : cap;
 }
 
 // ---- device: the scaffolding

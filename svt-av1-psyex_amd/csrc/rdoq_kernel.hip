@@ -459,7 +459,7 @@ int svt_hip_rdoq_batch(SvtHipContext *ctx, const SvtHipRdoqDesc *d) {
     p.iscan  = ctx->iscan_dev + (size_t)d->tx_size * 3 * 1024;
     p.g      = lvmap_geom(d->tx_size);
     p.rshift = d->sharpness > 2 ? d->sharpness : 2;
-    const uint32_t grid = lvmap_grid(p.g, d->n_jobs, p.n_packs);
+    const uint32_t grid = lvmap_grid(p.g, d->n_jobs, ctx->lvmap_max_grid, p.n_packs);
     std::lock_guard<std::mutex> lock(ctx->async_mu);
     switch (p.g.n) {
 #define CASE(N) case N: hipLaunchKernelGGL(rdoq_kernel<N>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, p); break;

@@ -67,6 +67,7 @@ struct SvtHipContext {
     int         me_dense_plan;         // 0: the pre-pass's units are sized by the launch; 1 .. 3: long / middle / fine units (svt_hip_context_set_me_dense_plan)
     unsigned long long me_dense_seq;   // launches with a pre-pass so far
     uint32_t    me_max_waves;          // 0: no limit; else the most persistent waves an ME kernel is launched with (svt_hip_context_set_me_max_waves)
+    uint32_t    lvmap_max_grid;        // 0: the rate / RDOQ batches launch at most 2048 workgroups; else that many (svt_hip_context_set_lvmap_max_grid)
 };
 
 struct SvtHipPaPicture {

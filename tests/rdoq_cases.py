@@ -551,28 +551,36 @@ def crc(a):
     return zlib.crc32(np.ascontiguousarray(a).tobytes())
 
 
+SPOILS = 7
+
+
+def spoil(c, inp, i, m):
+    """makes job i (eob >= 2) of a case and its inputs, in place, one the reference leaves undefined: the m-th way of SPOILS"""
+    n = c["coeff"].shape[1]
+    if m == 0:
+        inp["eob"][i] = n + 1
+    elif m == 1:
+        inp["eob"][i] = 65535
+    elif m == 2:
+        inp["qcoeff"][i, cr.scan_order(c["tx_size"], int(c["jobs"][i]["tx_type"]))[int(inp["eob"][i]) - 1]] = 0
+    elif m == 3:
+        c["jobs"][i]["txb_skip_ctx"] = 13
+    elif m == 4:
+        c["jobs"][i]["dc_sign_ctx"] = 3
+    elif m == 5:
+        c["jobs"][i]["tx_type"] = 16
+    else:
+        c["jobs"][i]["quant_row"] = len(c["quant_rows"])
+
+
 def undefined_case(tx_size, seed=7):
     """jobs the reference leaves undefined among ordinary ones: (case, inputs, the indices of the undefined jobs)"""
     c = build_case(tx_size, 0, seed)
     inp = quantized(c)
-    n = c["coeff"].shape[1]
     ok = [i for i in range(len(c["jobs"])) if inp["eob"][i] >= 2]
-    bad = ok[1::2][:7]
+    bad = ok[1::2][:SPOILS]
     for m, i in enumerate(bad):
-        if m == 0:
-            inp["eob"][i] = n + 1
-        elif m == 1:
-            inp["eob"][i] = 65535
-        elif m == 2:
-            inp["qcoeff"][i, cr.scan_order(tx_size, int(c["jobs"][i]["tx_type"]))[int(inp["eob"][i]) - 1]] = 0
-        elif m == 3:
-            c["jobs"][i]["txb_skip_ctx"] = 13
-        elif m == 4:
-            c["jobs"][i]["dc_sign_ctx"] = 3
-        elif m == 5:
-            c["jobs"][i]["tx_type"] = 16
-        else:
-            c["jobs"][i]["quant_row"] = len(c["quant_rows"])
+        spoil(c, inp, i, m)
     return c, inp, bad
 
 

@@ -49,13 +49,15 @@ def odd_count(tx_size, n):
     return n - 1 if jpw > 1 and n % jpw == 0 else n
 
 
-def run(ctx, dev_table, c, n, variant=(1, 0), lvl=1, **kw):
-    """the batch on the first n jobs of a case, outputs pre-filled with 0xA5 and n spare slots behind each: checks the guards, returns the rest"""
+def run(ctx, dev_table, c, n, variant=(1, 0), lvl=1, spare=None, **kw):
+    """the batch on the first n jobs of a case, outputs pre-filled with 0xA5 and `spare` spare slots (default n) behind each: checks the guards,
+    returns the rest"""
+    spare = n if spare is None else spare
     out = rate.run_rate_hip(ctx, dev_table, c["tx_size"], c["plane"], c["jobs"][:n], c["qcoeff"][:n], c["eob"][:n], reduced_tx_set=c["reduced"],
-                            coeff_rate_est_lvl=lvl, mds_fast_coeff_est_level=variant[0], mds_subres_step=variant[1], spare_jobs=n, fill=FILL, **kw)
+                            coeff_rate_est_lvl=lvl, mds_fast_coeff_est_level=variant[0], mds_subres_step=variant[1], spare_jobs=spare, fill=FILL, **kw)
     res = {}
     for name, a in out.items():
-        m = len(a) - n
+        m = len(a) - spare
         assert np.all(a[m:].view(np.uint8) == FILL), f"{name}: spare slots written"
         res[name] = a[:m]
     return res

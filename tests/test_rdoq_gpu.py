@@ -21,15 +21,16 @@ def dev_tables(hip_ctx):
     return [rate.upload_tables(T) for T in rq.shared()["tables"]]
 
 
-def run(ctx, dev_table, c, inp, n, fallback=True):
-    """the batch on the first n jobs of a case, every array pre-filled with 0xA5 and followed by n spare slots: checks the guards and that coeff is
-    unchanged, returns the rest cut to n jobs"""
+def run(ctx, dev_table, c, inp, n, fallback=True, spare=None):
+    """the batch on the first n jobs of a case, every array pre-filled with 0xA5 and followed by `spare` spare slots (default n): checks the guards
+    and that coeff is unchanged, returns the rest cut to n jobs"""
+    spare = n if spare is None else spare
     fb = (inp["qcoeff_b"][:n], inp["dqcoeff_b"][:n], inp["eob_b"][:n]) if fallback else None
     out = rdoq.run_rdoq_hip(ctx, dev_table, c["tx_size"], c["plane"], c["jobs"][:n], c["quant_rows"], c["coeff"][:n], inp["qcoeff"][:n], inp["dqcoeff"][:n],
-                            inp["eob"][:n], c["lam"], iqmatrix=c["iqmatrix"], fallback=fb, spare_jobs=n, fill=FILL, **{k: c[k] for k in CONTROLS})
+                            inp["eob"][:n], c["lam"], iqmatrix=c["iqmatrix"], fallback=fb, spare_jobs=spare, fill=FILL, **{k: c[k] for k in CONTROLS})
     res = {}
     for name, a in out.items():
-        assert len(a) == 2 * n, name
+        assert len(a) == n + spare, name
         assert np.all(np.ascontiguousarray(a[n:]).view(np.uint8) == FILL), f"{name}: spare slots written"
         res[name] = a[:n]
     assert np.array_equal(res.pop("coeff"), c["coeff"][:n]), "coeff changed"
@@ -135,13 +136,12 @@ def test_rejected_descriptor_returns_non_zero_and_leaves_the_buffers_as_filled(h
         assert bool(torch.all(t == FILL)), name
 
 
-@pytest.mark.parametrize("tx_size", [0, 2, 17, 4])  # TX_4X4, TX_16X16, TX_16X64, TX_64X64
-def test_chain_rd_batch_rdoq_rate_batch_inverse_on_device(hip_ctx, dev_tables, tx_size):
+def chain(hip_ctx, dev_tables, tx_size):
     """tx_type_search with RDOQ on the device: svt_hip_rd_batch (quant_kind 1) writes coeff / qcoeff / dqcoeff / eob / dist_coeff, svt_hip_rdoq_batch
     rewrites them in place, svt_hip_coeff_rate_batch prices them (dist_stride 2 on the renewed dist_coeff) and picks the groups' winners,
     svt_hip_inv_txfm_batch reconstructs from the optimised dqcoeff -- all on the same stream and buffers, one synchronisation at the end.  The
     inverse runs on every candidate (choosing the winners' jobs on the host would need a second synchronisation); the winners' blocks are the ones
-    checked.  Equal to the restatements fed with the oracle's RD outputs."""
+    checked.  Equal to the restatements fed with the oracle's RD outputs.  Returns the job count."""
     import pyoracle
     import torch
     T = rq.shared()["tables"][0]
@@ -210,3 +210,10 @@ def test_chain_rd_batch_rdoq_rate_batch_inverse_on_device(hip_ctx, dev_tables, t
         L.orc_inv_txfm2d_add(dq.ctypes.data_as(C.c_void_p), C.c_void_p(pred.ctypes.data + 2 * off), W, blk.ctypes.data_as(C.c_void_p), tw,
                              int(jobs["tx_type"][j]), tx_size, 10)
         assert np.array_equal(recon[y:y + th, x:x + tw], blk), j
+    return n
+
+
+@pytest.mark.parametrize("tx_size", [0, 2, 17, 4])  # TX_4X4, TX_16X16, TX_16X64, TX_64X64
+def test_chain_rd_batch_rdoq_rate_batch_inverse_on_device(hip_ctx, dev_tables, tx_size):
+    """the chain of chain() at four sizes, under the default cap of the grid"""
+    chain(hip_ctx, dev_tables, tx_size)
