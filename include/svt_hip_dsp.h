@@ -83,7 +83,8 @@ typedef struct SvtHipRdBatchDesc {
 } SvtHipRdBatchDesc;
 
 /* Enqueues one batch on the context stream (asynchronous).  Every pointer in `d` is a DEVICE pointer.
- * Returns non-zero (and leaves nothing enqueued) when the descriptor fails validation. */
+ * Returns non-zero (and leaves nothing enqueued) when the descriptor fails validation.
+ * Every svt_hip_*_batch entry of this header that takes a descriptor leaves "<entry>: null context or descriptor" in svt_hip_last_error for a null argument. */
 int svt_hip_rd_batch(SvtHipContext *ctx, const SvtHipRdBatchDesc *d);
 
 /* ---- forward transform alone ------------------------------------------------------------------------------------

@@ -73,7 +73,8 @@ typedef struct SvtHipFullpelBatchDesc {
     int16_t  *best_mv;                     /* [n_jobs][2] = (best_mvx, best_mvy) */
 } SvtHipFullpelBatchDesc;
 
-/* Jobs of one batch run concurrently: a job chains only from its own slot, as a batch enqueued earlier on the stream (same output arrays) left it. */
+/* Jobs of one batch run concurrently: a job chains only from its own slot, as a batch enqueued earlier on the stream (same output arrays) left it.
+ * Both batch entries of this header: non-zero and a text in svt_hip_last_error for a refused descriptor, "<entry>: null context or descriptor" for a null argument. */
 int svt_hip_md_fullpel_batch(SvtHipContext *ctx, const SvtHipFullpelBatchDesc *d);
 
 #define SVT_HIP_USE_2_TAPS 1

@@ -72,7 +72,8 @@ typedef struct SvtHipPmeBatchDesc {
     int16_t  *best_mv;               /* out: [n_jobs][2] = (best_mvx, best_mvy) */
 } SvtHipPmeBatchDesc;
 
-/* Enqueues the batch on the context stream (asynchronous); one wave per job. */
+/* Enqueues the batch on the context stream (asynchronous); one wave per job.
+ * Non-zero and a text in svt_hip_last_error for a refused descriptor, "svt_hip_pme_sad_batch: null context or descriptor" for a null argument. */
 int svt_hip_pme_sad_batch(SvtHipContext *ctx, const SvtHipPmeBatchDesc *d);
 
 /* svt_pme_sad_loop_kernel (aom_dsp_rtcd.h:868): host pointers, synchronous (see svt_hip_leaf.h for the contract of the pointer-level entries) */

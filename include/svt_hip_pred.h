@@ -89,7 +89,8 @@ typedef struct SvtHipInterPredDesc {
 } SvtHipInterPredDesc;
 
 /* Enqueues one batch on the context stream (asynchronous); one wave per job.  Returns SVT_HIP_ERR_BAD_PARAM (and svt_hip_last_error) and
- * enqueues nothing when svt_hip_inter_pred_check_desc refuses the descriptor; n_jobs == 0 returns 0 and enqueues nothing. */
+ * enqueues nothing when svt_hip_inter_pred_check_desc refuses the descriptor; n_jobs == 0 returns 0 and enqueues nothing.
+ * A null context or descriptor leaves "<entry>: null context or descriptor", here and in every other svt_hip_*_batch entry that takes a descriptor. */
 int    svt_hip_inter_pred_batch(SvtHipContext *ctx, const SvtHipInterPredDesc *d);
 /* Host-only validation: null descriptor or dst / jobs / status, bit_depth other than 8 / 10, ss_x / ss_y > 1, n_refs outside
  * 1..SVT_HIP_INTER_PRED_MAX_REFS, a reference with a null plane, a zero stride, a stride below its width, or an origin outside the plane,

@@ -1,7 +1,8 @@
-// batch_host.h -- the host side that the prediction batch entries share (inter, intra, CfL, warp, masked compound /
-// inter-intra, OBMC, the interpolation-filter search, palette): the refusal macro of their *_check_desc functions, the
-// validation of an SvtHipInterPredRef array, the lookup behind every *_layout entry and the enqueue sequence of an
-// asynchronous batch entry.  A new batch entry supplies a check, a count and a launch; the order of the steps is here.
+// batch_host.h -- the host side that the asynchronous batch entries share: the enqueue sequence of a batch entry (the
+// eight files of inter, intra, CfL, warp, masked compound / inter-intra, OBMC, the interpolation-filter search and palette;
+// RD and the transforms alone, the MD searches, PME, statistics, SSIM, rate, RDOQ), and for the first eight the refusal
+// macro of their *_check_desc functions, the validation of an SvtHipInterPredRef array and the lookup behind every
+// *_layout entry.  A new batch entry supplies a check, a count and a launch; the order of the steps is here.
 #ifndef SVT_HIP_BATCH_HOST_H
 #define SVT_HIP_BATCH_HOST_H
 #include <stddef.h>
@@ -46,20 +47,30 @@ static inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b
 // The 10-bit or the 8-bit instantiation of a kernel template: pick_hbd(d->bit_depth, kernel<true>, kernel<false>)
 template <class Kernel> Kernel pick_hbd(unsigned bit_depth, Kernel hbd, Kernel lbd) { return bit_depth == 10 ? hbd : lbd; }
 
-// An asynchronous batch entry: refuses null arguments and what `check` refuses, returns for an empty batch before it
-// touches the context, then enqueues on ctx->stream under ctx->async_mu.  `count` is the descriptor's member that says
-// how much there is to do; `launch` holds the entry's hipLaunchKernelGGL calls and its grid arithmetic.
-template <class Desc, class Check, class Launch>
-int enqueue_batch(const char *entry, SvtHipContext *ctx, const Desc *d, Check check, uint32_t Desc::*count, Launch launch) {
-    if (!ctx || !d) BAD("%s: null context or descriptor", entry);
-    const int rc = check(d);
-    if (rc) return rc;
-    if (d->*count == 0) return SVT_HIP_OK;
+// The enqueue itself, on ctx->stream under ctx->async_mu, with one question to the runtime behind all of `launch`'s
+// hipLaunchKernelGGL calls.  An entry that takes an argument list, not a descriptor, calls this after its own checks.
+template <class Launch> int enqueue_locked(const char *entry, SvtHipContext *ctx, Launch launch) {
     (void)hipSetDevice(ctx->device);
     std::lock_guard<std::mutex> lock(ctx->async_mu);
     launch();
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return svt_hip_fail(ctx, SVT_HIP_ERR_LAUNCH, "%s: the launch failed: %s", entry, hipGetErrorString(e));
     return SVT_HIP_OK;
+}
+
+// An asynchronous batch entry: refuses null arguments and what `check` refuses, returns for an empty batch before it
+// touches the context, then enqueues.  `count` (and `count2`: both zero) is the descriptor's member that says how much
+// there is to do; `launch` holds the entry's hipLaunchKernelGGL calls and its grid arithmetic.
+template <class Desc, class Check, class Launch>
+int enqueue_batch(const char *entry, SvtHipContext *ctx, const Desc *d, Check check, uint32_t Desc::*count, uint32_t Desc::*count2, Launch launch) {
+    if (!ctx || !d) BAD("%s: null context or descriptor", entry);
+    const int rc = check(d);
+    if (rc) return rc;
+    if (d->*count == 0 && d->*count2 == 0) return SVT_HIP_OK;
+    return enqueue_locked(entry, ctx, launch);
+}
+template <class Desc, class Check, class Launch>
+int enqueue_batch(const char *entry, SvtHipContext *ctx, const Desc *d, Check check, uint32_t Desc::*count, Launch launch) {
+    return enqueue_batch(entry, ctx, d, check, count, count, launch);
 }
 #endif

@@ -18,6 +18,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_dsp.h"
 #include "lvmap_core.h"
 #include "wave_ops.h"
@@ -221,49 +222,40 @@ int svt_hip_context_set_lvmap_max_grid(SvtHipContext *ctx, uint32_t max_grid) {
     return SVT_HIP_OK;
 }
 
-int svt_hip_coeff_rate_batch(SvtHipContext *ctx, const SvtHipCoeffRateDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: null context or descriptor");
+static int coeff_rate_check(const SvtHipCoeffRateDesc *d) {
     if (d->tx_size >= SVT_HIP_TX_SIZES_ALL || d->plane_type > 1)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: tx_size %u (below 19) / plane_type %u (0 or 1)", d->tx_size, d->plane_type);
+        BAD("svt_hip_coeff_rate_batch: tx_size %u (below 19) / plane_type %u (0 or 1)", d->tx_size, d->plane_type);
     if (d->mds_subres_step > 2 || d->mds_fast_coeff_est_level == 0)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: mds_subres_step %u (0..2) / mds_fast_coeff_est_level %u (not 0)",
-                            d->mds_subres_step, d->mds_fast_coeff_est_level);
-    if (!d->jobs || !d->tables || !d->qcoeff || !d->eob || !d->bits)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: a mandatory pointer (jobs, tables, qcoeff, eob, bits) is null");
-    const int       ts = d->tx_size;
-    const LvMapGeom g  = lvmap_geom(ts);
-    if (((uintptr_t)d->qcoeff & 15) && g.n >= 256)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: qcoeff is not 16-byte aligned (sizes of 256 coefficients and more are read 16 bytes at a time)");
-    if (d->rd_cost && !d->dist) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: rd_cost without dist");
+        BAD("svt_hip_coeff_rate_batch: mds_subres_step %u (0..2) / mds_fast_coeff_est_level %u (not 0)", d->mds_subres_step, d->mds_fast_coeff_est_level);
+    if (!d->jobs || !d->tables || !d->qcoeff || !d->eob || !d->bits) BAD("svt_hip_coeff_rate_batch: a mandatory pointer (jobs, tables, qcoeff, eob, bits) is null");
+    if (((uintptr_t)d->qcoeff & 15) && lvmap_geom(d->tx_size).n >= 256)
+        BAD("svt_hip_coeff_rate_batch: qcoeff is not 16-byte aligned (sizes of 256 coefficients and more are read 16 bytes at a time)");
+    if (d->rd_cost && !d->dist) BAD("svt_hip_coeff_rate_batch: rd_cost without dist");
     const bool groups = d->n_groups || d->group_start || d->best_job || d->best_cost;
-    if (groups && !d->rd_cost) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: groups without rd_cost");
-    if (groups && (!d->group_start || !d->best_job || !d->best_cost))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: groups need group_start, best_job and best_cost");
-    if (d->n_jobs == 0 && d->n_groups == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    RateParams p;
-    memset(&p, 0, sizeof(p));
-    p.d = *d;
-    for (int k = 0; k < 3; k++) p.iscan[k] = ctx->iscan_dev + ((size_t)ts * 3 + k) * 1024;
-    p.g = g;
-    for (int inter = 0; inter < 2; inter++) p.ext_set[inter] = ext_tx_set(ts, inter, d->reduced_tx_set != 0);
-    p.c_div = d->mds_fast_coeff_est_level > d->mds_subres_step ? (uint32_t)(d->mds_fast_coeff_est_level - d->mds_subres_step) : 1u;
-    const uint32_t grid = lvmap_grid(g, d->n_jobs, ctx->lvmap_max_grid, p.n_packs);
-    std::lock_guard<std::mutex> lock(ctx->async_mu); // the winners' launch follows its own costs' when several threads enqueue
-    if (d->n_jobs) {
-        switch (g.n) {
+    if (groups && !d->rd_cost) BAD("svt_hip_coeff_rate_batch: groups without rd_cost");
+    if (groups && (!d->group_start || !d->best_job || !d->best_cost)) BAD("svt_hip_coeff_rate_batch: groups need group_start, best_job and best_cost");
+    return SVT_HIP_OK;
+}
+
+int svt_hip_coeff_rate_batch(SvtHipContext *ctx, const SvtHipCoeffRateDesc *d) {
+    // both launches under one hold of the lock: the winners' launch follows its own costs' when several threads enqueue
+    return enqueue_batch("svt_hip_coeff_rate_batch", ctx, d, coeff_rate_check, &SvtHipCoeffRateDesc::n_jobs, &SvtHipCoeffRateDesc::n_groups, [=] {
+        const int  ts = d->tx_size;
+        RateParams p;
+        memset(&p, 0, sizeof(p));
+        p.d = *d;
+        for (int k = 0; k < 3; k++) p.iscan[k] = ctx->iscan_dev + ((size_t)ts * 3 + k) * 1024;
+        p.g = lvmap_geom(ts);
+        for (int inter = 0; inter < 2; inter++) p.ext_set[inter] = ext_tx_set(ts, inter, d->reduced_tx_set != 0);
+        p.c_div = d->mds_fast_coeff_est_level > d->mds_subres_step ? (uint32_t)(d->mds_fast_coeff_est_level - d->mds_subres_step) : 1u;
+        const uint32_t grid = lvmap_grid(p.g, d->n_jobs, ctx->lvmap_max_grid, p.n_packs);
+        if (d->n_jobs) switch (p.g.n) { // lvmap_geom gives one of these for every tx_size the check accepted
 #define CASE(N) case N: hipLaunchKernelGGL(coeff_rate_kernel<N>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, p); break;
             CASE(16) CASE(32) CASE(64) CASE(128) CASE(256) CASE(512) CASE(1024)
 #undef CASE
-        default: return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_coeff_rate_batch: %d coefficients", g.n);
         }
-        SVT_HIP_CHECK(ctx, hipGetLastError());
-    }
-    if (d->n_groups) {
-        hipLaunchKernelGGL(rate_group_kernel, dim3((d->n_groups + 255) / 256), dim3(256), 0, ctx->stream, *d);
-        SVT_HIP_CHECK(ctx, hipGetLastError());
-    }
-    return SVT_HIP_OK;
+        if (d->n_groups) hipLaunchKernelGGL(rate_group_kernel, dim3(ceil_div(d->n_groups, 256)), dim3(256), 0, ctx->stream, *d);
+    });
 }
 
 } // extern "C"

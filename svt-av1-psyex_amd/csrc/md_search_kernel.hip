@@ -16,6 +16,7 @@
 #include <limits.h>
 #include <string.h>
 #include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_md_search.h"
 #include "mv_cost.h"
 #include "wave_ops.h"
@@ -375,36 +376,33 @@ __global__ void __launch_bounds__(64) md_subpel_kernel(const SubpelParams p) {
 
 } // namespace
 
-extern "C" int svt_hip_md_fullpel_batch(SvtHipContext *ctx, const SvtHipFullpelBatchDesc *d) {
-    if (!ctx || !d) return SVT_HIP_ERR_BAD_PARAM;
+static int md_fullpel_check(const SvtHipFullpelBatchDesc *d) {
     if (d->n_jobs == 0) return SVT_HIP_OK;
-    if (!d->src || !d->ref || !d->jobs || !d->best_cost || !d->best_mv) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "md full-pel batch: a mandatory pointer is null");
-    if (d->mv_cost_type < 0 || d->mv_cost_type > SVT_HIP_MV_COST_NONE) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "md full-pel batch: mv_cost_type %d", d->mv_cost_type);
+    if (!d->src || !d->ref || !d->jobs || !d->best_cost || !d->best_mv) BAD("md full-pel batch: a mandatory pointer is null");
+    if (d->mv_cost_type < 0 || d->mv_cost_type > SVT_HIP_MV_COST_NONE) BAD("md full-pel batch: mv_cost_type %d", d->mv_cost_type);
     if (d->mv_cost_type == SVT_HIP_MV_COST_ENTROPY && (!d->mvjcost || !d->mvcost[0] || !d->mvcost[1]))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "md full-pel batch: MV_COST_ENTROPY needs the joint and component cost tables");
-    hipSetDevice(ctx->device);
-    FullpelParams p;
-    p.d = *d;
-    hipLaunchKernelGGL(md_fullpel_kernel, dim3(d->n_jobs), dim3(64), 0, ctx->stream, p);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
+        BAD("md full-pel batch: MV_COST_ENTROPY needs the joint and component cost tables");
+    return SVT_HIP_OK;
+}
+
+extern "C" int svt_hip_md_fullpel_batch(SvtHipContext *ctx, const SvtHipFullpelBatchDesc *d) {
+    return enqueue_batch("svt_hip_md_fullpel_batch", ctx, d, md_fullpel_check, &SvtHipFullpelBatchDesc::n_jobs,
+                         [=] { hipLaunchKernelGGL(md_fullpel_kernel, dim3(d->n_jobs), dim3(64), 0, ctx->stream, FullpelParams{*d}); });
+}
+
+static int md_subpel_check(const SvtHipSubpelBatchDesc *d) {
+    if (d->n_jobs == 0) return SVT_HIP_OK;
+    if (!d->src || !d->ref || !d->jobs || !d->best_mv || !d->besterr || !d->distortion || !d->sse) BAD("md sub-pel batch: a mandatory pointer is null");
+    if (d->mv_cost_type < 0 || d->mv_cost_type > SVT_HIP_MV_COST_NONE || d->forced_stop < 0 || d->forced_stop > 3)
+        BAD("md sub-pel batch: mv_cost_type %d / forced_stop %d", d->mv_cost_type, d->forced_stop);
+    if (d->search_method < 0 || d->search_method > 1 || (d->search_method == 1 && (d->subpel_search_type < SVT_HIP_USE_2_TAPS || d->subpel_search_type > SVT_HIP_USE_8_TAPS)))
+        BAD("md sub-pel batch: search_method %d / subpel_search_type %d", d->search_method, d->subpel_search_type);
+    if (d->mv_cost_type == SVT_HIP_MV_COST_ENTROPY && (!d->mvjcost || !d->mvcost[0] || !d->mvcost[1]))
+        BAD("md sub-pel batch: MV_COST_ENTROPY needs the joint and component cost tables");
     return SVT_HIP_OK;
 }
 
 extern "C" int svt_hip_md_subpel_batch(SvtHipContext *ctx, const SvtHipSubpelBatchDesc *d) {
-    if (!ctx || !d) return SVT_HIP_ERR_BAD_PARAM;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    if (!d->src || !d->ref || !d->jobs || !d->best_mv || !d->besterr || !d->distortion || !d->sse)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "md sub-pel batch: a mandatory pointer is null");
-    if (d->mv_cost_type < 0 || d->mv_cost_type > SVT_HIP_MV_COST_NONE || d->forced_stop < 0 || d->forced_stop > 3)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "md sub-pel batch: mv_cost_type %d / forced_stop %d", d->mv_cost_type, d->forced_stop);
-    if (d->search_method < 0 || d->search_method > 1 || (d->search_method == 1 && (d->subpel_search_type < SVT_HIP_USE_2_TAPS || d->subpel_search_type > SVT_HIP_USE_8_TAPS)))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "md sub-pel batch: search_method %d / subpel_search_type %d", d->search_method, d->subpel_search_type);
-    if (d->mv_cost_type == SVT_HIP_MV_COST_ENTROPY && (!d->mvjcost || !d->mvcost[0] || !d->mvcost[1]))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "md sub-pel batch: MV_COST_ENTROPY needs the joint and component cost tables");
-    hipSetDevice(ctx->device);
-    SubpelParams p;
-    p.d = *d;
-    hipLaunchKernelGGL(md_subpel_kernel, dim3(d->n_jobs), dim3(64), 0, ctx->stream, p);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_batch("svt_hip_md_subpel_batch", ctx, d, md_subpel_check, &SvtHipSubpelBatchDesc::n_jobs,
+                         [=] { hipLaunchKernelGGL(md_subpel_kernel, dim3(d->n_jobs), dim3(64), 0, ctx->stream, SubpelParams{*d}); });
 }

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <string.h>
 #include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "leaf_guard.h"
 #include "../../include/svt_hip_pme.h"
 #include "mv_cost.h"
@@ -81,19 +82,18 @@ __global__ void __launch_bounds__(64) pme_sad_kernel(const PmeParams p) {
 
 } // namespace
 
-extern "C" int svt_hip_pme_sad_batch(SvtHipContext *ctx, const SvtHipPmeBatchDesc *d) {
-    if (!ctx || !d) return SVT_HIP_ERR_BAD_PARAM;
+static int pme_sad_check(const SvtHipPmeBatchDesc *d) {
     if (d->n_jobs == 0) return SVT_HIP_OK;
-    if (!d->src || !d->ref || !d->jobs || !d->best_cost || !d->best_mv) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "pme batch: a mandatory pointer is null");
-    if (d->mv_cost_type < 0 || d->mv_cost_type > SVT_HIP_MV_COST_NONE) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "pme batch: mv_cost_type %d", d->mv_cost_type);
+    if (!d->src || !d->ref || !d->jobs || !d->best_cost || !d->best_mv) BAD("pme batch: a mandatory pointer is null");
+    if (d->mv_cost_type < 0 || d->mv_cost_type > SVT_HIP_MV_COST_NONE) BAD("pme batch: mv_cost_type %d", d->mv_cost_type);
     if (d->mv_cost_type == SVT_HIP_MV_COST_ENTROPY && (!d->mvjcost || !d->mvcost[0] || !d->mvcost[1]))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "pme batch: MV_COST_ENTROPY needs the joint and component cost tables");
-    hipSetDevice(ctx->device);
-    PmeParams p;
-    p.d = *d;
-    hipLaunchKernelGGL(pme_sad_kernel, dim3(d->n_jobs), dim3(64), 0, ctx->stream, p);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
+        BAD("pme batch: MV_COST_ENTROPY needs the joint and component cost tables");
     return SVT_HIP_OK;
+}
+
+extern "C" int svt_hip_pme_sad_batch(SvtHipContext *ctx, const SvtHipPmeBatchDesc *d) {
+    return enqueue_batch("svt_hip_pme_sad_batch", ctx, d, pme_sad_check, &SvtHipPmeBatchDesc::n_jobs,
+                         [=] { hipLaunchKernelGGL(pme_sad_kernel, dim3(d->n_jobs), dim3(64), 0, ctx->stream, PmeParams{*d}); });
 }
 
 // ---- pointer-level entry (the reference's prototype, host pointers, synchronous) ----

@@ -16,6 +16,7 @@
 #include <string.h>
 #include <type_traits>
 #include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_dsp.h"
 
 #include "txfm_core.h"
@@ -665,16 +666,13 @@ template <int TS, int BD, typename Pix> __global__ void __launch_bounds__(64, rd
     }
 }
 
-template <int BD, typename Pix> int launch_inv(SvtHipContext *ctx, const InvParams &p) {
+template <int BD, typename Pix> void launch_inv(SvtHipContext *ctx, const InvParams &p) {
     const dim3 b(64);
-#define CASE(S) case S: hipLaunchKernelGGL((inv_tx_kernel<S, BD, Pix>), dim3((p.d.n_jobs + rd_blocks_per_wave(S) - 1) / rd_blocks_per_wave(S)), b, 0, ctx->stream, p); break;
-    switch (p.d.tx_size) {
+#define CASE(S) case S: hipLaunchKernelGGL((inv_tx_kernel<S, BD, Pix>), dim3(ceil_div(p.d.n_jobs, rd_blocks_per_wave(S))), b, 0, ctx->stream, p); break;
+    switch (p.d.tx_size) { // like launch_fwd and launch_size: no default, the entry's check let only these sizes through
         CASE(0) CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16) CASE(17) CASE(18)
-    default: return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "tx_size %d", p.d.tx_size);
     }
 #undef CASE
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -748,28 +746,22 @@ template <int TS> __global__ void __launch_bounds__(64, rd_waves_per_simd(TS)) f
     }
 }
 
-int launch_fwd(SvtHipContext *ctx, const FwdParams &p) {
+void launch_fwd(SvtHipContext *ctx, const FwdParams &p) {
     const dim3 b(64);
-#define CASE(S) case S: hipLaunchKernelGGL((fwd_tx_kernel<S>), dim3((p.d.n_jobs + rd_blocks_per_wave(S) - 1) / rd_blocks_per_wave(S)), b, 0, ctx->stream, p); break;
+#define CASE(S) case S: hipLaunchKernelGGL((fwd_tx_kernel<S>), dim3(ceil_div(p.d.n_jobs, rd_blocks_per_wave(S))), b, 0, ctx->stream, p); break;
     switch (p.d.tx_size) {
         CASE(0) CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16) CASE(17) CASE(18)
-    default: return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "tx_size %d", p.d.tx_size);
     }
 #undef CASE
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
 }
 
-template <int BD> int launch_size(SvtHipContext *ctx, const RdParams &p) {
+template <int BD> void launch_size(SvtHipContext *ctx, const RdParams &p) {
     const dim3 b(64);
-#define CASE(S) case S: hipLaunchKernelGGL((rd_tx_kernel<S, BD>), dim3((p.d.n_jobs + rd_blocks_per_wave(S) - 1) / rd_blocks_per_wave(S)), b, 0, ctx->stream, p); break;
+#define CASE(S) case S: hipLaunchKernelGGL((rd_tx_kernel<S, BD>), dim3(ceil_div(p.d.n_jobs, rd_blocks_per_wave(S))), b, 0, ctx->stream, p); break;
     switch (p.tx_size) {
         CASE(0) CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16) CASE(17) CASE(18)
-    default: return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "tx_size %d", p.tx_size);
     }
 #undef CASE
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
 }
 
 // host-side scan order generator (av1_scan_orders, Codec/coefficients.h:2197): diagonal scan for 2-D types and IDTX
@@ -800,27 +792,29 @@ int svt_hip_scan_order(int tx_size, int tx_type, int16_t *scan, int16_t *iscan) 
     return scan_order(tx_size, tx_type, scan, iscan);
 }
 
-int svt_hip_rd_batch(SvtHipContext *ctx, const SvtHipRdBatchDesc *d) {
-    if (!ctx || !d) return SVT_HIP_ERR_BAD_PARAM;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    if ((d->bit_depth != 8 && d->bit_depth != 10) || d->quant_kind > 2)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "bit_depth %u / quant_kind %u", d->bit_depth, d->quant_kind);
+static int rd_batch_check(const SvtHipRdBatchDesc *d) {
+    if (d->n_jobs == 0) return SVT_HIP_OK; // like the transform, MD search, PME and statistics entries: an empty batch is accepted whatever else it holds
+    if ((d->bit_depth != 8 && d->bit_depth != 10) || d->quant_kind > 2) BAD("bit_depth %u / quant_kind %u", d->bit_depth, d->quant_kind);
     if (!d->src || !d->pred || !d->jobs || !d->quant_rows || !d->eob || !d->satd || !d->dist_coeff || !d->three_quad_energy || !d->sse)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "a mandatory pointer of the RD batch is null");
-    if ((d->qmatrix == nullptr) != (d->iqmatrix == nullptr)) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "qmatrix and iqmatrix go together");
-    hipSetDevice(ctx->device);
-    RdParams p;
-    p.d       = *d;
-    p.tx_size = d->tx_size;
-    if (p.tx_size < 0 || p.tx_size >= 19) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "tx_size %d", p.tx_size);
-    for (int k = 0; k < 3; k++) p.iscan[k] = ctx->iscan_dev + ((size_t)p.tx_size * 3 + k) * 1024;
-    const int rc = d->bit_depth == 8 ? launch_size<8>(ctx, p) : launch_size<10>(ctx, p);
+        BAD("a mandatory pointer of the RD batch is null");
+    if ((d->qmatrix == nullptr) != (d->iqmatrix == nullptr)) BAD("qmatrix and iqmatrix go together");
+    if (d->tx_size >= SVT_HIP_TX_SIZES_ALL) BAD("tx_size %d", d->tx_size);
+    return SVT_HIP_OK;
+}
+
+int svt_hip_rd_batch(SvtHipContext *ctx, const SvtHipRdBatchDesc *d) {
+    const int rc = enqueue_batch("svt_hip_rd_batch", ctx, d, rd_batch_check, &SvtHipRdBatchDesc::n_jobs, [=] {
+        RdParams p = {*d, {}, d->tx_size};
+        for (int k = 0; k < 3; k++) p.iscan[k] = ctx->iscan_dev + ((size_t)p.tx_size * 3 + k) * 1024;
+        if (d->bit_depth == 8) launch_size<8>(ctx, p);
+        else launch_size<10>(ctx, p);
+    });
 #ifdef SVT_RD_TIER_STATS
     unsigned int st[10] = {0}, zero[10] = {0};
-    if (hipStreamSynchronize(ctx->stream) == hipSuccess && hipMemcpyFromSymbol(st, HIP_SYMBOL(g_rd_tier_stats), sizeof(st)) == hipSuccess &&
-        hipMemcpyToSymbol(HIP_SYMBOL(g_rd_tier_stats), zero, sizeof(zero)) == hipSuccess)
+    if (rc == SVT_HIP_OK && d->n_jobs && hipStreamSynchronize(ctx->stream) == hipSuccess &&
+        hipMemcpyFromSymbol(st, HIP_SYMBOL(g_rd_tier_stats), sizeof(st)) == hipSuccess && hipMemcpyToSymbol(HIP_SYMBOL(g_rd_tier_stats), zero, sizeof(zero)) == hipSuccess)
         fprintf(stderr, "rd_tier_stats tx_size %d jobs %u  row x col (0 general, 1 bounded, 2 clamp-free): %u %u %u | %u %u %u | %u %u %u  row tier from the quantizer: %u\n",
-                p.tx_size, d->n_jobs, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9]);
+                d->tx_size, d->n_jobs, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9]);
 #endif
     return rc;
 }
@@ -891,21 +885,20 @@ extern "C" int svt_hip_fullpel_pred(SvtHipContext *ctx, const void *ref, uint32_
                                     uint32_t pred_stride) {
     if (!ctx || !ref || !sb_best_mv || !pred || list > 1 || ref_idx > 3 || (bit_depth != 8 && bit_depth != 10) || !width || !height)
         return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_fullpel_pred: bad argument");
-    hipSetDevice(ctx->device);
-    const uint32_t w64 = (width + 63) / 64, h64 = (height + 63) / 64;
+    const uint32_t w64 = ceil_div(width, 64), h64 = ceil_div(height, 64);
     if (b64_row_start >= h64) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_fullpel_pred: b64_row_start %u >= %u", b64_row_start, h64);
     if (b64_row_count == 0 || b64_row_start + b64_row_count > h64) b64_row_count = h64 - b64_row_start;
     const dim3 g(w64, b64_row_count), blk(256);
     const size_t bpp = bit_depth == 8 ? 1 : 2;
     const int vec_ok = ((reinterpret_cast<uintptr_t>(pred) % (8 * bpp)) == 0 && pred_stride % 8 == 0) ? 1 : 0; // aligned 8-sample stores
-    if (bit_depth == 8)
-        hipLaunchKernelGGL(fullpel_pred_kernel<uint8_t>, g, blk, 0, ctx->stream, static_cast<const uint8_t *>(ref), ref_stride, (int)width, (int)height,
-                           sb_best_mv, (int)list, (int)ref_idx, w64, (int)b64_row_start, static_cast<uint8_t *>(pred), pred_stride, vec_ok);
-    else
-        hipLaunchKernelGGL(fullpel_pred_kernel<uint16_t>, g, blk, 0, ctx->stream, static_cast<const uint16_t *>(ref), ref_stride, (int)width, (int)height,
-                           sb_best_mv, (int)list, (int)ref_idx, w64, (int)b64_row_start, static_cast<uint16_t *>(pred), pred_stride, vec_ok);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
+    return enqueue_locked("svt_hip_fullpel_pred", ctx, [=] {
+        if (bit_depth == 8)
+            hipLaunchKernelGGL(fullpel_pred_kernel<uint8_t>, g, blk, 0, ctx->stream, static_cast<const uint8_t *>(ref), ref_stride, (int)width, (int)height,
+                               sb_best_mv, (int)list, (int)ref_idx, w64, (int)b64_row_start, static_cast<uint8_t *>(pred), pred_stride, vec_ok);
+        else
+            hipLaunchKernelGGL(fullpel_pred_kernel<uint16_t>, g, blk, 0, ctx->stream, static_cast<const uint16_t *>(ref), ref_stride, (int)width, (int)height,
+                               sb_best_mv, (int)list, (int)ref_idx, w64, (int)b64_row_start, static_cast<uint16_t *>(pred), pred_stride, vec_ok);
+    });
 }
 
 extern "C" int svt_hip_fullpel_pred_batch(SvtHipContext *ctx, uint32_t ref_stride, uint32_t width, uint32_t height, uint8_t bit_depth, uint32_t pred_stride,
@@ -913,7 +906,7 @@ extern "C" int svt_hip_fullpel_pred_batch(SvtHipContext *ctx, uint32_t ref_strid
     if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
     if (!jobs || n_jobs == 0 || n_jobs > SVT_HIP_PRED_MAX_JOBS || (bit_depth != 8 && bit_depth != 10) || !width || !height)
         return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_fullpel_pred_batch: bad argument (1..%d jobs)", SVT_HIP_PRED_MAX_JOBS);
-    const uint32_t w64 = (width + 63) / 64, h64 = (height + 63) / 64;
+    const uint32_t w64 = ceil_div(width, 64), h64 = ceil_div(height, 64);
     const size_t   bpp = bit_depth == 8 ? 1 : 2;
     PredBatch pb;
     memset(&pb, 0, sizeof(pb));
@@ -929,37 +922,40 @@ extern "C" int svt_hip_fullpel_pred_batch(SvtHipContext *ctx, uint32_t ref_strid
         vec_ok   = vec_ok && (reinterpret_cast<uintptr_t>(j.pred) % (8 * bpp)) == 0;
         pb.job[i] = j;
     }
-    hipSetDevice(ctx->device);
     const dim3 g(w64, rows_max, n_jobs), blk(256);
-    if (bit_depth == 8) hipLaunchKernelGGL(fullpel_pred_batch_kernel<uint8_t>, g, blk, 0, ctx->stream, pb, ref_stride, (int)width, (int)height, w64, pred_stride, vec_ok);
-    else hipLaunchKernelGGL(fullpel_pred_batch_kernel<uint16_t>, g, blk, 0, ctx->stream, pb, ref_stride, (int)width, (int)height, w64, pred_stride, vec_ok);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
+    return enqueue_locked("svt_hip_fullpel_pred_batch", ctx, [&] {
+        if (bit_depth == 8) hipLaunchKernelGGL(fullpel_pred_batch_kernel<uint8_t>, g, blk, 0, ctx->stream, pb, ref_stride, (int)width, (int)height, w64, pred_stride, vec_ok);
+        else hipLaunchKernelGGL(fullpel_pred_batch_kernel<uint16_t>, g, blk, 0, ctx->stream, pb, ref_stride, (int)width, (int)height, w64, pred_stride, vec_ok);
+    });
+}
+
+static int inv_txfm_check(const SvtHipInvTxBatchDesc *d) {
+    if (d->n_jobs == 0) return SVT_HIP_OK;
+    if ((d->bit_depth != 8 && d->bit_depth != 10) || (d->sample_bytes != 1 && d->sample_bytes != 2) || (d->bit_depth == 10 && d->sample_bytes != 2))
+        BAD("inverse batch: bit_depth %u with %u-byte samples", d->bit_depth, d->sample_bytes);
+    if (d->tx_size >= SVT_HIP_TX_SIZES_ALL) BAD("tx_size %u", d->tx_size);
+    if (!d->pred || !d->recon || !d->jobs || !d->dqcoeff) BAD("a pointer of the inverse batch is null");
     return SVT_HIP_OK;
 }
 
 extern "C" int svt_hip_inv_txfm_batch(SvtHipContext *ctx, const SvtHipInvTxBatchDesc *d) {
-    if (!ctx || !d) return SVT_HIP_ERR_BAD_PARAM;
+    return enqueue_batch("svt_hip_inv_txfm_batch", ctx, d, inv_txfm_check, &SvtHipInvTxBatchDesc::n_jobs, [=] {
+        const InvParams p = {*d};
+        if (d->bit_depth == 10) launch_inv<10, uint16_t>(ctx, p);
+        else if (d->sample_bytes == 1) launch_inv<8, uint8_t>(ctx, p);
+        else launch_inv<8, uint16_t>(ctx, p);
+    });
+}
+
+static int fwd_txfm_check(const SvtHipFwdTxBatchDesc *d) {
     if (d->n_jobs == 0) return SVT_HIP_OK;
-    if ((d->bit_depth != 8 && d->bit_depth != 10) || (d->sample_bytes != 1 && d->sample_bytes != 2) || (d->bit_depth == 10 && d->sample_bytes != 2))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "inverse batch: bit_depth %u with %u-byte samples", d->bit_depth, d->sample_bytes);
-    if (d->tx_size >= SVT_HIP_TX_SIZES_ALL) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "tx_size %u", d->tx_size);
-    if (!d->pred || !d->recon || !d->jobs || !d->dqcoeff) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "a pointer of the inverse batch is null");
-    hipSetDevice(ctx->device);
-    InvParams p;
-    p.d = *d;
-    if (d->bit_depth == 10) return launch_inv<10, uint16_t>(ctx, p);
-    return d->sample_bytes == 1 ? launch_inv<8, uint8_t>(ctx, p) : launch_inv<8, uint16_t>(ctx, p);
+    if (d->tx_size >= SVT_HIP_TX_SIZES_ALL) BAD("tx_size %u", d->tx_size);
+    if (!d->residual || !d->jobs || !d->coeff) BAD("a pointer of the forward batch is null");
+    return SVT_HIP_OK;
 }
 
 extern "C" int svt_hip_fwd_txfm_batch(SvtHipContext *ctx, const SvtHipFwdTxBatchDesc *d) {
-    if (!ctx || !d) return SVT_HIP_ERR_BAD_PARAM;
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    if (d->tx_size >= SVT_HIP_TX_SIZES_ALL) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "tx_size %u", d->tx_size);
-    if (!d->residual || !d->jobs || !d->coeff) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "a pointer of the forward batch is null");
-    hipSetDevice(ctx->device);
-    FwdParams p;
-    p.d = *d;
-    return launch_fwd(ctx, p);
+    return enqueue_batch("svt_hip_fwd_txfm_batch", ctx, d, fwd_txfm_check, &SvtHipFwdTxBatchDesc::n_jobs, [=] { launch_fwd(ctx, FwdParams{*d}); });
 }
 
 // The cosine table (constant memory of this device's copy of the code object) and the inverse scan orders, made once per

@@ -28,6 +28,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "../../include/svt_hip_dsp.h"
 #include "lvmap_core.h"
 #include "wave_ops.h"
@@ -441,34 +442,31 @@ extern "C" {
 
 size_t svt_hip_rdoq_desc_size(void) { return sizeof(SvtHipRdoqDesc); }
 
-int svt_hip_rdoq_batch(SvtHipContext *ctx, const SvtHipRdoqDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_rdoq_batch: null context or descriptor");
+static int rdoq_check(const SvtHipRdoqDesc *d) {
     if (d->tx_size >= SVT_HIP_TX_SIZES_ALL || d->plane_type > 1 || d->sharpness > 7)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_rdoq_batch: tx_size %u (below 19) / plane_type %u (0 or 1) / sharpness %u (0..7)", d->tx_size,
-                            d->plane_type, d->sharpness);
+        BAD("svt_hip_rdoq_batch: tx_size %u (below 19) / plane_type %u (0 or 1) / sharpness %u (0..7)", d->tx_size, d->plane_type, d->sharpness);
     if (!d->jobs || !d->tables || !d->quant_rows || !d->coeff || !d->qcoeff || !d->dqcoeff || !d->eob)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_rdoq_batch: a mandatory pointer (jobs, tables, quant_rows, coeff, qcoeff, dqcoeff, eob) is null");
-    if (d->n_quant_rows == 0) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_rdoq_batch: no quantizer rows");
-    if ((d->qcoeff_b || d->dqcoeff_b || d->eob_b) && !(d->qcoeff_b && d->dqcoeff_b && d->eob_b))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_rdoq_batch: the fallback needs qcoeff_b, dqcoeff_b and eob_b");
-    if (d->n_jobs == 0) return SVT_HIP_OK;
-    hipSetDevice(ctx->device);
-    RdoqParams p;
-    memset(&p, 0, sizeof(p));
-    p.d = *d;
-    p.iscan  = ctx->iscan_dev + (size_t)d->tx_size * 3 * 1024;
-    p.g      = lvmap_geom(d->tx_size);
-    p.rshift = d->sharpness > 2 ? d->sharpness : 2;
-    const uint32_t grid = lvmap_grid(p.g, d->n_jobs, ctx->lvmap_max_grid, p.n_packs);
-    std::lock_guard<std::mutex> lock(ctx->async_mu);
-    switch (p.g.n) {
-#define CASE(N) case N: hipLaunchKernelGGL(rdoq_kernel<N>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, p); break;
-        CASE(16) CASE(32) CASE(64) CASE(128) CASE(256) CASE(512) CASE(1024)
-#undef CASE
-    default: return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_rdoq_batch: %d coefficients", p.g.n);
-    }
-    SVT_HIP_CHECK(ctx, hipGetLastError());
+        BAD("svt_hip_rdoq_batch: a mandatory pointer (jobs, tables, quant_rows, coeff, qcoeff, dqcoeff, eob) is null");
+    if (d->n_quant_rows == 0) BAD("svt_hip_rdoq_batch: no quantizer rows");
+    if ((d->qcoeff_b || d->dqcoeff_b || d->eob_b) && !(d->qcoeff_b && d->dqcoeff_b && d->eob_b)) BAD("svt_hip_rdoq_batch: the fallback needs qcoeff_b, dqcoeff_b and eob_b");
     return SVT_HIP_OK;
+}
+
+int svt_hip_rdoq_batch(SvtHipContext *ctx, const SvtHipRdoqDesc *d) {
+    return enqueue_batch("svt_hip_rdoq_batch", ctx, d, rdoq_check, &SvtHipRdoqDesc::n_jobs, [=] {
+        RdoqParams p;
+        memset(&p, 0, sizeof(p));
+        p.d = *d;
+        p.iscan  = ctx->iscan_dev + (size_t)d->tx_size * 3 * 1024;
+        p.g      = lvmap_geom(d->tx_size);
+        p.rshift = d->sharpness > 2 ? d->sharpness : 2;
+        const uint32_t grid = lvmap_grid(p.g, d->n_jobs, ctx->lvmap_max_grid, p.n_packs);
+        switch (p.g.n) { // lvmap_geom gives one of these for every tx_size the check accepted
+#define CASE(N) case N: hipLaunchKernelGGL(rdoq_kernel<N>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, p); break;
+            CASE(16) CASE(32) CASE(64) CASE(128) CASE(256) CASE(512) CASE(1024)
+#undef CASE
+        }
+    });
 }
 
 } // extern "C"

@@ -21,6 +21,7 @@
 #include <string.h>
 #include <mutex>
 #include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "leaf_guard.h"
 #include "psy_energy.h"
 #include "wave_ops.h"
@@ -202,14 +203,23 @@ const char *bad_job(const SvtHipBlockJob &jb, bool pyramid) {
     return nullptr;
 }
 
-int ssim_enqueue(SvtHipContext *ctx, const SvtHipSsimBatchDesc *d, int unclamped) {
-    SsimParams p;
-    p.d         = *d;
-    p.unclamped = unclamped;
-    const uint32_t n = d->n_pyramids + d->n_jobs;
+// the launch alone, under the caller's lock: ctx->async_mu for the batch entry (batch_host.h), leaf_mutex() for the pointer-level entries
+void ssim_enqueue(SvtHipContext *ctx, const SvtHipSsimBatchDesc *d, int unclamped) {
+    const SsimParams p = {*d, unclamped};
+    const uint32_t   n = d->n_pyramids + d->n_jobs;
     if (d->bit_depth == 8) hipLaunchKernelGGL(ssim_kernel<uint8_t>, dim3(n), dim3(64), 0, ctx->stream, p);
     else hipLaunchKernelGGL(ssim_kernel<uint16_t>, dim3(n), dim3(64), 0, ctx->stream, p);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
+}
+
+int ssim_batch_check(const SvtHipSsimBatchDesc *d) {
+    if (d->bit_depth != 8 && d->bit_depth != 10) BAD("svt_hip_ssim_batch: bit_depth %u (8 or 10)", d->bit_depth);
+    if (d->n_jobs == 0 && d->n_pyramids == 0) return SVT_HIP_OK; // behind bit_depth, ahead of the rest
+    if (!d->src || !d->ref || (d->n_jobs && !d->jobs) || (d->n_pyramids && !d->pyramids))
+        BAD("svt_hip_ssim_batch: a mandatory pointer (src, ref, jobs, pyramids) is null");
+    if (!d->ssim && !d->ssim_dist) BAD("svt_hip_ssim_batch: no output (ssim, ssim_dist)");
+    if (!d->src_stride || !d->ref_stride) BAD("svt_hip_ssim_batch: zero stride");
+    if (!(d->psy_rd == d->psy_rd)) BAD("svt_hip_ssim_batch: psy_rd is NaN");
+    if ((uint64_t)d->pyramid_out_base + (uint64_t)SVT_HIP_PYRAMID_BLOCKS * d->n_pyramids > 0xFFFFFFFFull) BAD("svt_hip_ssim_batch: pyramid output slots beyond 2^32");
     return SVT_HIP_OK;
 }
 
@@ -229,18 +239,8 @@ int svt_hip_ssim_check_jobs(const SvtHipBlockJob *jobs, uint32_t n_jobs, int pyr
 }
 
 int svt_hip_ssim_batch(SvtHipContext *ctx, const SvtHipSsimBatchDesc *d) {
-    if (!ctx || !d) return svt_hip_fail(nullptr, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ssim_batch: null context or descriptor");
-    if (d->bit_depth != 8 && d->bit_depth != 10) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ssim_batch: bit_depth %u (8 or 10)", d->bit_depth);
-    if (d->n_jobs == 0 && d->n_pyramids == 0) return SVT_HIP_OK;
-    if (!d->src || !d->ref || (d->n_jobs && !d->jobs) || (d->n_pyramids && !d->pyramids))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ssim_batch: a mandatory pointer (src, ref, jobs, pyramids) is null");
-    if (!d->ssim && !d->ssim_dist) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ssim_batch: no output (ssim, ssim_dist)");
-    if (!d->src_stride || !d->ref_stride) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ssim_batch: zero stride");
-    if (!(d->psy_rd == d->psy_rd)) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ssim_batch: psy_rd is NaN");
-    if ((uint64_t)d->pyramid_out_base + (uint64_t)SVT_HIP_PYRAMID_BLOCKS * d->n_pyramids > 0xFFFFFFFFull)
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_ssim_batch: pyramid output slots beyond 2^32");
-    hipSetDevice(ctx->device);
-    return ssim_enqueue(ctx, d, 0);
+    return enqueue_batch("svt_hip_ssim_batch", ctx, d, ssim_batch_check, &SvtHipSsimBatchDesc::n_jobs, &SvtHipSsimBatchDesc::n_pyramids,
+                         [=] { ssim_enqueue(ctx, d, 0); });
 }
 
 } // extern "C"
@@ -276,7 +276,8 @@ SsimLeafOut leaf_ssim(const void *src, uint32_t sp, const void *ref, uint32_t rp
     memset(&d, 0, sizeof(d));
     d.bit_depth = (uint8_t)bit_depth; d.n_jobs = 1; d.src_stride = sp; d.ref_stride = rp; d.src = d_src; d.ref = d_ref;
     d.jobs = reinterpret_cast<const SvtHipBlockJob *>(d_job); d.psy_rd = psy_rd; d.ssim = &o->ssim; d.ssim_dist = reinterpret_cast<uint64_t *>(&o->dist);
-    if (ssim_enqueue(ctx, &d, unclamped) != SVT_HIP_OK) leaf_fail("%s", svt_hip_err_buf());
+    ssim_enqueue(ctx, &d, unclamped);
+    leaf_check(ctx, hipGetLastError(), "the ssim_kernel launch");
     SsimLeafOut out;
     leaf_check(ctx, hipMemcpyAsync(&out, d_out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
     leaf_check(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svt_hip_internal.h"
+#include "batch_host.h"
 #include "psy_energy.h"
 #include "wave_ops.h"
 #include "../../include/svt_hip_spy_rd.h"
@@ -619,32 +620,32 @@ uint32_t svt_hip_block_stats_jobs_per_wave(SvtHipContext *ctx, const SvtHipBlock
     return (d->satd && d->n_jobs < (uint32_t)ctx->num_cus * 8u * kJobsPerWave) ? 1 : kJobsPerWave;
 }
 
-int svt_hip_block_stats_batch(SvtHipContext *ctx, const SvtHipBlockStatsDesc *d) {
-    if (!ctx || !d) return SVT_HIP_ERR_BAD_PARAM;
+static int block_stats_check(const SvtHipBlockStatsDesc *d) {
     if (d->n_jobs == 0 && d->n_pyramids == 0) return SVT_HIP_OK;
-    if (d->bit_depth != 8 && d->bit_depth != 10) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "bit_depth %u", d->bit_depth);
-    if (!d->src || !d->ref || (d->n_jobs && !d->jobs) || (d->n_pyramids && !d->pyramids))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "a mandatory pointer of the block-stats batch is null");
-    if (d->satd && d->bit_depth != 8) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "hadamard_path works on 8-bit input (enc_mode_config.c:2186)");
-    if ((d->variance10 || d->var_sse10) && d->bit_depth != 10) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "variance10 is defined on 10-bit planes");
+    if (d->bit_depth != 8 && d->bit_depth != 10) BAD("bit_depth %u", d->bit_depth);
+    if (!d->src || !d->ref || (d->n_jobs && !d->jobs) || (d->n_pyramids && !d->pyramids)) BAD("a mandatory pointer of the block-stats batch is null");
+    if (d->satd && d->bit_depth != 8) BAD("hadamard_path works on 8-bit input (enc_mode_config.c:2186)");
+    if ((d->variance10 || d->var_sse10) && d->bit_depth != 10) BAD("variance10 is defined on 10-bit planes");
     if (d->facade_dist && (!d->pred_mode || !d->compound_type || d->temporal_layer_index > 5))
-        return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "facade_dist needs pred_mode, compound_type and temporal_layer_index <= 5 (got %u)", d->temporal_layer_index);
-    hipSetDevice(ctx->device);
-    StatsParams p;
-    p.d = *d;
-    // a wave works through its jobs one after the other: four per wave (shared matrix-core tiles for 8x8 blocks, fewer waves) only when that
-    // still gives every CU several waves -- a one-picture batch's edge jobs are otherwise the launch's critical path
-    // (hadamard_path batches only: the psy / facade batches finish a wave's four jobs side by side, one tile per lane -- measured 32 us with four
-    // jobs per wave, 42 us with one, on the 2160p batch's 3,720 edge jobs)
-    p.jpw = svt_hip_block_stats_jobs_per_wave(ctx, d);
-    const uint32_t flat = (d->n_jobs + p.jpw - 1) / p.jpw; // waves of the flat list
-    p.n_front = d->n_pyramids;
-    if (d->satd && d->n_pyramids) // (8-bit planes: checked above)
-        hipLaunchKernelGGL(block_stats4_kernel<uint8_t>, dim3(d->n_pyramids + (flat + 3) / 4), dim3(256), 0, ctx->stream, p);
-    else if (d->bit_depth == 8) hipLaunchKernelGGL(block_stats_kernel<uint8_t>, dim3(d->n_pyramids + flat), dim3(64), 0, ctx->stream, p);
-    else hipLaunchKernelGGL(block_stats_kernel<uint16_t>, dim3(d->n_pyramids + flat), dim3(64), 0, ctx->stream, p);
-    SVT_HIP_CHECK(ctx, hipGetLastError());
+        BAD("facade_dist needs pred_mode, compound_type and temporal_layer_index <= 5 (got %u)", d->temporal_layer_index);
     return SVT_HIP_OK;
+}
+
+int svt_hip_block_stats_batch(SvtHipContext *ctx, const SvtHipBlockStatsDesc *d) {
+    return enqueue_batch("svt_hip_block_stats_batch", ctx, d, block_stats_check, &SvtHipBlockStatsDesc::n_jobs, &SvtHipBlockStatsDesc::n_pyramids, [=] {
+        StatsParams p = {*d};
+        // a wave works through its jobs one after the other: four per wave (shared matrix-core tiles for 8x8 blocks, fewer waves) only when that
+        // still gives every CU several waves -- a one-picture batch's edge jobs are otherwise the launch's critical path
+        // (hadamard_path batches only: the psy / facade batches finish a wave's four jobs side by side, one tile per lane -- measured 32 us with four
+        // jobs per wave, 42 us with one, on the 2160p batch's 3,720 edge jobs)
+        p.jpw = svt_hip_block_stats_jobs_per_wave(ctx, d);
+        const uint32_t flat = ceil_div(d->n_jobs, p.jpw); // waves of the flat list
+        p.n_front = d->n_pyramids;
+        if (d->satd && d->n_pyramids) // (8-bit planes: the check saw to it)
+            hipLaunchKernelGGL(block_stats4_kernel<uint8_t>, dim3(d->n_pyramids + ceil_div(flat, 4)), dim3(256), 0, ctx->stream, p);
+        else if (d->bit_depth == 8) hipLaunchKernelGGL(block_stats_kernel<uint8_t>, dim3(d->n_pyramids + flat), dim3(64), 0, ctx->stream, p);
+        else hipLaunchKernelGGL(block_stats_kernel<uint16_t>, dim3(d->n_pyramids + flat), dim3(64), 0, ctx->stream, p);
+    });
 }
 
 } // extern "C"

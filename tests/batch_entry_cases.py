@@ -1,6 +1,7 @@
-"""A descriptor that its *_check_desc accepts, for every asynchronous batch entry of the prediction families (inter, intra, CfL, warp, masked compound /
-inter-intra, OBMC, the interpolation-filter search, palette), and the table of those entries.  The pointers are never dereferenced: the validations read
-the descriptor alone, so these serve the CPU tests of the refusals (tests/test_<family>.py) and of the entries' common contract (tests/test_batch_entries.py)."""
+"""A descriptor that its check accepts, for every asynchronous batch entry that runs through csrc/batch_host.h: the prediction families (inter, intra, CfL,
+warp, masked compound / inter-intra, OBMC, the interpolation-filter search, palette) in ENTRIES, and the older ones (RD, the transforms alone, the MD
+searches, PME, statistics, SSIM, rate, RDOQ) in OLDER.  The pointers are never dereferenced: the validations read the descriptor alone, so these serve the
+CPU tests of the refusals (tests/test_<family>.py) and of the entries' common contract (tests/test_batch_entries.py)."""
 from svt_av1_psyex_amd import abi, cfl, warp
 
 P = 0x1000
@@ -113,6 +114,57 @@ def good_palette_pred_desc():
                                search_jobs=64, search_results=64, search_status=64, jobs=64, status=64, color_map=64, map_bytes=4096)
 
 
+def good_rd_desc():
+    return abi.RdBatchDesc(bit_depth=10, quant_kind=0, tx_size=2, n_jobs=4, src_stride=256, pred_stride=256, src=P, pred=P, jobs=P, quant_rows=P, n_quant_rows=1,
+                           eob=P, satd=P, dist_coeff=P, three_quad_energy=P, sse=P)
+
+
+def good_inv_txfm_desc():
+    return abi.InvTxBatchDesc(bit_depth=10, sample_bytes=2, tx_size=2, n_jobs=4, pred_stride=256, recon_stride=256, pred=P, recon=P, jobs=P, dqcoeff=P)
+
+
+def good_fwd_txfm_desc():
+    return abi.FwdTxBatchDesc(tx_size=2, n_jobs=4, residual_stride=256, residual=P, jobs=P, coeff=P)
+
+
+MV_COST_NONE = 5  # SVT_HIP_MV_COST_NONE: no cost table is mandatory
+
+
+def good_md_fullpel_desc():
+    return abi.FullpelBatchDesc(n_jobs=4, src_stride=256, ref_stride=512, src=P, ref=P, ref_max_width=512, ref_max_height=448, jobs=P, mv_cost_type=MV_COST_NONE,
+                                best_cost=P, best_mv=P)
+
+
+def good_md_subpel_desc():
+    return abi.SubpelBatchDesc(n_jobs=4, src_stride=256, ref_stride=512, src=P, ref=P, jobs=P, forced_stop=0, iters_per_step=2, search_method=0,
+                               mv_cost_type=MV_COST_NONE, best_mv=P, besterr=P, distortion=P, sse=P)
+
+
+def good_pme_desc():
+    return abi.PmeBatchDesc(n_jobs=4, src_stride=256, ref_stride=512, src=P, ref=P, jobs=P, mv_cost_type=MV_COST_NONE, best_cost=P, best_mv=P)
+
+
+def good_block_stats_desc():
+    return abi.BlockStatsDesc(bit_depth=8, n_jobs=4, src_stride=256, ref_stride=256, src=P, ref=P, jobs=P, sad=P, n_pyramids=1, pyramids=P)
+
+
+def good_ssim_desc(n_pyramids=1):
+    return abi.SsimBatchDesc(bit_depth=8, n_jobs=4, src_stride=64, ref_stride=64, src=P, ref=P, jobs=P, ssim=P, ssim_dist=P, n_pyramids=n_pyramids,
+                             pyramids=P if n_pyramids else None)
+
+
+def good_coeff_rate_desc(n_groups=2):
+    d = abi.CoeffRateDesc(tx_size=2, plane_type=0, coeff_rate_est_lvl=1, mds_fast_coeff_est_level=1, n_jobs=4, jobs=P, tables=P, qcoeff=P, eob=P, bits=P)
+    if n_groups:
+        d.n_groups, d.lambda_, d.dist, d.rd_cost, d.group_start, d.best_job, d.best_cost = n_groups, 100, P, P, P, P, P
+    return d
+
+
+def good_rdoq_desc():
+    return abi.RdoqDesc(tx_size=2, plane_type=0, eob_th=255, eob_fast_th=255, n_jobs=4, lambda_=100, jobs=P, tables=P, quant_rows=P, n_quant_rows=1,
+                        coeff=P, qcoeff=P, dqcoeff=P, eob=P)
+
+
 # (the entry, a descriptor it accepts, the member whose zero means "nothing to do")
 ENTRIES = [("svt_hip_inter_pred_batch", good_inter_pred_desc, "n_jobs"),
            ("svt_hip_intra_pred_batch", good_intra_pred_desc, "n_jobs"),
@@ -132,3 +184,19 @@ ENTRIES = [("svt_hip_inter_pred_batch", good_inter_pred_desc, "n_jobs"),
            ("svt_hip_ifs_scatter_filters", good_ifs_scatter_desc, "n_patches"),
            ("svt_hip_palette_search_batch", good_palette_desc, "n_jobs"),
            ("svt_hip_palette_pred_batch", good_palette_pred_desc, "n_jobs")]
+
+# The older entries that run through the same sequence.  Their checks keep the order each had against "nothing to do":
+EMPTY_FIRST = "an empty batch is accepted whatever else the descriptor holds"
+BIT_DEPTH_THEN_EMPTY = "bit_depth is looked at, then an empty batch is accepted, then the rest"
+CHECK_FIRST = "everything is checked, then an empty batch is accepted"
+# (the entry, a descriptor it accepts, the members that are all zero when there is nothing to do, a mandatory pointer, the order)
+OLDER = [("svt_hip_rd_batch", good_rd_desc, ("n_jobs",), "src", EMPTY_FIRST),
+         ("svt_hip_inv_txfm_batch", good_inv_txfm_desc, ("n_jobs",), "dqcoeff", EMPTY_FIRST),
+         ("svt_hip_fwd_txfm_batch", good_fwd_txfm_desc, ("n_jobs",), "coeff", EMPTY_FIRST),
+         ("svt_hip_md_fullpel_batch", good_md_fullpel_desc, ("n_jobs",), "best_mv", EMPTY_FIRST),
+         ("svt_hip_md_subpel_batch", good_md_subpel_desc, ("n_jobs",), "besterr", EMPTY_FIRST),
+         ("svt_hip_pme_sad_batch", good_pme_desc, ("n_jobs",), "best_cost", EMPTY_FIRST),
+         ("svt_hip_block_stats_batch", good_block_stats_desc, ("n_jobs", "n_pyramids"), "ref", EMPTY_FIRST),
+         ("svt_hip_ssim_batch", good_ssim_desc, ("n_jobs", "n_pyramids"), "src", BIT_DEPTH_THEN_EMPTY),
+         ("svt_hip_coeff_rate_batch", good_coeff_rate_desc, ("n_jobs", "n_groups"), "tables", CHECK_FIRST),
+         ("svt_hip_rdoq_batch", good_rdoq_desc, ("n_jobs",), "quant_rows", CHECK_FIRST)]

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import coeff_rate_cases as cr
+from batch_entry_cases import good_coeff_rate_desc
 from svt_av1_psyex_amd import abi, api
 
 BAD_PARAM = 2
@@ -177,12 +178,8 @@ def test_struct_sizes_match_ctypes():
         assert getattr(abi.LvMapCoeffCost, name).offset == 4 * first and getattr(abi.LvMapCoeffCost, name).size == 4 * int(np.prod(shape)), name
 
 
-def _good_desc():
-    p = C.c_void_p(0x1000)  # never dereferenced: every case below fails validation before anything touches the device
-    return abi.CoeffRateDesc(tx_size=2, plane_type=0, coeff_rate_est_lvl=1, mds_fast_coeff_est_level=1, n_jobs=4, jobs=p, tables=p, qcoeff=p, eob=p, bits=p)
-
-
-BAD = ["null_ctx", "null_desc", "tx_size_19", "tx_size_255", "plane_type_2", "subres_3", "fast_0", "no_jobs", "no_tables", "no_qcoeff", "no_eob", "no_bits",
+# (null arguments: tests/test_batch_entries.py)
+BAD = ["tx_size_19", "tx_size_255", "plane_type_2", "subres_3", "fast_0", "no_jobs", "no_tables", "no_qcoeff", "no_eob", "no_bits",
        "unaligned_qcoeff", "rd_cost_without_dist", "groups_without_rd_cost", "group_count_without_rd_cost", "groups_without_group_start", "groups_without_best_job",
        "groups_without_best_cost"]
 
@@ -191,14 +188,8 @@ BAD = ["null_ctx", "null_desc", "tx_size_19", "tx_size_255", "plane_type_2", "su
 def test_bad_descriptor_is_rejected_without_a_gpu(bad):
     L = api.lib()
     ctx = C.create_string_buffer(4096)  # a stand-in handle: validation comes first, and a rejected call enqueues nothing
-    d = _good_desc()
+    d = good_coeff_rate_desc(n_groups=0)
     p = C.c_void_p(0x1000)
-    if bad == "null_ctx":
-        assert L.svt_hip_coeff_rate_batch(None, C.byref(d)) == BAD_PARAM
-        return
-    if bad == "null_desc":
-        assert L.svt_hip_coeff_rate_batch(ctx, None) == BAD_PARAM
-        return
     if bad.startswith("tx_size"):
         d.tx_size = int(bad.split("_")[-1])
     elif bad == "plane_type_2":

@@ -8,6 +8,7 @@ import pytest
 
 import coeff_rate_cases as cr
 import rdoq_cases as rq
+from batch_entry_cases import good_rdoq_desc
 from svt_av1_psyex_amd import abi, api
 
 BAD_PARAM = 2
@@ -138,13 +139,8 @@ def test_struct_sizes_match_ctypes():
     assert (abi.RDOQ_OPTIMISED, abi.RDOQ_EMPTY, abi.RDOQ_GATED, abi.RDOQ_UNDEFINED) == (rq.ST_OPTIMISED, rq.ST_EMPTY, rq.ST_GATED, rq.ST_UNDEFINED)
 
 
-def _good_desc():
-    p = C.c_void_p(0x1000)  # never dereferenced: every case below fails validation before anything touches the device
-    return abi.RdoqDesc(tx_size=2, plane_type=0, eob_th=255, eob_fast_th=255, n_jobs=4, lambda_=100, jobs=p, tables=p, quant_rows=p, n_quant_rows=1,
-                        coeff=p, qcoeff=p, dqcoeff=p, eob=p)
-
-
-BAD = ["null_ctx", "null_desc", "tx_size_19", "tx_size_255", "plane_type_2", "sharpness_8", "no_jobs", "no_tables", "no_quant_rows", "no_coeff", "no_qcoeff",
+# (null arguments: tests/test_batch_entries.py)
+BAD = ["tx_size_19", "tx_size_255", "plane_type_2", "sharpness_8", "no_jobs", "no_tables", "no_quant_rows", "no_coeff", "no_qcoeff",
        "no_dqcoeff", "no_eob", "zero_quant_rows", "fallback_without_qcoeff_b", "fallback_without_dqcoeff_b", "fallback_without_eob_b"]
 
 
@@ -152,14 +148,8 @@ BAD = ["null_ctx", "null_desc", "tx_size_19", "tx_size_255", "plane_type_2", "sh
 def test_bad_descriptor_is_rejected_without_a_gpu(bad):
     L = api.lib()
     ctx = C.create_string_buffer(4096)  # a stand-in handle: validation comes first, and a rejected call enqueues nothing
-    d = _good_desc()
+    d = good_rdoq_desc()
     p = C.c_void_p(0x1000)
-    if bad == "null_ctx":
-        assert L.svt_hip_rdoq_batch(None, C.byref(d)) == BAD_PARAM
-        return
-    if bad == "null_desc":
-        assert L.svt_hip_rdoq_batch(ctx, None) == BAD_PARAM
-        return
     if bad.startswith("tx_size"):
         d.tx_size = int(bad.split("_")[-1])
     elif bad == "plane_type_2":

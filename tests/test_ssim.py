@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import ssim_cases as sc
+from batch_entry_cases import good_ssim_desc
 from svt_av1_psyex_amd import abi, api, stats
 
 BAD_PARAM = 2
@@ -100,23 +101,13 @@ def test_descriptor_size_matches_ctypes():
     assert L.svt_hip_ssim_desc_size() == C.sizeof(abi.SsimBatchDesc)
 
 
-def _good_desc():
-    p = C.c_void_p(0x1000)  # never dereferenced: every case below fails validation before anything touches the device
-    return abi.SsimBatchDesc(bit_depth=8, n_jobs=4, src_stride=64, ref_stride=64, src=p, ref=p, jobs=p, ssim=p, ssim_dist=p)
-
-
-@pytest.mark.parametrize("bad", ["null_ctx", "null_desc", "bit_depth_9", "bit_depth_12", "no_src", "no_ref", "no_jobs", "no_pyramids", "no_outputs",
+# (null arguments: tests/test_batch_entries.py)
+@pytest.mark.parametrize("bad", ["bit_depth_9", "bit_depth_12", "no_src", "no_ref", "no_jobs", "no_pyramids", "no_outputs",
                                  "zero_stride", "nan_psy"])
 def test_bad_descriptor_is_rejected_without_a_gpu(bad):
     L = api.lib()
     ctx = C.create_string_buffer(64)  # a stand-in handle: validation comes first, and a rejected call enqueues nothing
-    d = _good_desc()
-    if bad == "null_ctx":
-        assert L.svt_hip_ssim_batch(None, C.byref(d)) == BAD_PARAM
-        return
-    if bad == "null_desc":
-        assert L.svt_hip_ssim_batch(ctx, None) == BAD_PARAM
-        return
+    d = good_ssim_desc(n_pyramids=0)
     if bad.startswith("bit_depth"):
         d.bit_depth = int(bad.split("_")[-1])
     elif bad == "no_src":
