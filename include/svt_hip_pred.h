@@ -20,7 +20,7 @@
  *
  * Out of scope: scaled references (svt_av1_convolve_2d_scale*, super-res / resize) (masked compound and inter-intra are svt_hip_mask.h, OBMC is svt_hip_obmc.h,
  * the choice of filter_x / filter_y by interpolation_filter_search is svt_hip_ifs.h, whose scatter entry writes the two bytes of these job records),
- * global-motion estimation (warped motion is svt_hip_warp.h), intra-BC's bilinear path, the split 8 + 2-bit reference layout (src_ptr_2b, svt_aom_pack_block), the light-PD
+ * global-motion estimation (its refinement and MV correspondences are svt_hip_gm.h; warped motion is svt_hip_warp.h), intra-BC's bilinear path, the split 8 + 2-bit reference layout (src_ptr_2b, svt_aom_pack_block), the light-PD
  * predictors, 12-bit, and pointer-level leaves for the convolve rtcd entries (one call per block; the batch is the boundary).
  *
  * Defined where the reference is not: the reference relies on the picture padding covering the clamped block plus the filter reach; the

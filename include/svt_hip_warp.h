@@ -56,9 +56,10 @@
  * block does not end inside src_samples.  What stays on the host, after the sync the candidate needs anyway: svt_aom_choose_best_av1_mv_pred
  * and the is_valid_mv_diff test.
  *
- * Out of scope: the masked second reference (av1_make_masked_warp_inter_predictor), global-motion estimation (global_me.c), 12-bit, 4:2:2 and
+ * Out of scope: the masked second reference (av1_make_masked_warp_inter_predictor), 12-bit, 4:2:2 and
  * 4:4:4 (ss_x != ss_y is computed as the formulas say but not pinned on the reference), scaled references, and pointer-level leaves for
- * svt_av1_warp_affine (one call per block; the batch is the boundary).
+ * svt_av1_warp_affine (one call per block; the batch is the boundary).  Global-motion estimation (global_me.c) is svt_hip_gm.h: its refinement warps
+ * whole pictures with the tile arithmetic of these entries (csrc/warp_core.h).
  */
 #ifndef SVT_HIP_WARP_H
 #define SVT_HIP_WARP_H

@@ -736,3 +736,38 @@ PALETTE_CAND_DTYPE = [("size", "u1"), ("first_index", "u1"), ("colors", "<u2", (
                       ("map_cost", "<i4"), ("index0_cost", "<i4"), ("size_cost", "<i4"), ("rate", "<i4")]
 PALETTE_RESULT_DTYPE = [("n_colors", "<u4"), ("n_cands", "<u4"), ("cands", PALETTE_CAND_DTYPE, (PALETTE_MAX_CANDS,))]
 PALETTE_PRED_JOB_DTYPE = [("search_index", "<u4"), ("cand_index", "<u4"), ("dst_offset", "<u4"), ("map_offset", "<u4")]
+
+
+# ---- include/svt_hip_gm.h ----
+GM_OK, GM_IDENTICAL, GM_UNDEFINED = 0, 1, 0xFF
+GM_IDENTITY, GM_TRANSLATION, GM_ROTZOOM, GM_AFFINE = 0, 1, 2, 3  # TransformationType
+GM_MAX_REFINEMENTS = 5
+GM_ROUND_ERRORS = 61
+GM_MAX_PAIRS = 8
+GM_MAX_JOBS = 65535
+GM_NO_FRAME_ERROR = 0x7FFFFFFFFFFFFFFF  # best_frame_error as the reference passes it (INT64_MAX)
+
+
+class GmRefineJob(C.Structure):  # SvtHipGmRefineJob
+    _fields_ = [("wmmat", C.c_int32 * 6), ("params_cost", C.c_int32), ("ref", C.c_uint8), ("wmtype", C.c_uint8), ("reserved", C.c_uint8 * 2),
+                ("best_frame_error", C.c_int64)]
+
+
+class GmRefineDesc(C.Structure):  # SvtHipGmRefineDesc
+    _fields_ = [("n_jobs", C.c_uint32), ("n_refs", C.c_uint8), ("n_refinements", C.c_uint8), ("chess_refn", C.c_uint8), ("rfn_early_exit", C.c_uint8),
+                ("src", WarpRef), ("refs", WarpRef * WARP_MAX_REFS), ("jobs", C.c_void_p), ("work", C.c_void_p), ("models", C.c_void_p),
+                ("best_error", C.c_void_p), ("pic_sad", C.c_void_p), ("status", C.c_void_p), ("round_error", C.c_void_p)]
+
+
+class GmPair(C.Structure):  # SvtHipGmPair
+    _fields_ = [("list", C.c_uint8), ("ref", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class GmCorrDesc(C.Structure):  # SvtHipGmCorrDesc
+    _fields_ = [("aligned_width", C.c_uint16), ("aligned_height", C.c_uint16), ("enable_me_8x8", C.c_uint8), ("enable_me_16x16", C.c_uint8),
+                ("max_cand", C.c_uint8), ("max_refs", C.c_uint8), ("max_l0", C.c_uint8), ("n_pu", C.c_uint8), ("method", C.c_uint8), ("shift", C.c_uint8),
+                ("n_pairs", C.c_uint32), ("cap", C.c_uint32), ("pairs", GmPair * GM_MAX_PAIRS), ("me", MeResults), ("corr", C.c_void_p), ("count", C.c_void_p),
+                ("sums", C.c_void_p)]
+
+
+GM_REFINE_JOB_DTYPE = [("wmmat", "<i4", (6,)), ("params_cost", "<i4"), ("ref", "u1"), ("wmtype", "u1"), ("reserved", "u1", (2,)), ("best_frame_error", "<i8")]
