@@ -77,6 +77,37 @@ def samples(t, bit_depth):
     return t.numel() * t.element_size() // (2 if bit_depth > 8 else 1)
 
 
+def sample_dtype(bit_depth):
+    """The numpy dtype of a sample of `bit_depth`."""
+    return np.uint16 if bit_depth > 8 else np.uint8
+
+
+def to_device(a, dtype=None):
+    """A host array, converted to `dtype` where one is given, as a flat byte tensor on the device (torch's stream; the array stays the caller's)."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).view(np.uint8).reshape(-1).copy()).cuda()
+
+
+def records_to_device(a, dtype):
+    """Records of `dtype` as a byte tensor; an empty list gives one zeroed record, so that a descriptor still gets a pointer."""
+    return to_device(a if len(a) else np.zeros(1, dtype), dtype)
+
+
+def filled(nbytes, fill):
+    """A byte tensor of at least one byte, every byte `fill` (torch's stream)."""
+    import torch
+    return torch.full((max(1, nbytes),), fill, dtype=torch.uint8, device="cuda")
+
+
+def to_host(t, dtype=np.uint8, shape=None, count=None):
+    """A byte tensor read back as `dtype`: the first `count` elements where given (the tensor may be longer: see filled), reshaped where given."""
+    a = t.cpu().numpy()
+    if count is not None:
+        a = a[:count * np.dtype(dtype).itemsize]
+    a = a.view(dtype)
+    return a if shape is None else a.reshape(shape)
+
+
 def config_from_preset(enc_mode, width, height, qp=35, temporal_layer_index=1, hierarchical_levels=4, sc_class1=0,
                        rtc_tune=0, fps=30):
     """SvtHipMeConfig of a CLI preset (restates svt_aom_sig_deriv_me, Codec/enc_mode_config.c:681-833)."""

@@ -53,25 +53,24 @@ def run_cfl_pred_hip(ctx, bit_depth, width, height, alphas, luma, dc, jobs, dst_
     samples between two bands of `guard` samples.  Returns {"dst": the two destinations with their bands, as they are after the call (they start
     as the byte `fill`), "status": [n + spare_jobs], "ac": [n + spare_jobs][H][W] int16 or None, "luma" / "dc": the inputs read back}."""
     import torch
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     sb = np.dtype(dt).itemsize
     n = len(jobs)
     luma = np.ascontiguousarray(luma, dtype=dt)
     dc = [np.ascontiguousarray(a, dtype=dt) for a in dc]
     lw, lh = (luma.shape[1], luma.shape[0]) if luma_size is None else luma_size
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-    t_luma, t_dc = dev(luma), [dev(a) for a in dc]
+    t_luma, t_dc = api.to_device(luma), [api.to_device(a) for a in dc]
     t_dst = [torch.full(((dst_samples + 2 * guard) * sb,), fill, dtype=torch.uint8, device="cuda") for _ in range(2)]
-    t_status = torch.full((max(1, n + spare_jobs),), fill, dtype=torch.uint8, device="cuda")
-    t_ac = torch.full((max(1, n + spare_jobs) * width * height * 2,), fill, dtype=torch.uint8, device="cuda") if want_ac else None
-    t_jobs = dev(np.ascontiguousarray(jobs, dtype=abi.CFL_PRED_JOB_DTYPE) if n else np.zeros(1, abi.CFL_PRED_JOB_DTYPE))
+    t_status = api.filled(n + spare_jobs, fill)
+    t_ac = api.filled(max(1, n + spare_jobs) * width * height * 2, fill) if want_ac else None
+    t_jobs = api.records_to_device(jobs, abi.CFL_PRED_JOB_DTYPE)
     torch.cuda.current_stream().synchronize()  # the fills and copies above ran on torch's stream; the context stream is not waited for
     run_cfl_pred_device(ctx, bit_depth, width, height, alphas, t_luma, luma.shape[1], lw, lh, t_dc, dc[0].shape[1], t_dst, dst_stride, slot_stride, t_jobs,
                         n, t_status, t_ac, dst_samples=dst_samples, dst_first=guard)
     ctx.sync()
-    return {"dst": [t.cpu().numpy().view(dt) for t in t_dst], "status": t_status.cpu().numpy()[:n + spare_jobs],
-            "ac": t_ac.cpu().numpy().view(np.int16).reshape(-1, height, width)[:n + spare_jobs] if want_ac else None,
-            "luma": t_luma.cpu().numpy().view(dt).reshape(luma.shape), "dc": [t.cpu().numpy().view(dt).reshape(a.shape) for t, a in zip(t_dc, dc)]}
+    return {"dst": [api.to_host(t, dt) for t in t_dst], "status": api.to_host(t_status, count=n + spare_jobs),
+            "ac": api.to_host(t_ac, np.int16, (-1, height, width))[:n + spare_jobs] if want_ac else None,
+            "luma": api.to_host(t_luma, dt, luma.shape), "dc": [api.to_host(t, dt, a.shape) for t, a in zip(t_dc, dc)]}
 
 
 PICK_OUT_DTYPES = {"best_rd": "<u8", "cfl_alpha_idx": "u1", "cfl_alpha_signs": "u1", "status": "u1"}
@@ -95,18 +94,16 @@ def run_pick_device(ctx, n_blocks, bits, dist, mode_bits, alpha_fac_bits, lam, i
 
 def download_pick(outs):
     """run_pick_device's outputs as numpy arrays (after ctx.sync())"""
-    return {name: t.cpu().numpy().view(PICK_OUT_DTYPES[name]) for name, t in outs.items()}
+    return {name: api.to_host(t, PICK_OUT_DTYPES[name]) for name, t in outs.items()}
 
 
 def run_pick_hip(ctx, bits, dist, mode_bits, alpha_fac_bits, lam, itr_th, n_mag=16, spare=0, fill=0):
     """svt_hip_cfl_pick_alpha_batch on host arrays: bits / dist uint64 [n][2][33], mode_bits int32 [n], alpha_fac_bits int32 [8][2][16]."""
-    import torch
-    dev = lambda a, dt: torch.from_numpy((np.ascontiguousarray(a, dt) if np.size(a) else np.zeros(1, dt)).view(np.uint8).reshape(-1).copy()).cuda()
     n = len(mode_bits)
     bits, dist = np.ascontiguousarray(bits, np.uint64), np.ascontiguousarray(dist, np.uint64)
     if bits.size != n * 2 * abi.CFL_SLOTS or dist.size != bits.size or np.asarray(alpha_fac_bits).size != 8 * 2 * 16:
         raise ValueError(f"{n} blocks: bits holds {bits.size}, dist {dist.size}, alpha_fac_bits {np.asarray(alpha_fac_bits).size}")
-    ins = [dev(bits, np.uint64), dev(dist, np.uint64), dev(mode_bits, np.int32), dev(alpha_fac_bits, np.int32)]  # held until the stream has run
+    ins = [api.records_to_device(a, dt) for a, dt in ((bits, np.uint64), (dist, np.uint64), (mode_bits, np.int32), (alpha_fac_bits, np.int32))]  # held until the stream has run
     outs = run_pick_device(ctx, n, *ins, lam, itr_th, n_mag, 1, spare, fill)
     ctx.sync()
     return download_pick(outs)

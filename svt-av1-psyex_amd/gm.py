@@ -41,11 +41,6 @@ def check_corr_desc(d):
     api.check_desc("svt_hip_gm_corr_check_desc", d)
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
 def run_gm_refine_device(ctx, src, refs, n_refinements, chess_refn, rfn_early_exit, jobs, n_jobs, with_round_error=True, spare=0, fill=0):
     """Enqueues svt_hip_gm_refine_batch on the context stream and returns (the outputs as device byte tensors by name -- "round_error" among them
     when asked for --, the scratch tensor, which must live until the batch is done), without waiting.  src: an abi.WarpRef, refs: a list of them;
@@ -54,7 +49,7 @@ def run_gm_refine_device(ctx, src, refs, n_refinements, chess_refn, rfn_early_ex
     sizes = {k: np.dtype(dt).itemsize for k, dt in REFINE_OUT_DTYPES.items()}
     if with_round_error:
         sizes["round_error"] = 8 * abi.GM_ROUND_ERRORS
-    outs = {k: torch.full((max(1, n_jobs + spare) * sz,), fill, dtype=torch.uint8, device="cuda") for k, sz in sizes.items()}
+    outs = {k: api.filled(max(1, n_jobs + spare) * sz, fill) for k, sz in sizes.items()}
     work = torch.empty((work_bytes(n_jobs),), dtype=torch.uint8, device="cuda")
     torch.cuda.current_stream().synchronize()  # the fills ran on torch's stream
     d = refine_desc(src, refs, n_refinements, chess_refn, rfn_early_exit, jobs.data_ptr(), n_jobs, work.data_ptr(),
@@ -68,17 +63,17 @@ def run_gm_refine_hip(ctx, src, planes, n_refinements, chess_refn, rfn_early_exi
     height); jobs: abi.GM_REFINE_JOB_DTYPE.  Returns the outputs by name, each [n + spare] (round_error [n + spare][61]), and "planes" / "src" read
     back."""
     n = len(jobs)
-    t_planes = [_dev(np.ascontiguousarray(p[0], dtype=np.uint8)) for p in [src] + list(planes)]
+    t_planes = [api.to_device(p[0], np.uint8) for p in [src] + list(planes)]
     refs = [plane_ref(t, p[0].shape[1], p[1], p[2], p[3], p[4], p[0].shape[0]) for t, p in zip(t_planes, [src] + list(planes))]
-    t_jobs = _dev(np.ascontiguousarray(jobs, dtype=abi.GM_REFINE_JOB_DTYPE) if n else np.zeros(1, abi.GM_REFINE_JOB_DTYPE))
+    t_jobs = api.records_to_device(jobs, abi.GM_REFINE_JOB_DTYPE)
     outs, work = run_gm_refine_device(ctx, refs[0], refs[1:], n_refinements, chess_refn, rfn_early_exit, t_jobs, n, with_round_error, spare, fill)
     ctx.sync()
     del work
-    out = {k: outs[k].cpu().numpy().view(np.dtype(dt)) for k, dt in REFINE_OUT_DTYPES.items()}
+    out = {k: api.to_host(outs[k], np.dtype(dt)) for k, dt in REFINE_OUT_DTYPES.items()}
     if with_round_error:
-        out["round_error"] = outs["round_error"].cpu().numpy().view("<i8").reshape(-1, abi.GM_ROUND_ERRORS)
-    out["src"] = t_planes[0].cpu().numpy().reshape(src[0].shape)
-    out["planes"] = [t.cpu().numpy().reshape(p[0].shape) for t, p in zip(t_planes[1:], planes)]
+        out["round_error"] = api.to_host(outs["round_error"], "<i8", (-1, abi.GM_ROUND_ERRORS))
+    out["src"] = api.to_host(t_planes[0], shape=src[0].shape)
+    out["planes"] = [api.to_host(t, shape=p[0].shape) for t, p in zip(t_planes[1:], planes)]
     return out
 
 
@@ -120,7 +115,7 @@ def run_gm_correspondence_hip(ctx, pic, method, shift, pairs, arrays, cap=None, 
     {"corr", "count" (uint32), "sums" (uint32)} as numpy arrays."""
     me, keep = abi.MeResults(), []
     for name in ME_ARRAYS:
-        keep.append(_dev(arrays[name]))
+        keep.append(api.to_device(arrays[name]))
         setattr(me, name, keep[-1].data_ptr())
     outs = run_gm_correspondence_device(ctx, pic, method, shift, pairs, me, cap, spare, fill)
     ctx.sync()

@@ -53,21 +53,16 @@ def run_scatter_device(ctx, patches, n_patches, results, result_status, n_result
     return d
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
 def run_ifs_hip(ctx, bit_depth, planes, src, jobs, fac_bits, params, dst_shape=None, dst_stride=None, mv_array=None, spare_jobs=0, fill=0, want_arrays=True):
     """svt_hip_ifs_batch on host arrays.  planes: a list of (padded plane [H][W], org_x, org_y); src: the source plane [H][W]; jobs: abi.IFS_JOB_DTYPE;
     fac_bits: int32 [16][3]; dst_shape: (rows, columns) of the destination plane or None for dst == NULL.  Every output starts as the byte `fill`.
     Returns {"results", "status", "rd", "sse", "dst"} as they are after the call (dst None without a destination)."""
     import torch
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
-    t_planes = [_dev(np.ascontiguousarray(p, dtype=dt)) for p, _, _ in planes]
+    t_planes = [api.to_device(p, dt) for p, _, _ in planes]
     refs = [plane_ref(t, p.shape[1], ox, oy, p.shape[1], p.shape[0]) for t, (p, ox, oy) in zip(t_planes, planes)]
-    t_src = _dev(np.ascontiguousarray(src, dtype=dt))
+    t_src = api.to_device(src, dt)
     t_dst = None
     if dst_shape is not None:
         rows, cols = dst_shape
@@ -77,16 +72,16 @@ def run_ifs_hip(ctx, bit_depth, planes, src, jobs, fac_bits, params, dst_shape=N
     full = lambda nbytes: torch.full((nbytes,), fill, dtype=torch.uint8, device="cuda")
     t_status, t_res = full(slots), full(slots * np.dtype(abi.IFS_RESULT_DTYPE).itemsize)
     t_rd, t_sse = (full(slots * 72), full(slots * 72)) if want_arrays else (None, None)
-    t_jobs = _dev(np.ascontiguousarray(jobs, dtype=abi.IFS_JOB_DTYPE) if n else np.zeros(1, abi.IFS_JOB_DTYPE))
-    t_fac = _dev(np.ascontiguousarray(fac_bits, dtype=np.int32))
-    t_mv = _dev(np.ascontiguousarray(mv_array, dtype=np.int16)) if mv_array is not None and len(mv_array) else None
+    t_jobs = api.records_to_device(jobs, abi.IFS_JOB_DTYPE)
+    t_fac = api.to_device(fac_bits, np.int32)
+    t_mv = api.to_device(mv_array, np.int16) if mv_array is not None and len(mv_array) else None
     torch.cuda.current_stream().synchronize()  # the fills and copies above ran on torch's stream; the context stream is not waited for
     run_ifs_device(ctx, bit_depth, refs, t_src, src.shape[1], t_jobs, n, t_fac, t_res, t_status, params, dst=t_dst, dst_stride=dst_stride or 0, mv_array=t_mv,
                    n_mvs=len(mv_array) if t_mv is not None else 0, rd=t_rd, sse=t_sse)
     ctx.sync()
-    out = {"results": t_res.cpu().numpy().view(abi.IFS_RESULT_DTYPE), "status": t_status.cpu().numpy(),
-           "dst": t_dst.cpu().numpy().view(dt).reshape(rows, dst_stride) if t_dst is not None else None}
-    out["rd"], out["sse"] = (t.cpu().numpy().view(np.uint64).reshape(slots, 9) if t is not None else None for t in (t_rd, t_sse))
+    out = {"results": api.to_host(t_res, abi.IFS_RESULT_DTYPE), "status": api.to_host(t_status),
+           "dst": api.to_host(t_dst, dt, (rows, dst_stride)) if t_dst is not None else None}
+    out["rd"], out["sse"] = (api.to_host(t, np.uint64, (slots, 9)) if t is not None else None for t in (t_rd, t_sse))
     return out
 
 
@@ -95,10 +90,10 @@ def run_scatter_hip(ctx, patches, results, result_status, records, filter_x_offs
     call, status [n_patches])."""
     import torch
     n = len(patches)
-    t_pat = _dev(np.ascontiguousarray(patches, dtype=abi.IFS_PATCH_DTYPE) if n else np.zeros(1, abi.IFS_PATCH_DTYPE))
-    t_res, t_rs, t_rec = _dev(np.ascontiguousarray(results, dtype=abi.IFS_RESULT_DTYPE)), _dev(np.ascontiguousarray(result_status, dtype=np.uint8)), _dev(records)
-    t_status = torch.full((max(1, n),), fill, dtype=torch.uint8, device="cuda")
+    t_pat = api.records_to_device(patches, abi.IFS_PATCH_DTYPE)
+    t_res, t_rs, t_rec = api.to_device(results, abi.IFS_RESULT_DTYPE), api.to_device(result_status, np.uint8), api.to_device(records)
+    t_status = api.filled(n, fill)
     torch.cuda.current_stream().synchronize()
     run_scatter_device(ctx, t_pat, n, t_res, t_rs, len(results), t_rec, len(records), records.dtype.itemsize, filter_x_offset, t_status)
     ctx.sync()
-    return t_rec.cpu().numpy().view(records.dtype), t_status.cpu().numpy()[:n]
+    return api.to_host(t_rec, records.dtype), api.to_host(t_status, count=n)

@@ -32,20 +32,19 @@ def run_intra_pred_hip(ctx, bit_depth, disable_edge_filter, nbr, jobs, dst_shape
     samples (default: columns).  Returns {"dst": [rows][dst_stride] as it is after the call (it starts as the byte `fill`), "status":
     [n + spare_jobs] (the spare slots start as `fill`), "nbr": the neighbour plane read back}."""
     import torch
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
     rows, cols = dst_shape
     dst_stride = cols if dst_stride is None else dst_stride
     nbr = np.ascontiguousarray(nbr, dtype=dt)
     width, height = (nbr.shape[1], nbr.shape[0]) if nbr_size is None else nbr_size
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-    t_nbr = dev(nbr)
+    t_nbr = api.to_device(nbr)
     t_dst = torch.full((rows * dst_stride * np.dtype(dt).itemsize,), fill, dtype=torch.uint8, device="cuda")
-    t_status = torch.full((max(1, n + spare_jobs),), fill, dtype=torch.uint8, device="cuda")
-    t_jobs = dev(np.ascontiguousarray(jobs, dtype=abi.INTRA_PRED_JOB_DTYPE) if n else np.zeros(1, abi.INTRA_PRED_JOB_DTYPE))
+    t_status = api.filled(n + spare_jobs, fill)
+    t_jobs = api.records_to_device(jobs, abi.INTRA_PRED_JOB_DTYPE)
     torch.cuda.current_stream().synchronize()  # the fills and copies above ran on torch's stream; the context stream is not waited for
     run_intra_pred_device(ctx, bit_depth, disable_edge_filter, t_nbr, nbr.shape[1], width, height, t_dst, dst_stride, t_jobs, n, t_status,
                           dst_samples=rows * dst_stride)
     ctx.sync()
-    return {"dst": t_dst.cpu().numpy().view(dt).reshape(rows, dst_stride), "status": t_status.cpu().numpy()[:n + spare_jobs],
-            "nbr": t_nbr.cpu().numpy().view(dt).reshape(nbr.shape)}
+    return {"dst": api.to_host(t_dst, dt, (rows, dst_stride)), "status": api.to_host(t_status, count=n + spare_jobs),
+            "nbr": api.to_host(t_nbr, dt, nbr.shape)}

@@ -70,16 +70,6 @@ def run_mask_search_device(ctx, bit_depth, mult, src, src_stride, pred0, pred0_s
     return d
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def _fill(nbytes, fill):
-    import torch
-    return torch.full((max(1, nbytes),), fill, dtype=torch.uint8, device="cuda")
-
-
 def run_masked_pred_hip(ctx, bit_depth, ss_x, ss_y, plane, planes, jobs, dst_shape, dst_stride=None, mv_array=None, results=None, mask_buf=None, spare_jobs=0,
                         fill=0):
     """svt_hip_masked_pred_batch on host arrays.  planes: a list of (padded plane, org_x, org_y); jobs: abi.MASKED_PRED_JOB_DTYPE; mask_buf: the bytes
@@ -87,62 +77,62 @@ def run_masked_pred_hip(ctx, bit_depth, ss_x, ss_y, plane, planes, jobs, dst_sha
     (dst and the spare status slots start as the byte `fill`)."""
     import torch
     from . import pred
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
     rows, cols = dst_shape
     dst_stride = cols if dst_stride is None else dst_stride
-    t_planes = [_dev(np.ascontiguousarray(p, dtype=dt)) for p, _, _ in planes]
+    t_planes = [api.to_device(p, dt) for p, _, _ in planes]
     refs = [pred.plane_ref(t, p.shape[1], ox, oy, p.shape[1], p.shape[0]) for t, (p, ox, oy) in zip(t_planes, planes)]
-    t_dst = _fill(rows * dst_stride * np.dtype(dt).itemsize, fill)
-    t_status = _fill(n + spare_jobs, fill)
-    t_jobs = _dev(np.ascontiguousarray(jobs, dtype=abi.MASKED_PRED_JOB_DTYPE) if n else np.zeros(1, abi.MASKED_PRED_JOB_DTYPE))
-    t_mv = _dev(np.ascontiguousarray(mv_array, dtype=np.int16)) if mv_array is not None and len(mv_array) else None
-    t_res = _dev(np.ascontiguousarray(results, dtype=abi.MASK_SEARCH_RESULT_DTYPE)) if results is not None and len(results) else None
-    t_mask = _dev(np.ascontiguousarray(mask_buf, dtype=np.uint8)) if mask_buf is not None else None
+    t_dst = api.filled(rows * dst_stride * np.dtype(dt).itemsize, fill)
+    t_status = api.filled(n + spare_jobs, fill)
+    t_jobs = api.records_to_device(jobs, abi.MASKED_PRED_JOB_DTYPE)
+    t_mv = api.to_device(mv_array, np.int16) if mv_array is not None and len(mv_array) else None
+    t_res = api.to_device(results, abi.MASK_SEARCH_RESULT_DTYPE) if results is not None and len(results) else None
+    t_mask = api.to_device(mask_buf, np.uint8) if mask_buf is not None else None
     torch.cuda.current_stream().synchronize()  # the fills and copies above ran on torch's stream; the context stream is not waited for
     run_masked_pred_device(ctx, bit_depth, ss_x, ss_y, plane, refs, t_dst, dst_stride, t_jobs, n, t_status, mv_array=t_mv,
                            n_mvs=len(mv_array) if t_mv is not None else 0, results=t_res, n_results=len(results) if t_res is not None else 0, mask_buf=t_mask,
                            dst_samples=rows * dst_stride)
     ctx.sync()
-    return {"dst": t_dst.cpu().numpy().view(dt).reshape(rows, dst_stride), "status": t_status.cpu().numpy()[:n + spare_jobs],
-            "mask_buf": t_mask.cpu().numpy() if t_mask is not None else None,
-            "planes": [t.cpu().numpy().view(dt).reshape(p.shape) for t, (p, _, _) in zip(t_planes, planes)]}
+    return {"dst": api.to_host(t_dst, dt, (rows, dst_stride)), "status": api.to_host(t_status, count=n + spare_jobs),
+            "mask_buf": api.to_host(t_mask) if t_mask is not None else None,
+            "planes": [api.to_host(t, dt, p.shape) for t, (p, _, _) in zip(t_planes, planes)]}
 
 
 def run_interintra_blend_hip(ctx, bit_depth, intra, inter, jobs, dst_shape=None, results=None, spare_jobs=0, fill=0):
     """svt_hip_interintra_blend_batch on host arrays.  intra / inter: planes [rows][stride]; dst_shape None: the destination is the inter plane
     itself (in place), else a plane of that shape filled with `fill`.  Returns {"dst", "status", "intra", "inter"} after the call."""
     import torch
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
-    t_intra, t_inter = _dev(np.ascontiguousarray(intra, dtype=dt)), _dev(np.ascontiguousarray(inter, dtype=dt))
+    t_intra, t_inter = api.to_device(intra, dt), api.to_device(inter, dt)
     in_place = dst_shape is None
     dst_shape = inter.shape if in_place else dst_shape
-    t_dst = t_inter if in_place else _fill(dst_shape[0] * dst_shape[1] * np.dtype(dt).itemsize, fill)
-    t_status = _fill(n + spare_jobs, fill)
-    t_jobs = _dev(np.ascontiguousarray(jobs, dtype=abi.INTERINTRA_JOB_DTYPE) if n else np.zeros(1, abi.INTERINTRA_JOB_DTYPE))
-    t_res = _dev(np.ascontiguousarray(results, dtype=abi.MASK_SEARCH_RESULT_DTYPE)) if results is not None and len(results) else None
+    t_dst = t_inter if in_place else api.filled(dst_shape[0] * dst_shape[1] * np.dtype(dt).itemsize, fill)
+    t_status = api.filled(n + spare_jobs, fill)
+    t_jobs = api.records_to_device(jobs, abi.INTERINTRA_JOB_DTYPE)
+    t_res = api.to_device(results, abi.MASK_SEARCH_RESULT_DTYPE) if results is not None and len(results) else None
     torch.cuda.current_stream().synchronize()
     run_interintra_blend_device(ctx, bit_depth, t_intra, intra.shape[1], t_inter, inter.shape[1], t_dst, dst_shape[1], t_jobs, n, t_status, results=t_res,
                                 n_results=len(results) if t_res is not None else 0)
     ctx.sync()
-    return {"dst": t_dst.cpu().numpy().view(dt).reshape(dst_shape), "status": t_status.cpu().numpy()[:n + spare_jobs],
-            "intra": t_intra.cpu().numpy().view(dt).reshape(intra.shape), "inter": t_inter.cpu().numpy().view(dt).reshape(inter.shape)}
+    return {"dst": api.to_host(t_dst, dt, dst_shape), "status": api.to_host(t_status, count=n + spare_jobs),
+            "intra": api.to_host(t_intra, dt, intra.shape), "inter": api.to_host(t_inter, dt, inter.shape)}
 
 
 def run_mask_search_hip(ctx, bit_depth, mult, src, pred0, pred1, intra, jobs, spare_jobs=0, fill=0):
     """svt_hip_mask_search_batch on host arrays.  src / pred0 / pred1 / intra: planes [rows][stride] (pred0 / intra may be None).  Returns
     {"results": abi.MASK_SEARCH_RESULT_DTYPE [n + spare_jobs] (they start as the byte `fill`), "status"} after the call."""
     import torch
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
-    up = lambda a: _dev(np.ascontiguousarray(a, dtype=dt)) if a is not None else None
+    up = lambda a: api.to_device(a, dt) if a is not None else None
     t_src, t_p0, t_p1, t_in = up(src), up(pred0), up(pred1), up(intra)
-    t_jobs = _dev(np.ascontiguousarray(jobs, dtype=abi.MASK_SEARCH_JOB_DTYPE) if n else np.zeros(1, abi.MASK_SEARCH_JOB_DTYPE))
+    t_jobs = api.records_to_device(jobs, abi.MASK_SEARCH_JOB_DTYPE)
     rec = np.dtype(abi.MASK_SEARCH_RESULT_DTYPE).itemsize
-    t_res, t_status = _fill((n + spare_jobs) * rec, fill), _fill(n + spare_jobs, fill)
+    t_res, t_status = api.filled((n + spare_jobs) * rec, fill), api.filled(n + spare_jobs, fill)
     torch.cuda.current_stream().synchronize()
     run_mask_search_device(ctx, bit_depth, mult, t_src, src.shape[1], t_p0, pred0.shape[1] if pred0 is not None else 0, t_p1, pred1.shape[1], t_in,
                            intra.shape[1] if intra is not None else 0, t_jobs, n, t_res, t_status)
     ctx.sync()
-    return {"results": t_res.cpu().numpy()[:(n + spare_jobs) * rec].view(abi.MASK_SEARCH_RESULT_DTYPE), "status": t_status.cpu().numpy()[:n + spare_jobs]}
+    return {"results": api.to_host(t_res, abi.MASK_SEARCH_RESULT_DTYPE, count=n + spare_jobs), "status": api.to_host(t_status, count=n + spare_jobs)}

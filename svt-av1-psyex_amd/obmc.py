@@ -70,71 +70,62 @@ def run_target_device(ctx, strip_bit_depth, blocks, n_blocks, jobs, n_jobs, abov
     return d
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def _records(a, dtype):
-    return _dev(np.ascontiguousarray(a, dtype=dtype) if len(a) else np.zeros(1, dtype))
-
-
 def run_neighbour_hip(ctx, bit_depth, ss_x, ss_y, plane, planes, blocks, jobs, above, left, mv_array=None, spare_jobs=0, fill=0):
     """svt_hip_obmc_neighbour_batch on host arrays.  planes: a list of (padded plane, org_x, org_y) of this plane; blocks: abi.OBMC_BLOCK_DTYPE;
     jobs: abi.OBMC_JOB_DTYPE; above / left: the strip buffers as they are before the call (1-D, uint8 or uint16).  Returns {"above", "left",
     "status" [n + spare_jobs] (the spare slots start as the byte `fill`), "planes": the reference planes read back}."""
     import torch
     from . import pred
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
-    t_planes = [_dev(np.ascontiguousarray(p, dtype=dt)) for p, _, _ in planes]
+    t_planes = [api.to_device(p, dt) for p, _, _ in planes]
     refs = [pred.plane_ref(t, p.shape[1], ox, oy, p.shape[1], p.shape[0]) for t, (p, ox, oy) in zip(t_planes, planes)]
-    t_above, t_left = _dev(np.ascontiguousarray(above, dtype=dt)), _dev(np.ascontiguousarray(left, dtype=dt))
-    t_status = torch.full((max(1, n + spare_jobs),), fill, dtype=torch.uint8, device="cuda")
-    t_blocks, t_jobs = _records(blocks, abi.OBMC_BLOCK_DTYPE), _records(jobs, abi.OBMC_JOB_DTYPE)
-    t_mv = _dev(np.ascontiguousarray(mv_array, dtype=np.int16)) if mv_array is not None and len(mv_array) else None
+    t_above, t_left = api.to_device(above, dt), api.to_device(left, dt)
+    t_status = api.filled(n + spare_jobs, fill)
+    t_blocks, t_jobs = api.records_to_device(blocks, abi.OBMC_BLOCK_DTYPE), api.records_to_device(jobs, abi.OBMC_JOB_DTYPE)
+    t_mv = api.to_device(mv_array, np.int16) if mv_array is not None and len(mv_array) else None
     torch.cuda.current_stream().synchronize()  # the fills and copies above ran on torch's stream; the context stream is not waited for
     run_neighbour_device(ctx, bit_depth, ss_x, ss_y, plane, refs, t_blocks, max(1, len(blocks)), t_jobs, n, t_above, t_left, t_status, mv_array=t_mv,
                          n_mvs=len(mv_array) if t_mv is not None else 0, strip_samples=len(above))
     ctx.sync()
-    return {"above": t_above.cpu().numpy().view(dt), "left": t_left.cpu().numpy().view(dt), "status": t_status.cpu().numpy()[:n + spare_jobs],
-            "planes": [t.cpu().numpy().view(dt).reshape(p.shape) for t, (p, _, _) in zip(t_planes, planes)]}
+    return {"above": api.to_host(t_above, dt), "left": api.to_host(t_left, dt), "status": api.to_host(t_status, count=n + spare_jobs),
+            "planes": [api.to_host(t, dt, p.shape) for t, (p, _, _) in zip(t_planes, planes)]}
 
 
 def run_blend_hip(ctx, bit_depth, ss_x, ss_y, plane, blocks, jobs, above, left, dst, spare_jobs=0, fill=0):
     """svt_hip_obmc_blend_batch on host arrays.  dst: the prediction plane [rows][stride] as it is before the call.  Returns {"dst", "status", "above",
     "left"} after the call."""
     import torch
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
-    t_above, t_left, t_dst = (_dev(np.ascontiguousarray(a, dtype=dt)) for a in (above, left, dst))
-    t_status = torch.full((max(1, n + spare_jobs),), fill, dtype=torch.uint8, device="cuda")
-    t_blocks, t_jobs = _records(blocks, abi.OBMC_BLOCK_DTYPE), _records(jobs, abi.OBMC_JOB_DTYPE)
+    t_above, t_left, t_dst = (api.to_device(a, dt) for a in (above, left, dst))
+    t_status = api.filled(n + spare_jobs, fill)
+    t_blocks, t_jobs = api.records_to_device(blocks, abi.OBMC_BLOCK_DTYPE), api.records_to_device(jobs, abi.OBMC_JOB_DTYPE)
     torch.cuda.current_stream().synchronize()
     run_blend_device(ctx, bit_depth, ss_x, ss_y, plane, t_blocks, max(1, len(blocks)), t_jobs, n, t_above, t_left, t_dst, dst.shape[1], t_status,
                      strip_samples=len(above), dst_samples=dst.size)
     ctx.sync()
-    return {"dst": t_dst.cpu().numpy().view(dt).reshape(dst.shape), "status": t_status.cpu().numpy()[:n + spare_jobs], "above": t_above.cpu().numpy().view(dt),
-            "left": t_left.cpu().numpy().view(dt)}
+    return {"dst": api.to_host(t_dst, dt, dst.shape), "status": api.to_host(t_status, count=n + spare_jobs), "above": api.to_host(t_above, dt),
+            "left": api.to_host(t_left, dt)}
 
 
 def run_target_hip(ctx, strip_bit_depth, blocks, jobs, above, left, src, out_values, spare_jobs=0, fill=0):
     """svt_hip_obmc_target_batch on host arrays.  src: the 8-bit source luma plane [rows][stride] from its sample (0, 0); wsrc and mask hold
     out_values int32 each and start as the byte `fill`.  Returns {"wsrc", "mask", "status"} after the call."""
     import torch
-    dt = np.uint16 if strip_bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(strip_bit_depth)
     n = len(jobs)
-    t_above, t_left = _dev(np.ascontiguousarray(above, dtype=dt)), _dev(np.ascontiguousarray(left, dtype=dt))
-    t_src = _dev(np.ascontiguousarray(src, dtype=np.uint8))
-    t_wsrc, t_mask = (torch.full((max(1, out_values) * 4,), fill, dtype=torch.uint8, device="cuda") for _ in range(2))
-    t_status = torch.full((max(1, n + spare_jobs),), fill, dtype=torch.uint8, device="cuda")
-    t_blocks, t_jobs = _records(blocks, abi.OBMC_BLOCK_DTYPE), _records(jobs, abi.OBMC_JOB_DTYPE)
+    t_above, t_left = api.to_device(above, dt), api.to_device(left, dt)
+    t_src = api.to_device(src, np.uint8)
+    t_wsrc, t_mask = (api.filled(max(1, out_values) * 4, fill) for _ in range(2))
+    t_status = api.filled(n + spare_jobs, fill)
+    t_blocks, t_jobs = api.records_to_device(blocks, abi.OBMC_BLOCK_DTYPE), api.records_to_device(jobs, abi.OBMC_JOB_DTYPE)
     torch.cuda.current_stream().synchronize()
     run_target_device(ctx, strip_bit_depth, t_blocks, max(1, len(blocks)), t_jobs, n, t_above, t_left, t_src, src.shape[1], t_wsrc, t_mask, t_status,
                       strip_samples=len(above), src_samples=src.size, out_values=out_values)
     ctx.sync()
-    return {"wsrc": t_wsrc.cpu().numpy().view(np.int32)[:out_values], "mask": t_mask.cpu().numpy().view(np.int32)[:out_values],
-            "status": t_status.cpu().numpy()[:n + spare_jobs]}
+    return {"wsrc": api.to_host(t_wsrc, np.int32, count=out_values), "mask": api.to_host(t_mask, np.int32, count=out_values),
+            "status": api.to_host(t_status, count=n + spare_jobs)}
 
 
 def check_search_desc(d):
@@ -164,13 +155,13 @@ def run_search_hip(ctx, params, ref, wsrc, mask, jobs, tables=None, spare_jobs=0
     column table) int32 arrays or None.  Returns {"best_mv" [n + spare_jobs][2], "results" abi.OBMC_SEARCH_RESULT_DTYPE, "status"}; all start as `fill`."""
     import torch
     n = len(jobs)
-    t_ref, t_wsrc, t_mask = _dev(np.ascontiguousarray(ref, dtype=np.uint8)), _dev(np.ascontiguousarray(wsrc, dtype=np.int32)), _dev(np.ascontiguousarray(mask, dtype=np.int32))
-    t_jobs = _records(jobs, abi.OBMC_SEARCH_JOB_DTYPE)
-    t_tab = [_dev(np.ascontiguousarray(t, dtype=np.int32)) for t in tables] if tables is not None else None
+    t_ref, t_wsrc, t_mask = api.to_device(ref, np.uint8), api.to_device(wsrc, np.int32), api.to_device(mask, np.int32)
+    t_jobs = api.records_to_device(jobs, abi.OBMC_SEARCH_JOB_DTYPE)
+    t_tab = [api.to_device(t, np.int32) for t in tables] if tables is not None else None
     rec = np.dtype(abi.OBMC_SEARCH_RESULT_DTYPE).itemsize
-    t_mv, t_res, t_st = (torch.full((max(1, (n + spare_jobs) * k),), fill, dtype=torch.uint8, device="cuda") for k in (4, rec, 1))
+    t_mv, t_res, t_st = (api.filled((n + spare_jobs) * k, fill) for k in (4, rec, 1))
     torch.cuda.current_stream().synchronize()
     run_search_device(ctx, params, t_ref, ref.shape[1], t_wsrc, t_mask, t_jobs, n, t_mv, t_res, t_st, tables=t_tab, ref_samples=ref.size, target_values=len(wsrc))
     ctx.sync()
-    return {"best_mv": t_mv.cpu().numpy()[:(n + spare_jobs) * 4].view(np.int16).reshape(-1, 2), "results": t_res.cpu().numpy()[:(n + spare_jobs) * rec].view(abi.OBMC_SEARCH_RESULT_DTYPE),
-            "status": t_st.cpu().numpy()[:n + spare_jobs]}
+    return {"best_mv": api.to_host(t_mv, np.int16, (-1, 2), count=(n + spare_jobs) * 2), "results": api.to_host(t_res, abi.OBMC_SEARCH_RESULT_DTYPE, count=n + spare_jobs),
+            "status": api.to_host(t_st, count=n + spare_jobs)}

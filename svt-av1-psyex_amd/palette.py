@@ -51,30 +51,25 @@ def run_pred_device(ctx, bit_depth, src, src_stride, dst, dst_stride, search_job
     return d
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
 def run_palette_hip(ctx, bit_depth, src, jobs, tables, params, map_bytes=0, pred_jobs=None, dst_samples=0, dst_stride=0, pred_map_bytes=0, spare_jobs=0, fill=0):
     """The search, and with pred_jobs the predictions right behind it on the stream, on host arrays.  src: the source plane [H][W]; jobs:
     abi.PALETTE_JOB_DTYPE; tables: (ycolor, ysize, ymode) int32 arrays; map_bytes: size of color_maps, 0 for none; pred_jobs:
     abi.PALETTE_PRED_JOB_DTYPE or None; pred_map_bytes: size of the predictions' color_map, 0 for none.  Every output starts as the byte `fill`.
     Returns {"results", "status", "color_maps", "dst", "pred_status", "pred_map"} as they are after the calls (None for what was not asked for)."""
     import torch
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
     slots = max(1, n + spare_jobs)
-    full = lambda nbytes: torch.full((max(1, nbytes),), fill, dtype=torch.uint8, device="cuda")
-    t_src = _dev(np.ascontiguousarray(src, dtype=dt))
-    t_jobs = _dev(np.ascontiguousarray(jobs, dtype=abi.PALETTE_JOB_DTYPE) if n else np.zeros(1, abi.PALETTE_JOB_DTYPE))
-    t_tab = [_dev(np.ascontiguousarray(t, dtype=np.int32)) for t in tables]
+    full = lambda nbytes: api.filled(nbytes, fill)
+    t_src = api.to_device(src, dt)
+    t_jobs = api.records_to_device(jobs, abi.PALETTE_JOB_DTYPE)
+    t_tab = [api.to_device(t, np.int32) for t in tables]
     t_res, t_status = full(slots * np.dtype(abi.PALETTE_RESULT_DTYPE).itemsize), full(slots)
     t_maps = full(map_bytes) if map_bytes else None
     out = {"color_maps": None, "dst": None, "pred_status": None, "pred_map": None}
     if pred_jobs is not None:
         m = len(pred_jobs)
-        t_pjobs = _dev(np.ascontiguousarray(pred_jobs, dtype=abi.PALETTE_PRED_JOB_DTYPE) if m else np.zeros(1, abi.PALETTE_PRED_JOB_DTYPE))
+        t_pjobs = api.records_to_device(pred_jobs, abi.PALETTE_PRED_JOB_DTYPE)
         t_dst, t_pst = full(dst_samples * np.dtype(dt).itemsize), full(m)
         t_pmap = full(pred_map_bytes) if pred_map_bytes else None
     torch.cuda.current_stream().synchronize()  # the fills and copies above ran on torch's stream; the context stream is not waited for
@@ -83,10 +78,10 @@ def run_palette_hip(ctx, bit_depth, src, jobs, tables, params, map_bytes=0, pred
         run_pred_device(ctx, bit_depth, t_src, src.shape[1], t_dst, dst_stride, t_jobs, t_res, t_status, max(1, n), t_pjobs, m, t_pst, color_map=t_pmap,
                         dst_samples=dst_samples, map_bytes=pred_map_bytes if pred_map_bytes else None)
     ctx.sync()
-    out["results"], out["status"] = t_res.cpu().numpy().view(abi.PALETTE_RESULT_DTYPE), t_status.cpu().numpy()
+    out["results"], out["status"] = api.to_host(t_res, abi.PALETTE_RESULT_DTYPE), api.to_host(t_status)
     if t_maps is not None:
-        out["color_maps"] = t_maps.cpu().numpy()
+        out["color_maps"] = api.to_host(t_maps)
     if pred_jobs is not None:
-        out["dst"], out["pred_status"] = t_dst.cpu().numpy().view(dt)[:dst_samples], t_pst.cpu().numpy()[:m]
-        out["pred_map"] = t_pmap.cpu().numpy() if t_pmap is not None else None
+        out["dst"], out["pred_status"] = api.to_host(t_dst, dt, count=dst_samples), api.to_host(t_pst, count=m)
+        out["pred_map"] = api.to_host(t_pmap) if t_pmap is not None else None
     return out

@@ -42,20 +42,19 @@ def run_inter_pred_hip(ctx, bit_depth, ss_x, ss_y, planes, jobs, dst_shape, dst_
     int16 [n][2] or None.  Returns {"dst": [rows][dst_stride] as it is after the call (it starts as the byte `fill`), "status": [n + spare_jobs]
     (the spare slots start as `fill`), "planes": the reference planes read back}."""
     import torch
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
     rows, cols = dst_shape
     dst_stride = cols if dst_stride is None else dst_stride
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-    t_planes = [dev(np.ascontiguousarray(p, dtype=dt)) for p, _, _ in planes]
+    t_planes = [api.to_device(p, dt) for p, _, _ in planes]
     refs = [plane_ref(t, p.shape[1], ox, oy, p.shape[1], p.shape[0]) for t, (p, ox, oy) in zip(t_planes, planes)]
     t_dst = torch.full((rows * dst_stride * np.dtype(dt).itemsize,), fill, dtype=torch.uint8, device="cuda")
-    t_status = torch.full((max(1, n + spare_jobs),), fill, dtype=torch.uint8, device="cuda")
-    t_jobs = dev(np.ascontiguousarray(jobs, dtype=abi.INTER_PRED_JOB_DTYPE) if n else np.zeros(1, abi.INTER_PRED_JOB_DTYPE))
-    t_mv = dev(np.ascontiguousarray(mv_array, dtype=np.int16)) if mv_array is not None and len(mv_array) else None
+    t_status = api.filled(n + spare_jobs, fill)
+    t_jobs = api.records_to_device(jobs, abi.INTER_PRED_JOB_DTYPE)
+    t_mv = api.to_device(mv_array, np.int16) if mv_array is not None and len(mv_array) else None
     torch.cuda.current_stream().synchronize()  # the fills and copies above ran on torch's stream; the context stream is not waited for
     run_inter_pred_device(ctx, bit_depth, ss_x, ss_y, refs, t_dst, dst_stride, t_jobs, n, t_status, mv_array=t_mv,
                           n_mvs=len(mv_array) if t_mv is not None else 0, dst_samples=rows * dst_stride)
     ctx.sync()
-    return {"dst": t_dst.cpu().numpy().view(dt).reshape(rows, dst_stride), "status": t_status.cpu().numpy()[:n + spare_jobs],
-            "planes": [t.cpu().numpy().view(dt).reshape(p.shape) for t, (p, _, _) in zip(t_planes, planes)]}
+    return {"dst": api.to_host(t_dst, dt, (rows, dst_stride)), "status": api.to_host(t_status, count=n + spare_jobs),
+            "planes": [api.to_host(t, dt, p.shape) for t, (p, _, _) in zip(t_planes, planes)]}

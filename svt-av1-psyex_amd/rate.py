@@ -55,7 +55,7 @@ RATE_OUT_DTYPES = {"bits": "<u8", "rd_cost": "<u8", "best_job": "<u4", "best_cos
 
 def download(outs):
     """run_rate_device's outputs as numpy arrays (after ctx.sync())"""
-    return {name: t.cpu().numpy().view(RATE_OUT_DTYPES[name]) for name, t in outs.items()}
+    return {name: api.to_host(t, RATE_OUT_DTYPES[name]) for name, t in outs.items()}
 
 
 def run_rate_hip(ctx, tables, tx_size, plane, jobs, qcoeff, eob, reduced_tx_set=0, coeff_rate_est_lvl=1, mds_fast_coeff_est_level=1,
@@ -63,8 +63,6 @@ def run_rate_hip(ctx, tables, tx_size, plane, jobs, qcoeff, eob, reduced_tx_set=
     """svt_hip_coeff_rate_batch on host arrays: jobs (abi.RATE_JOB_DTYPE), qcoeff int32 [n][min(W,32) * min(H,32)], eob uint16 [n], optional
     lam + dist (uint64 [n]) and group_start (uint32 [n_groups + 1]).  tables: upload_tables' tensor, or the host tables.  Returns
     {"bits", "rd_cost", "best_job", "best_cost"} (those asked for) as numpy arrays, each with its `spare_jobs` slots."""
-    import torch
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
     n = len(jobs)
     npk = min(abi.TX_W[tx_size], 32) * min(abi.TX_H[tx_size], 32) if tx_size < len(abi.TX_W) else 0
     qcoeff = np.ascontiguousarray(qcoeff, np.int32)
@@ -73,10 +71,10 @@ def run_rate_hip(ctx, tables, tx_size, plane, jobs, qcoeff, eob, reduced_tx_set=
     if not hasattr(tables, "data_ptr"):
         tables = upload_tables(tables)
     pad = np.zeros(1, np.uint64)  # an empty batch still passes pointers
-    t_jobs = dev(np.ascontiguousarray(jobs, dtype=abi.RATE_JOB_DTYPE) if n else pad)
-    t_q, t_eob = dev(qcoeff if n else pad), dev(np.ascontiguousarray(eob, np.uint16) if n else pad)
-    t_dist = dev(np.ascontiguousarray(dist, np.uint64)) if dist is not None else None
-    t_gs = dev(np.ascontiguousarray(group_start, np.uint32)) if group_start is not None else None
+    t_jobs = api.to_device(np.ascontiguousarray(jobs, dtype=abi.RATE_JOB_DTYPE) if n else pad)
+    t_q, t_eob = api.to_device(qcoeff if n else pad), api.to_device(np.ascontiguousarray(eob, np.uint16) if n else pad)
+    t_dist = api.to_device(dist, np.uint64) if dist is not None else None
+    t_gs = api.to_device(group_start, np.uint32) if group_start is not None else None
     outs = run_rate_device(ctx, tables, tx_size, plane, t_jobs, n, t_q, t_eob, reduced_tx_set, coeff_rate_est_lvl, mds_fast_coeff_est_level,
                            mds_subres_step, lam, t_dist, 1, t_gs, len(group_start) - 1 if group_start is not None else 0, spare_jobs, fill)
     ctx.sync()

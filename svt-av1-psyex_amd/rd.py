@@ -50,7 +50,7 @@ class Enqueued:
 
     def download(self):
         """the per-job outputs as numpy arrays [slots, elements per job] (after ctx.sync())"""
-        return {name: self.outs[name].cpu().numpy().view(dt).reshape(self.slots, k) for name, (dt, k) in self.shapes.items()}
+        return {name: api.to_host(self.outs[name], dt, (self.slots, k)) for name, (dt, k) in self.shapes.items()}
 
 
 def enqueue_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, want_recon=True, qmatrix=None, iqmatrix=None, outputs=None,
@@ -68,20 +68,19 @@ def enqueue_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True,
     npk = min(abi.TX_W[ts], 32) * min(abi.TX_H[ts], 32)
     n = len(jobs)
     slots = n + spare_jobs
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
-    t_src, t_pred, t_jobs, t_q = dev(src), dev(pred), dev(jobs), dev(quant_rows)
+    t_src, t_pred, t_jobs, t_q = (api.to_device(a) for a in (src, pred, jobs, quant_rows))
     shapes = {name: (np.dtype(dt), k) for name, dt, k in abi.RD_OUT_FIELDS if name != "cul_level" or name in outputs}
     shapes.update({name: (np.dtype(np.int32), npk) for name in ("coeff", "qcoeff", "dqcoeff") if name in outputs})
     outs = {name: torch.full((slots * k * dt.itemsize,), fill, dtype=torch.uint8, device="cuda") for name, (dt, k) in shapes.items()}
     want_recon = "recon" in outputs
-    t_rec = (t_pred.clone() if recon_init is None else dev(np.asarray(recon_init, pred.dtype).reshape(pred.shape))) if want_recon else None
+    t_rec = (t_pred.clone() if recon_init is None else api.to_device(np.asarray(recon_init, pred.dtype).reshape(pred.shape))) if want_recon else None
     d = abi.RdBatchDesc(n_jobs=n, src=t_src.data_ptr(), pred=t_pred.data_ptr(), recon=t_rec.data_ptr() if want_recon else None,
                         jobs=t_jobs.data_ptr(), quant_rows=t_q.data_ptr(), n_quant_rows=len(quant_rows), **desc_fields)
     for name, t in outs.items():
         setattr(d, name, t.data_ptr())
     keep = [t_src, t_pred, t_jobs, t_q]
     if qmatrix is not None:
-        t_qm, t_iqm = dev(np.asarray(qmatrix, np.uint8)), dev(np.asarray(iqmatrix, np.uint8))
+        t_qm, t_iqm = api.to_device(qmatrix, np.uint8), api.to_device(iqmatrix, np.uint8)
         d.qmatrix, d.iqmatrix = t_qm.data_ptr(), t_iqm.data_ptr()
         keep += [t_qm, t_iqm]
     torch.cuda.synchronize()
@@ -99,7 +98,7 @@ def run_hip(ctx, desc_fields, src, pred, jobs, quant_rows, want_coeffs=True, wan
     ctx.sync()
     res = run.download()
     if run.recon is not None:
-        res["recon"] = run.recon.cpu().numpy().view(pred.dtype).reshape(pred.shape)
+        res["recon"] = api.to_host(run.recon, pred.dtype, pred.shape)
     return res
 
 
@@ -109,15 +108,14 @@ def run_fwd_hip(ctx, tx_size, residual, jobs, spare_jobs=0, fill=0):
     import torch
     residual = np.ascontiguousarray(residual, np.int16)
     n, wh = len(jobs), abi.TX_W[tx_size] * abi.TX_H[tx_size]
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
-    t_res, t_jobs = dev(residual), dev(jobs)
+    t_res, t_jobs = api.to_device(residual), api.to_device(jobs)
     t_co = torch.full(((n + spare_jobs) * wh * 4,), fill, dtype=torch.uint8, device="cuda")
     d = abi.FwdTxBatchDesc(tx_size=tx_size, n_jobs=n, residual_stride=residual.shape[1], residual=t_res.data_ptr(), jobs=t_jobs.data_ptr(),
                            coeff=t_co.data_ptr())
     torch.cuda.synchronize()
     ctx.check(api.lib().svt_hip_fwd_txfm_batch(ctx._h, C.byref(d)), "svt_hip_fwd_txfm_batch")
     ctx.sync()
-    return t_co.cpu().numpy().view(np.int32).reshape(n + spare_jobs, wh)
+    return api.to_host(t_co, np.int32, (n + spare_jobs, wh))
 
 
 def run_inv_hip(ctx, bit_depth, tx_size, pred, jobs, dqcoeff, recon=None):
@@ -125,13 +123,12 @@ def run_inv_hip(ctx, bit_depth, tx_size, pred, jobs, dqcoeff, recon=None):
     own row stride; recon = None runs in place (the recon plane IS the prediction plane).  Returns the recon plane."""
     import torch
     pred = np.ascontiguousarray(pred)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-    t_pred, t_co, t_jobs = dev(pred), dev(np.ascontiguousarray(dqcoeff, np.int32)), dev(jobs)
+    t_pred, t_co, t_jobs = api.to_device(pred), api.to_device(dqcoeff, np.int32), api.to_device(jobs)
     out = pred if recon is None else np.ascontiguousarray(recon, pred.dtype)
-    t_rec = t_pred if recon is None else dev(out)
+    t_rec = t_pred if recon is None else api.to_device(out)
     d = abi.InvTxBatchDesc(bit_depth=bit_depth, sample_bytes=pred.dtype.itemsize, tx_size=tx_size, n_jobs=len(jobs), pred_stride=pred.shape[1],
                            recon_stride=out.shape[1], pred=t_pred.data_ptr(), recon=t_rec.data_ptr(), jobs=t_jobs.data_ptr(), dqcoeff=t_co.data_ptr())
     torch.cuda.synchronize()
     ctx.check(api.lib().svt_hip_inv_txfm_batch(ctx._h, C.byref(d)), "svt_hip_inv_txfm_batch")
     ctx.sync()
-    return t_rec.cpu().numpy().view(pred.dtype).reshape(out.shape)
+    return api.to_host(t_rec, pred.dtype, out.shape)

@@ -39,7 +39,7 @@ def run_rdoq_device(ctx, tables, tx_size, plane, jobs, n_jobs, quant_rows, n_qua
 
 def download(outs):
     """run_rdoq_device's outputs as numpy arrays (after ctx.sync())"""
-    return {name: t.cpu().numpy().view(RDOQ_OUT_DTYPES[name]) for name, t in outs.items()}
+    return {name: api.to_host(t, RDOQ_OUT_DTYPES[name]) for name, t in outs.items()}
 
 
 def run_rdoq_hip(ctx, tables, tx_size, plane, jobs, quant_rows, coeff, qcoeff, dqcoeff, eob, lam, iqmatrix=None, fallback=None, spare_jobs=0, fill=0,
@@ -48,36 +48,35 @@ def run_rdoq_hip(ctx, tables, tx_size, plane, jobs, quant_rows, coeff, qcoeff, d
     [n][min(W,32) * min(H,32)], eob uint16 [n]; fallback = (qcoeff_b, dqcoeff_b, eob_b) or None; controls: CONTROLS.  tables: rate.upload_tables'
     tensor, or the host tables.  Returns {"coeff", "qcoeff", "dqcoeff", "eob"} as they are after the call plus the optional outputs, every array
     with its `spare_jobs` slots (the inputs' spare slots start as `fill`)."""
-    import torch
     unknown = set(controls) - set(CONTROLS)
     if unknown:
         raise ValueError(f"unknown RDOQ controls {sorted(unknown)}")
     n = len(jobs)
     npk = min(abi.TX_W[tx_size], 32) * min(abi.TX_H[tx_size], 32) if tx_size < len(abi.TX_W) else 0
 
-    def dev(a, dtype, per_job):
+    def padded(a, dtype, per_job):
         a = np.ascontiguousarray(a, dtype).reshape(-1)
         if a.size != n * per_job:
             raise ValueError(f"{n} jobs of {per_job} elements: an array holds {a.size}")
-        t = torch.full((max(1, (n + spare_jobs) * per_job) * a.itemsize,), fill, dtype=torch.uint8, device="cuda")  # an empty batch still passes pointers
-        t[:a.nbytes] = torch.from_numpy(a.view(np.uint8).copy()).cuda()
+        t = api.filled(max(1, (n + spare_jobs) * per_job) * a.itemsize, fill)  # an empty batch still passes pointers
+        t[:a.nbytes] = api.to_device(a)
         return t
     if not hasattr(tables, "data_ptr"):
         tables = rate.upload_tables(tables)
     pad = np.zeros(1, np.uint64)
-    t_jobs = torch.from_numpy(np.ascontiguousarray(np.ascontiguousarray(jobs, dtype=abi.RDOQ_JOB_DTYPE) if n else pad).view(np.uint8).reshape(-1).copy()).cuda()
-    t_rows = torch.from_numpy(np.ascontiguousarray(quant_rows, dtype=abi.QUANT_ROW_DTYPE).view(np.uint8).reshape(-1).copy()).cuda()
-    t_iqm = torch.from_numpy(np.ascontiguousarray(iqmatrix, np.uint8).copy()).cuda() if iqmatrix is not None else None
-    t_c, t_q, t_dq, t_eob = dev(coeff, np.int32, npk), dev(qcoeff, np.int32, npk), dev(dqcoeff, np.int32, npk), dev(eob, np.uint16, 1)
-    t_fb = (dev(fallback[0], np.int32, npk), dev(fallback[1], np.int32, npk), dev(fallback[2], np.uint16, 1)) if fallback is not None else None
+    t_jobs = api.to_device(np.ascontiguousarray(jobs, dtype=abi.RDOQ_JOB_DTYPE) if n else pad)
+    t_rows = api.to_device(quant_rows, abi.QUANT_ROW_DTYPE)
+    t_iqm = api.to_device(iqmatrix, np.uint8) if iqmatrix is not None else None
+    t_c, t_q, t_dq, t_eob = padded(coeff, np.int32, npk), padded(qcoeff, np.int32, npk), padded(dqcoeff, np.int32, npk), padded(eob, np.uint16, 1)
+    t_fb = (padded(fallback[0], np.int32, npk), padded(fallback[1], np.int32, npk), padded(fallback[2], np.uint16, 1)) if fallback is not None else None
     outs = run_rdoq_device(ctx, tables, tx_size, plane, t_jobs, n, t_rows, len(quant_rows), t_c, t_q, t_dq, t_eob, lam, iqmatrix=t_iqm, fallback=t_fb,
                            outputs=outputs, spare_jobs=spare_jobs, fill=fill, **controls)
     ctx.sync()
     res = download(outs)
     slots = n + spare_jobs
     for name, t in (("coeff", t_c), ("qcoeff", t_q), ("dqcoeff", t_dq)):
-        res[name] = t.cpu().numpy().view(np.int32)[:slots * npk].reshape(slots, npk)
-    res["eob"] = t_eob.cpu().numpy().view(np.uint16)[:slots]
+        res[name] = api.to_host(t, np.int32, (slots, npk), count=slots * npk)
+    res["eob"] = api.to_host(t_eob, np.uint16, count=slots)
     if "dist_coeff" in res:
         res["dist_coeff"] = res["dist_coeff"].reshape(-1, 2)
     return res

@@ -55,7 +55,7 @@ def run_hip(ctx, src, ref, jobs, bit_depth, satd=True, psy_rd=None, facade=None,
     import torch
     from . import api
     L = api.lib()
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
+    dev = api.to_device
     n_plain = len(jobs)
     n = n_plain + (abi.PYRAMID_BLOCKS * len(pyramids) if pyramids is not None else 0)
     inputs = [src, ref, jobs if n_plain else np.zeros(1, abi.BLOCK_JOB_DTYPE)]
@@ -86,13 +86,13 @@ def run_hip(ctx, src, ref, jobs, bit_depth, satd=True, psy_rd=None, facade=None,
     rc = L.svt_hip_block_stats_batch(ctx._h, C.byref(d))
     ctx.check(rc, "svt_hip_block_stats_batch")
     ctx.sync()
-    res = {name: outs[name].cpu().numpy().view(dt) for name, dt in fields}
+    res = {name: api.to_host(outs[name], dt) for name, dt in fields}
     if fill is not None:
         for name in res:
             assert (res[name][n:].view(np.uint8) == fill).all(), f"{name}: a slot past the batch's {n} was written"
             res[name] = res[name][:n]
         for a, t in zip(inputs, [t_src, t_ref, t_jobs] + ([t_pyr] if len(inputs) == 4 else [])):
-            assert np.array_equal(t.cpu().numpy(), np.ascontiguousarray(a).view(np.uint8).reshape(-1)), "an input buffer of the batch was written"
+            assert np.array_equal(api.to_host(t), np.ascontiguousarray(a).view(np.uint8).reshape(-1)), "an input buffer of the batch was written"
     if outputs is None and not satd:
         res.pop("satd")
     return res
@@ -127,7 +127,7 @@ def run_ssim_hip(ctx, src, ref, jobs, bit_depth, psy_rd=None, pyramids=None, spa
         if pyramids is not None:
             check_ssim_jobs(pyramids, pyramids=True)
     (src, src_stride), (ref, ref_stride) = (a if isinstance(a, tuple) else (a, a.shape[1]) for a in (src, ref))
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
+    dev = api.to_device
     n_plain, n_pyr = len(jobs), (len(pyramids) if pyramids is not None else 0)
     out_base = n_plain if out_base is None else out_base
     assert out_base >= n_plain
@@ -150,10 +150,10 @@ def run_ssim_hip(ctx, src, ref, jobs, bit_depth, psy_rd=None, pyramids=None, spa
     torch.cuda.synchronize()
     ctx.check(L.svt_hip_ssim_batch(ctx._h, C.byref(d)), "svt_hip_ssim_batch")
     ctx.sync()
-    res = {name: outs[name].cpu().numpy().view(dt) for name, dt in abi.SSIM_OUT_FIELDS}
+    res = {name: api.to_host(outs[name], dt) for name, dt in abi.SSIM_OUT_FIELDS}
     if fill is not None:
         for name in res:
             assert (res[name][n:].view(np.uint8) == fill).all(), f"{name}: a slot past the batch's {n} was written"
         for a, t in zip(inputs, t_in):
-            assert np.array_equal(t.cpu().numpy(), np.ascontiguousarray(a).view(np.uint8).reshape(-1)), "an input buffer of the batch was written"
+            assert np.array_equal(api.to_host(t), np.ascontiguousarray(a).view(np.uint8).reshape(-1)), "an input buffer of the batch was written"
     return {name: res[name][:n] for name in res}

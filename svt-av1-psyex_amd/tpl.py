@@ -53,8 +53,7 @@ def check_desc(d):
 
 def upload_case(case):
     """Device copies of a case's inputs and outputs (torch uint8 tensors), keyed like the case."""
-    import torch
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    dev = api.to_device
     t = dict(cur=dev(case["cur"]), recon=dev(case["recon"]), tpl_stats=dev(case["tpl_stats"]), tpl_src_stats=dev(case["tpl_src_stats"]),
              refs={k: (dev(r["src"]), dev(r["recon"])) for k, r in case["refs"].items()})
     me = case["me"]

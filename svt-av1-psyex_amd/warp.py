@@ -53,33 +53,28 @@ def run_warp_model_device(ctx, jobs, n_jobs, models, status, shut_approx=0, lowe
     return d
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
 def run_warp_pred_hip(ctx, bit_depth, ss_x, ss_y, planes, jobs, dst_shape, dst_stride=None, models=None, spare_jobs=0, fill=0):
     """svt_hip_warp_pred_batch on host arrays.  planes: a list of (padded plane [rows][stride] uint8 / uint16, org_x, org_y, picture width, picture
     height); jobs: abi.WARP_PRED_JOB_DTYPE; dst_shape: (rows, columns) of the destination plane, dst_stride its pitch in samples (default: columns);
     models: abi.WARP_MODEL_DTYPE records or None.  Returns {"dst": [rows][dst_stride] as it is after the call (it starts as the byte `fill`), "status":
     [n + spare_jobs] (the spare slots start as `fill`), "planes": the reference planes read back}."""
     import torch
-    dt = np.uint16 if bit_depth > 8 else np.uint8
+    dt = api.sample_dtype(bit_depth)
     n = len(jobs)
     rows, cols = dst_shape
     dst_stride = cols if dst_stride is None else dst_stride
-    t_planes = [_dev(np.ascontiguousarray(p[0], dtype=dt)) for p in planes]
+    t_planes = [api.to_device(p[0], dt) for p in planes]
     refs = [plane_ref(t, p.shape[1], ox, oy, pw, ph, p.shape[0]) for t, (p, ox, oy, pw, ph) in zip(t_planes, planes)]
     t_dst = torch.full((rows * dst_stride * np.dtype(dt).itemsize,), fill, dtype=torch.uint8, device="cuda")
-    t_status = torch.full((max(1, n + spare_jobs),), fill, dtype=torch.uint8, device="cuda")
-    t_jobs = _dev(np.ascontiguousarray(jobs, dtype=abi.WARP_PRED_JOB_DTYPE) if n else np.zeros(1, abi.WARP_PRED_JOB_DTYPE))
-    t_models = _dev(np.ascontiguousarray(models, dtype=abi.WARP_MODEL_DTYPE)) if models is not None and len(models) else None
+    t_status = api.filled(n + spare_jobs, fill)
+    t_jobs = api.records_to_device(jobs, abi.WARP_PRED_JOB_DTYPE)
+    t_models = api.to_device(models, abi.WARP_MODEL_DTYPE) if models is not None and len(models) else None
     torch.cuda.current_stream().synchronize()  # the fills and copies above ran on torch's stream; the context stream is not waited for
     run_warp_pred_device(ctx, bit_depth, ss_x, ss_y, refs, t_dst, dst_stride, t_jobs, n, t_status, models=t_models,
                          n_models=len(models) if t_models is not None else 0, dst_samples=rows * dst_stride)
     ctx.sync()
-    return {"dst": t_dst.cpu().numpy().view(dt).reshape(rows, dst_stride), "status": t_status.cpu().numpy()[:n + spare_jobs],
-            "planes": [t.cpu().numpy().view(dt).reshape(p[0].shape) for t, p in zip(t_planes, planes)]}
+    return {"dst": api.to_host(t_dst, dt, (rows, dst_stride)), "status": api.to_host(t_status, count=n + spare_jobs),
+            "planes": [api.to_host(t, dt, p[0].shape) for t, p in zip(t_planes, planes)]}
 
 
 def run_warp_model_hip(ctx, jobs, shut_approx=0, lower_band_th=0, upper_band_th=0, mv_array=None, spare_jobs=0, fill=0):
@@ -88,14 +83,14 @@ def run_warp_model_hip(ctx, jobs, shut_approx=0, lower_band_th=0, upper_band_th=
     import torch
     n = len(jobs)
     size = np.dtype(abi.WARP_MODEL_DTYPE).itemsize
-    t_jobs = _dev(np.ascontiguousarray(jobs, dtype=abi.WARP_MODEL_JOB_DTYPE) if n else np.zeros(1, abi.WARP_MODEL_JOB_DTYPE))
-    t_models = torch.full((max(1, n + spare_jobs) * size,), fill, dtype=torch.uint8, device="cuda")
-    t_status = torch.full((max(1, n + spare_jobs),), fill, dtype=torch.uint8, device="cuda")
-    t_mv = _dev(np.ascontiguousarray(mv_array, dtype=np.int16)) if mv_array is not None and len(mv_array) else None
+    t_jobs = api.records_to_device(jobs, abi.WARP_MODEL_JOB_DTYPE)
+    t_models = api.filled(max(1, n + spare_jobs) * size, fill)
+    t_status = api.filled(n + spare_jobs, fill)
+    t_mv = api.to_device(mv_array, np.int16) if mv_array is not None and len(mv_array) else None
     torch.cuda.current_stream().synchronize()
     run_warp_model_device(ctx, t_jobs, n, t_models, t_status, shut_approx, lower_band_th, upper_band_th, t_mv, len(mv_array) if t_mv is not None else 0)
     ctx.sync()
-    return {"models": t_models.cpu().numpy().view(abi.WARP_MODEL_DTYPE)[:n + spare_jobs], "status": t_status.cpu().numpy()[:n + spare_jobs]}
+    return {"models": api.to_host(t_models, abi.WARP_MODEL_DTYPE, count=n + spare_jobs), "status": api.to_host(t_status, count=n + spare_jobs)}
 
 
 MV_CENTRE = 1 << 14  # the cost tables hold indices -16384 .. 16384; the descriptor points at their centre entries
@@ -145,19 +140,19 @@ def run_wm_refine_hip(ctx, settings, planes, src, jobs, mv_array=None, cost_tabl
     abi.WM_REFINE_JOB_DTYPE; cost_tables: (mvjcost, row table, column table) int32 arrays or None.  Returns the outputs by name, each [n + spare]
     (best_mv [n + spare][2]), and "planes" / "src" read back."""
     n = len(jobs)
-    t_planes = [_dev(np.ascontiguousarray(p[0], dtype=np.uint8)) for p in planes]
+    t_planes = [api.to_device(p[0], np.uint8) for p in planes]
     refs = [plane_ref(t, p.shape[1], ox, oy, pw, ph, p.shape[0]) for t, (p, ox, oy, pw, ph) in zip(t_planes, planes)]
-    t_src = _dev(np.ascontiguousarray(src, dtype=np.uint8))
-    t_jobs = _dev(np.ascontiguousarray(jobs, dtype=abi.WM_REFINE_JOB_DTYPE) if n else np.zeros(1, abi.WM_REFINE_JOB_DTYPE))
-    t_mv = _dev(np.ascontiguousarray(mv_array, dtype=np.int16)) if mv_array is not None and len(mv_array) else None
-    t_cost = [_dev(np.ascontiguousarray(t, dtype=np.int32)) for t in cost_tables] if cost_tables is not None else None
+    t_src = api.to_device(src, np.uint8)
+    t_jobs = api.records_to_device(jobs, abi.WM_REFINE_JOB_DTYPE)
+    t_mv = api.to_device(mv_array, np.int16) if mv_array is not None and len(mv_array) else None
+    t_cost = [api.to_device(t, np.int32) for t in cost_tables] if cost_tables is not None else None
     outs = run_wm_refine_device(ctx, settings, refs, t_src, src.shape[1], t_jobs, n, t_mv, len(mv_array) if t_mv is not None else 0, t_cost, waves_per_job,
                                 spare, fill)
     ctx.sync()
-    out = {name: t.cpu().numpy().view(REFINE_OUT_DTYPES[name]) for name, t in outs.items()}
+    out = {name: api.to_host(t, REFINE_OUT_DTYPES[name]) for name, t in outs.items()}
     out["best_mv"] = out["best_mv"].reshape(-1, 2)
-    out["planes"] = [t.cpu().numpy().reshape(p[0].shape) for t, p in zip(t_planes, planes)]
-    out["src"] = t_src.cpu().numpy().reshape(src.shape)
+    out["planes"] = [api.to_host(t, shape=p[0].shape) for t, p in zip(t_planes, planes)]
+    out["src"] = api.to_host(t_src, shape=src.shape)
     return out
 
 

@@ -9,7 +9,7 @@ import pytest
 
 import gm_cases as gc
 import warp_cases as wc
-from svt_av1_psyex_amd import abi, gm, warp
+from svt_av1_psyex_amd import abi, api, gm, warp
 
 pytestmark = pytest.mark.gpu
 
@@ -111,16 +111,16 @@ def test_a_refined_rotzoom_model_through_the_warp_prediction(hip_ctx):
     want_model = gc.restated("one_72x44")[0]["models"]
     assert int(want_model[0]["wmtype"]) == gc.ROTZOOM and int(want_model[0]["valid"]) == 1
     ref = b["planes"][1]
-    t_planes = [gm._dev(p[0]) for p in [b["src"], ref]]
+    t_planes = [api.to_device(p[0]) for p in [b["src"], ref]]
     refs = [warp.plane_ref(t, p[0].shape[1], p[1], p[2], p[3], p[4], p[0].shape[0]) for t, p in zip(t_planes, [b["src"], ref])]
     jobs = b["jobs"].copy()
     jobs["ref"] = 0
-    outs, work = gm.run_gm_refine_device(hip_ctx, refs[0], refs[1:], b["n_refinements"], b["chess_refn"], b["rfn_early_exit"], gm._dev(jobs), 1, fill=FILL)
+    outs, work = gm.run_gm_refine_device(hip_ctx, refs[0], refs[1:], b["n_refinements"], b["chess_refn"], b["rfn_early_exit"], api.to_device(jobs), 1, fill=FILL)
     pj = wc.pack_jobs([wc.pred_job(y * 64 + x, x, y, w, h, [0], [], flags=wc.MODEL0_FROM_ARRAY, model_index=(0, 0)) for x, y, w, h in ((0, 0, 32, 32), (40, 8, 16, 32), (56, 32, 8, 8))],
                       wc.PRED_JOB_DTYPE)
     dst = torch.full((64 * 64,), FILL, dtype=torch.uint8, device="cuda")
     status = torch.full((len(pj),), FILL, dtype=torch.uint8, device="cuda")
-    t_jobs = gm._dev(pj)
+    t_jobs = api.to_device(pj)
     torch.cuda.current_stream().synchronize()
     warp.run_warp_pred_device(hip_ctx, 8, 0, 0, refs[1:], dst, 64, t_jobs, len(pj), status, models=outs["models"], n_models=1)
     hip_ctx.sync()

@@ -9,17 +9,13 @@ with the restatement of tests/cfl_cases.py.  Per batch: ms, the bytes read (the 
 job records) and written (the slots and the status bytes) and the GB/s that makes.  The yardstick is a device-to-device copy (torch's copy_ on
 the same stream, timed the same way) of as many bytes as the batch writes; the ratio batch / copy is printed per batch.  Prints one JSON line per
 measurement (and, with --out, writes them as JSON)."""
-import argparse
 import ctypes as C
-import json
-import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import cfl_cases as cc  # noqa: E402
 from svt_av1_psyex_amd import abi, api, cfl  # noqa: E402
 
@@ -27,23 +23,8 @@ LW, LH = 3840, 2160
 CW, CH = LW // 2, LH // 2
 
 
-def timed(ctx, ext, reps, launch):
-    import torch
-    for _ in range(5):
-        launch()
-    ctx.sync()
-    ms = []
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ctx.sync()
-    q = statistics.quantiles(ms, n=4)
-    return dict(ms_median=round(statistics.median(ms), 4), ms_q1=round(q[0], 4), ms_q3=round(q[2], 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4))
+def ms_fields(ms):
+    return {f"ms_{k}": round(v, 4) for k, v in perf_common.quartiles(ms).items()}
 
 
 def make_jobs(size):
@@ -57,10 +38,7 @@ def make_jobs(size):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the figures as JSON to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 30)
     import torch
     L = api.lib()
     ctx = api.Context(0)
@@ -80,7 +58,7 @@ def main():
         t_dst = [torch.zeros(samples * 2, dtype=torch.uint8, device="cuda") for _ in range(2)]
         torch.cuda.synchronize()
         d = cfl.run_cfl_pred_device(ctx, 10, size, size, cfl.ALPHAS_FULL, t_luma, LW, LW, LH, t_dc, CW, t_dst, size, slot, t_jobs, n, t_status)
-        t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_cfl_pred_batch(ctx._h, C.byref(d)), "svt_hip_cfl_pred_batch"))
+        t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_cfl_pred_batch(ctx._h, C.byref(d)), "svt_hip_cfl_pred_batch")))
         if t_status.cpu().numpy().any():
             raise SystemExit(f"{size}x{size}: a job reported a status other than 0")
         got = [x.cpu().numpy().view(np.uint16) for x in t_dst]
@@ -93,22 +71,20 @@ def main():
         rd_b, wr_b = n * (4 * slot * 2 + 2 * slot * 2 + 24), 2 * samples * 2 + n
         res = dict(entry="svt_hip_cfl_pred_batch", block=size, n_alpha=abi.CFL_SLOTS, jobs=n, **t, bytes_read=rd_b, bytes_written=wr_b,
                    gb_per_s=round((rd_b + wr_b) / t["ms_median"] / 1e6, 1), gb_per_s_written=round(wr_b / t["ms_median"] / 1e6, 1))
-        print(json.dumps(res), flush=True)
+        perf_common.emit(res)
         # the yardstick: as many bytes, device to device
         t_from, t_to = torch.zeros(wr_b, dtype=torch.uint8, device="cuda"), torch.zeros(wr_b, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         with torch.cuda.stream(ext):
-            c = timed(ctx, ext, a.reps, lambda: t_to.copy_(t_from))
+            c = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: t_to.copy_(t_from)))
         copy = dict(entry="device_to_device_copy", block=size, bytes=wr_b, **c, gb_per_s_written=round(wr_b / c["ms_median"] / 1e6, 1))
-        print(json.dumps(copy), flush=True)
+        perf_common.emit(copy)
         res["over_copy"] = round(t["ms_median"] / c["ms_median"], 2)
-        print(json.dumps(dict(block=size, over_copy=res["over_copy"])), flush=True)
+        perf_common.emit(dict(block=size, over_copy=res["over_copy"]))
         results += [res, copy]
         del t_dst, t_from, t_to, got
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        json.dump(results, open(a.out, "w"), indent=1)
+    perf_common.write_json(a.out, results)
 
 
 if __name__ == "__main__":

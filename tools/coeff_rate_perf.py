@@ -8,17 +8,14 @@ on the context stream, 5 warm-up launches, median of --reps.  Also printed: the 
 coefficient) against the 8.0 TB/s HBM spec peak.  The tables are the default-probability tables of tests/golden/coeff_rate.npz; the
 results are compared with the restatement of tests/coeff_rate_cases.py on a sample of the jobs.  Prints one JSON line per size (and, with
 --out, writes the figures as JSON)."""
-import argparse
 import ctypes as C
-import json
-import os
 import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import coeff_rate_cases as cr  # noqa: E402
 from svt_av1_psyex_amd import abi, api, rate, rd  # noqa: E402
 
@@ -27,29 +24,12 @@ W, H = 3840, 2160
 GROUP = 16
 
 
-def timed(ctx, ext, reps, launch):
-    import torch
-    for _ in range(5):
-        launch()
-    ctx.sync()
-    ms = []
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ctx.sync()
+def median_min(ms):
     return statistics.median(ms), min(ms)
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the figures as JSON to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 30)
     import torch
     L = api.lib()
     ctx = api.Context(0)
@@ -86,8 +66,8 @@ def main():
                               dist_stride=2, dist=outs["dist_coeff"].data_ptr(), rd_cost=t_cost.data_ptr(), group_start=t_gs.data_ptr(),
                               best_job=t_bj.data_ptr(), best_cost=t_bc.data_ptr())
         torch.cuda.synchronize()
-        rd_ms, rd_min = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_rd_batch(ctx._h, C.byref(d)), "svt_hip_rd_batch"))
-        rate_ms, rate_min = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_coeff_rate_batch(ctx._h, C.byref(r)), "svt_hip_coeff_rate_batch"))
+        rd_ms, rd_min = median_min(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_rd_batch(ctx._h, C.byref(d)), "svt_hip_rd_batch")))
+        rate_ms, rate_min = median_min(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_coeff_rate_batch(ctx._h, C.byref(r)), "svt_hip_coeff_rate_batch")))
         # a sample of the jobs against the restatement
         eob = outs["eob"].cpu().numpy().view(np.uint16)
         q = outs["qcoeff"].cpu().numpy().view(np.int32).reshape(n, npk)
@@ -102,11 +82,9 @@ def main():
                    rate_gb_per_s=round(n * npk * 4 / rate_ms / 1e6, 1), rate_hbm_peak_share=round(n * npk * 4 / rate_ms / 1e-3 / HBM_PEAK, 4),
                    qcoeff_bytes=n * npk * 4, bits_bytes=n * 8, bits_and_cost_bytes=n * 16, winner_bytes=n_groups * 12)
         results.append(res)
-        print(json.dumps(res), flush=True)
+        perf_common.emit(res)
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        json.dump(results, open(a.out, "w"), indent=1)
+    perf_common.write_json(a.out, results)
 
 
 if __name__ == "__main__":

@@ -18,20 +18,16 @@ cfl_alpha_idx, cfl_alpha_signs and the slots it evaluated.  Where the reference 
 checks that) and the fixture holds 0, 0, as include/svt_hip_cfl.h defines.  --check recomputes everything and compares it with the committed
 file instead of writing it; either way the restatement is compared with the reference on every job and every case, and the coverage conditions
 are asserted."""
-import argparse
 import ctypes as C
-import io
 import os
-import subprocess
 import sys
-import tempfile
-import zipfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import cfl_cases as cc  # noqa: E402
+import refbuild  # noqa: E402
 
 HARNESS_LEAVES = r"""
 #include <stdlib.h>
@@ -127,47 +123,13 @@ int harness_pick(const uint64_t *bits, const uint64_t *dist, const int32_t *fac,
 }
 """
 
-VERSION_SCRIPT = "{ global: harness_*; local: *; };\n"
 SOURCES = ["Codec/intra_prediction.c", "C_DEFAULT/cfl_c.c", "C_DEFAULT/intra_prediction_c.c", "C_DEFAULT/filterintra_c.c", "C_DEFAULT/picture_operators_c.c",
            "Codec/cdef.c", "Codec/aom_dsp_rtcd.c", "Codec/common_dsp_rtcd.c"]
 
 
 def build(ref, tmp):
-    """Compiles the sources and the harness; symbols the link still wants become stand-ins (functions that abort) and the link is repeated."""
-    lib = os.path.join(ref, "Source", "Lib")
-    inc = [f"-I{ref}/Source/API"] + [f"-I{lib}/{d}" for d in ("Codec", "C_DEFAULT", "Globals", "ASM_SSE2", "ASM_SSSE3", "ASM_SSE4_1", "ASM_AVX2")]
-    inc += [f"-I{ref}/third_party/fastfeat", f"-I{ref}/third_party/safestringlib"]
-    flags = ["-O2", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w", "-msse4.1", "-DARCH_X86_64=1", "-DEN_AVX512_SUPPORT=0", "-DEXCLUDE_HASH=1",
-             "-DREPRODUCIBLE_BUILDS=0"] + inc
-    open(os.path.join(tmp, "exports.map"), "w").write(VERSION_SCRIPT)
-    objs = []
-    for src in [os.path.join(lib, s) for s in SOURCES]:
-        obj = os.path.join(tmp, os.path.basename(src)[:-2] + ".o")
-        subprocess.run(["gcc"] + flags + ["-c", src, "-o", obj], check=True)
-        objs.append(obj)
-    for name, text in (("harness_leaves", HARNESS_LEAVES), ("harness_pick", HARNESS_PICK)):
-        open(os.path.join(tmp, name + ".c"), "w").write(text)
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, name + ".c"), "-o", os.path.join(tmp, name + ".o")], check=True)
-        objs.append(os.path.join(tmp, name + ".o"))
-    so = os.path.join(tmp, "libcflref.so")
-    standins = []
-    for _ in range(4):
-        text = "\n".join(f'void {s}(void) {{ fputs("stand-in called: {s}\\n", stderr); abort(); }}' for s in standins)
-        open(os.path.join(tmp, "standins.c"), "w").write("#include <stdio.h>\n#include <stdlib.h>\n" + text + "\n")
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, "standins.c"), "-o", os.path.join(tmp, "standins.o")], check=True)
-        r = subprocess.run(["gcc", "-shared", "-o", so] + objs + [os.path.join(tmp, "standins.o"), "-Wl,--gc-sections", "-Wl,-z,defs",
-                            f"-Wl,--version-script={tmp}/exports.map", "-lm", "-lpthread"], capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        wanted = sorted({ln.split("`")[1].split("'")[0] for ln in r.stderr.splitlines() if "undefined reference to `" in ln})
-        if not wanted or set(wanted) <= set(standins):
-            raise RuntimeError(r.stderr[-4000:])
-        standins = sorted(set(standins) | set(wanted))
-    else:
-        raise RuntimeError(r.stderr[-4000:])
-    if standins:
-        print(f"stand-ins for {len(standins)} symbols the link still wants (the SIMD bodies the rtcd files name and what the rest of product_coding_loop.c calls)")
-    L = C.CDLL(so)
+    """The stand-ins are the SIMD bodies the rtcd files name and what the rest of product_coding_loop.c calls."""
+    L = refbuild.build(ref, tmp, "cflref", SOURCES, [("harness_leaves", HARNESS_LEAVES), ("harness_pick", HARNESS_PICK)], standins=True)
     L.harness_cfl_job.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.harness_cfl_job.restype = None
     L.harness_pick.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
@@ -248,36 +210,13 @@ def generate(L):
     return out
 
 
-def save(path, arrays):
-    """an .npz with fixed time stamps, so that the same arrays give the same bytes"""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
-        for name in sorted(arrays):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[name]), allow_pickle=False)
-            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            info.external_attr = 0o644 << 16
-            z.writestr(info, buf.getvalue(), compresslevel=9)
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--ref", required=True, help="root of the reference encoder's source tree")
-    ap.add_argument("--check", action="store_true", help="compare with the committed fixture instead of writing it")
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        out = generate(build(a.ref, tmp))
-    if a.check:
-        z = np.load(cc.GOLDEN)
-        bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-        print("identical" if not bad else f"differs: {bad}")
-        sys.exit(1 if bad else 0)
-    save(cc.GOLDEN, out)
-    largest = max(os.path.getsize(os.path.join(os.path.dirname(cc.GOLDEN), f)) for f in os.listdir(os.path.dirname(cc.GOLDEN)) if f != os.path.basename(cc.GOLDEN))
-    print(f"wrote {cc.GOLDEN} ({os.path.getsize(cc.GOLDEN)} bytes; the largest other fixture has {largest}), {len(out)} arrays")
-    if os.path.getsize(cc.GOLDEN) > largest:
-        sys.exit("the fixture is larger than the largest fixture already there")
+def wrote(path, out):
+    largest = max(os.path.getsize(os.path.join(os.path.dirname(path), f)) for f in os.listdir(os.path.dirname(path)) if f != os.path.basename(path))
+    line = f"wrote {path} ({os.path.getsize(path)} bytes; the largest other fixture has {largest}), {len(out)} arrays"
+    if os.path.getsize(path) > largest:
+        sys.exit(line + "\nthe fixture is larger than the largest fixture already there")
+    return line
 
 
 if __name__ == "__main__":
-    main()
+    refbuild.main(__doc__, build, {cc.GOLDEN: generate}, wrote=wrote)

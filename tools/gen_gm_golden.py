@@ -21,21 +21,17 @@ evaluation without its early exit among them --, and the conditions of the case 
 the refusals (an evaluation that returns 1 and leaves the parameters as they were), the ROTZOOM state (gamma and delta the reference used differ
 from those of the fresh matrix, in a job whose kept parameters would differ with fresh ones), both ends of rfn_early_exit.  For every evaluation the
 reference's own return and the full error are shown to lead to the same decision.  --time reports the reference's C time of picture-sized jobs."""
-import argparse
 import ctypes as C
-import io
 import os
-import subprocess
 import sys
-import tempfile
 import time
-import zipfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import gm_cases as gc  # noqa: E402
+import refbuild  # noqa: E402
 
 HARNESS = r"""
 #define svt_av1_warp_error harness_spy_warp_error
@@ -147,45 +143,13 @@ int harness_corr(const int *p, uint8_t *total, uint8_t *cands, uint32_t *mvs, in
 }
 """
 
-VERSION_SCRIPT = "{ global: harness_*; local: *; };\n"
 SOURCES = ["Codec/enc_warped_motion.c", "Codec/warped_motion.c", "C_DEFAULT/compute_sad_c.c", "Codec/aom_dsp_rtcd.c", "Codec/common_dsp_rtcd.c"]
 LOG_W = 19
 
 
 def build(ref, tmp):
-    """Compiles the sources and the harness; symbols the link still wants become stand-ins (functions that abort) and the link is repeated."""
-    lib = os.path.join(ref, "Source", "Lib")
-    inc = [f"-I{ref}/Source/API"] + [f"-I{lib}/{d}" for d in ("Codec", "C_DEFAULT", "Globals", "ASM_SSE2", "ASM_SSSE3", "ASM_SSE4_1", "ASM_AVX2")]
-    inc += [f"-I{ref}/third_party/fastfeat", f"-I{ref}/third_party/safestringlib"]
-    flags = ["-O2", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w", "-msse4.1", "-DARCH_X86_64=1", "-DEN_AVX512_SUPPORT=0", "-DEXCLUDE_HASH=1",
-             "-DREPRODUCIBLE_BUILDS=0", "-DNDEBUG"] + inc
-    open(os.path.join(tmp, "exports.map"), "w").write(VERSION_SCRIPT)
-    open(os.path.join(tmp, "harness.c"), "w").write(HARNESS)
-    objs = [os.path.join(tmp, "harness.o")]
-    subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, "harness.c"), "-o", objs[0]], check=True)
-    for src in SOURCES:
-        obj = os.path.join(tmp, os.path.basename(src)[:-2] + ".o")
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(lib, src), "-o", obj], check=True)
-        objs.append(obj)
-    so = os.path.join(tmp, "libgmref.so")
-    standins = []
-    for _ in range(8):
-        text = "\n".join(f'void {s}(void) {{ fputs("stand-in called: {s}\\n", stderr); abort(); }}' for s in standins)
-        open(os.path.join(tmp, "standins.c"), "w").write("#include <stdio.h>\n#include <stdlib.h>\n" + text + "\n")
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, "standins.c"), "-o", os.path.join(tmp, "standins.o")], check=True)
-        r = subprocess.run(["gcc", "-shared", "-o", so] + objs + [os.path.join(tmp, "standins.o"), "-Wl,--gc-sections", "-Wl,-z,defs",
-                            f"-Wl,--version-script={tmp}/exports.map", "-lm", "-lpthread"], capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        wanted = sorted({ln.split("`")[1].split("'")[0] for ln in r.stderr.splitlines() if "undefined reference to `" in ln})
-        if not wanted or set(wanted) <= set(standins):
-            raise RuntimeError(r.stderr[-4000:])
-        standins = sorted(set(standins) | set(wanted))
-    else:
-        raise RuntimeError(r.stderr[-4000:])
-    if standins:
-        print(f"stand-ins for {len(standins)} symbols the link still wants: {standins[:6]}")
-    L = C.CDLL(so)
+    """Symbols the link still wants get stand-ins: the SIMD bodies the rtcd files name and what the rest of the compiled sources calls."""
+    L = refbuild.build(ref, tmp, "gmref", SOURCES, [("harness", HARNESS)], standins=True)
     P = C.c_void_p
     L.harness_refine.argtypes = [P, P, P, P, C.c_int64, P, P, C.c_int]
     L.harness_corr.argtypes = [P, P, P, P, P, C.c_int]
@@ -334,38 +298,6 @@ def time_reference(L):
                   f"(half of the harness's, which evaluates twice)")
 
 
-def save(path, arrays):
-    """an .npz with fixed time stamps, so that the same arrays give the same bytes"""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
-        for name in sorted(arrays):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[name]), allow_pickle=False)
-            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            info.external_attr = 0o644 << 16
-            z.writestr(info, buf.getvalue(), compresslevel=9)
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--ref", required=True, help="root of the reference encoder's source tree")
-    ap.add_argument("--check", action="store_true", help="compare with the committed fixture instead of writing it")
-    ap.add_argument("--time", action="store_true", help="report the reference's C time of picture-sized jobs and stop")
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        L = build(a.ref, tmp)
-        if a.time:
-            time_reference(L)
-            return
-        out = generate(L)
-    if a.check:
-        z = np.load(gc.GOLDEN)
-        bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-        print("identical" if not bad else f"differs: {bad}")
-        sys.exit(1 if bad else 0)
-    save(gc.GOLDEN, out)
-    print(f"wrote {gc.GOLDEN} ({os.path.getsize(gc.GOLDEN)} bytes), {len(out)} arrays")
-
-
 if __name__ == "__main__":
-    main()
+    refbuild.main(__doc__, build, {gc.GOLDEN: generate}, flags=[("--time", "report the reference's C time of picture-sized jobs and stop")],
+                  first=lambda a, L: a.time and (time_reference(L) or True))

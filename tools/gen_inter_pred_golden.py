@@ -16,18 +16,16 @@ batch a CRC-32 per job of the predicted block (per filter pair for the exhaustiv
 recomputes everything and compares it with the committed file instead of writing it; either way the restatement of tests/inter_pred_cases.py
 is compared with the reference on every job, every job's reads are checked to lie inside its padded plane, and the coverage conditions are
 asserted on the reference's results (the call counts of the sixteen functions are the harness's own)."""
-import argparse
 import ctypes as C
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import inter_pred_cases as ip  # noqa: E402
+import refbuild  # noqa: E402
 
 HARNESS = r"""
 #include <stdlib.h>
@@ -98,44 +96,12 @@ void harness_predict(const int *p, uint8_t *src0, uint8_t *src1, int src_stride,
     }
 }
 """
-VERSION_SCRIPT = "{ global: harness_*; local: *; };\n"
 SOURCES = ["Codec/inter_prediction.c", "Codec/enc_inter_prediction.c", "Codec/aom_dsp_rtcd.c", "Codec/common_dsp_rtcd.c"]
 
 
 def build(ref, tmp):
-    """Compiles the sources and the harness; symbols the link still wants become stand-ins (functions that abort) and the link is repeated."""
-    lib = os.path.join(ref, "Source", "Lib")
-    inc = [f"-I{ref}/Source/API"] + [f"-I{lib}/{d}" for d in ("Codec", "C_DEFAULT", "Globals", "ASM_SSE2", "ASM_SSSE3", "ASM_SSE4_1", "ASM_AVX2")]
-    inc += [f"-I{ref}/third_party/fastfeat", f"-I{ref}/third_party/safestringlib"]
-    flags = ["-O2", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w", "-DARCH_X86_64=1", "-DEN_AVX512_SUPPORT=0", "-DEXCLUDE_HASH=1",
-             "-DREPRODUCIBLE_BUILDS=0"] + inc
-    open(os.path.join(tmp, "exports.map"), "w").write(VERSION_SCRIPT)
-    objs = []
-    for src in [os.path.join(lib, s) for s in SOURCES]:
-        obj = os.path.join(tmp, os.path.basename(src)[:-2] + ".o")
-        subprocess.run(["gcc"] + flags + ["-c", src, "-o", obj], check=True)
-        objs.append(obj)
-    so = os.path.join(tmp, "libinterpredref.so")
-    standins = []
-    for _ in range(3):
-        text = "\n".join(f"void {s}(void) {{ abort(); }}" for s in standins)
-        open(os.path.join(tmp, "harness.c"), "w").write(HARNESS)
-        open(os.path.join(tmp, "standins.c"), "w").write("#include <stdlib.h>\n" + text + "\n")
-        for name in ("harness", "standins"):
-            subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, name + ".c"), "-o", os.path.join(tmp, name + ".o")], check=True)
-        r = subprocess.run(["gcc", "-shared", "-o", so] + objs + [os.path.join(tmp, "harness.o"), os.path.join(tmp, "standins.o"), "-Wl,--gc-sections",
-                            "-Wl,-z,defs", f"-Wl,--version-script={tmp}/exports.map", "-lm"], capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        wanted = sorted({ln.split("`")[1].split("'")[0] for ln in r.stderr.splitlines() if "undefined reference to `" in ln})
-        if not wanted or set(wanted) <= set(standins):
-            raise RuntimeError(r.stderr[-4000:])
-        standins = sorted(set(standins) | set(wanted))
-    else:
-        raise RuntimeError(r.stderr[-4000:])
-    if standins:
-        print(f"stand-ins for {len(standins)} symbols the link still wants: {' '.join(standins)}")
-    L = C.CDLL(so)
+    """Symbols the link still wants get stand-ins: the SIMD bodies the rtcd files name and what the rest of the compiled sources calls."""
+    L = refbuild.build(ref, tmp, "interpredref", SOURCES, [("harness", HARNESS)], standins=True)
     L.harness_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.harness_predict.restype = None
     L.harness_counts.argtypes = [C.c_void_p]
@@ -199,21 +165,5 @@ def generate(L):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--ref", required=True, help="root of the reference encoder's source tree")
-    ap.add_argument("--check", action="store_true", help="compare with the committed fixture instead of writing it")
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        out = generate(build(a.ref, tmp))
-    if a.check:
-        z = np.load(ip.GOLDEN)
-        bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-        print("identical" if not bad else f"differs: {bad}")
-        sys.exit(1 if bad else 0)
-    np.savez_compressed(ip.GOLDEN, **out)
-    print(f"wrote {ip.GOLDEN} ({os.path.getsize(ip.GOLDEN)} bytes), {len(out)} arrays")
-
-
 if __name__ == "__main__":
-    main()
+    refbuild.main(__doc__, build, {ip.GOLDEN: generate}, save=refbuild.savez)

@@ -17,18 +17,16 @@ the samples tests/intra_pred_cases.py's job_reads names and a poison value every
 fixture holds numbers only: per batch a CRC-32 per job of the predicted block, and the full block of a sample of jobs.  --check recomputes
 everything and compares it with the committed file instead of writing it; either way the restatement is compared with the reference on every
 job, every job's reads are checked to lie inside the neighbour plane, and the coverage conditions are asserted on the reference's results."""
-import argparse
 import ctypes as C
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import intra_pred_cases as ic  # noqa: E402
+import refbuild  # noqa: E402
 
 HARNESS = r"""
 #include <stdlib.h>
@@ -127,46 +125,13 @@ def table_wrappers():
     return "\n".join(out)
 
 
-VERSION_SCRIPT = "{ global: harness_*; local: *; };\n"
 SOURCES = ["Codec/intra_prediction.c", "C_DEFAULT/intra_prediction_c.c", "C_DEFAULT/filterintra_c.c", "C_DEFAULT/picture_operators_c.c",
            "Codec/cdef.c", "Codec/aom_dsp_rtcd.c", "Codec/common_dsp_rtcd.c"]
 
 
 def build(ref, tmp):
-    """Compiles the sources and the harness; symbols the link still wants become stand-ins (functions that abort) and the link is repeated."""
-    lib = os.path.join(ref, "Source", "Lib")
-    inc = [f"-I{ref}/Source/API"] + [f"-I{lib}/{d}" for d in ("Codec", "C_DEFAULT", "Globals", "ASM_SSE2", "ASM_SSSE3", "ASM_SSE4_1", "ASM_AVX2")]
-    inc += [f"-I{ref}/third_party/fastfeat", f"-I{ref}/third_party/safestringlib"]
-    flags = ["-O2", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w", "-DARCH_X86_64=1", "-DEN_AVX512_SUPPORT=0", "-DEXCLUDE_HASH=1",
-             "-DREPRODUCIBLE_BUILDS=0"] + inc
-    open(os.path.join(tmp, "exports.map"), "w").write(VERSION_SCRIPT)
-    objs = []
-    for src in [os.path.join(lib, s) for s in SOURCES]:
-        obj = os.path.join(tmp, os.path.basename(src)[:-2] + ".o")
-        subprocess.run(["gcc"] + flags + ["-c", src, "-o", obj], check=True)
-        objs.append(obj)
-    so = os.path.join(tmp, "libintrapredref.so")
-    open(os.path.join(tmp, "harness.c"), "w").write(HARNESS.replace("@TABLE_WRAPPERS@", table_wrappers()))
-    subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, "harness.c"), "-o", os.path.join(tmp, "harness.o")], check=True)
-    standins = []
-    for _ in range(4):
-        text = "\n".join(f'void {s}(void) {{ fputs("stand-in called: {s}\\n", stderr); abort(); }}' for s in standins)
-        open(os.path.join(tmp, "standins.c"), "w").write("#include <stdio.h>\n#include <stdlib.h>\n" + text + "\n")
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, "standins.c"), "-o", os.path.join(tmp, "standins.o")], check=True)
-        r = subprocess.run(["gcc", "-shared", "-o", so] + objs + [os.path.join(tmp, "harness.o"), os.path.join(tmp, "standins.o"), "-Wl,--gc-sections",
-                            "-Wl,-z,defs", f"-Wl,--version-script={tmp}/exports.map", "-lm"], capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        wanted = sorted({ln.split("`")[1].split("'")[0] for ln in r.stderr.splitlines() if "undefined reference to `" in ln})
-        if not wanted or set(wanted) <= set(standins):
-            raise RuntimeError(r.stderr[-4000:])
-        standins = sorted(set(standins) | set(wanted))
-    else:
-        raise RuntimeError(r.stderr[-4000:])
-    if standins:
-        print(f"stand-ins for {len(standins)} symbols the link still wants (the SIMD bodies the rtcd files name, never chosen without a CPU flag, and what "
-              f"the rest of enc_intra_prediction.c calls)")
-    L = C.CDLL(so)
+    """The stand-ins are the SIMD bodies the rtcd files name, never chosen without a CPU flag, and what the rest of enc_intra_prediction.c calls."""
+    L = refbuild.build(ref, tmp, "intrapredref", SOURCES, [("harness", HARNESS.replace("@TABLE_WRAPPERS@", table_wrappers()))], standins=True)
     L.harness_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.harness_predict.restype = None
     L.harness_counts.argtypes = [C.c_void_p]
@@ -233,21 +198,5 @@ def generate(L):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--ref", required=True, help="root of the reference encoder's source tree")
-    ap.add_argument("--check", action="store_true", help="compare with the committed fixture instead of writing it")
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        out = generate(build(a.ref, tmp))
-    if a.check:
-        z = np.load(ic.GOLDEN)
-        bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-        print("identical" if not bad else f"differs: {bad}")
-        sys.exit(1 if bad else 0)
-    np.savez_compressed(ic.GOLDEN, **out)
-    print(f"wrote {ic.GOLDEN} ({os.path.getsize(ic.GOLDEN)} bytes), {len(out)} arrays")
-
-
 if __name__ == "__main__":
-    main()
+    refbuild.main(__doc__, build, {ic.GOLDEN: generate}, save=refbuild.savez)

@@ -23,14 +23,9 @@ block per size and depth; per search batch every output of every job (exit, wedg
 use_wedge_interintra, interintra_wedge_index -- the reference returns no rd).  --check recomputes everything and compares it with the committed
 file instead of writing it; either way the restatement of tests/mask_cases.py is compared with the reference on every job, every prediction job's
 reads are checked to lie inside its padded plane, and the conditions of the planted search inputs are asserted on the reference's results."""
-import argparse
 import ctypes as C
-import io
 import os
-import subprocess
 import sys
-import tempfile
-import zipfile
 
 import numpy as np
 
@@ -38,6 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import inter_pred_cases as ip  # noqa: E402
 import mask_cases as mc  # noqa: E402
+import refbuild  # noqa: E402
 
 HARNESS = r"""
 #include "inter_prediction.c"
@@ -256,49 +252,15 @@ int harness_interintra_search(const int *p, uint8_t *src, int src_stride, const 
 }
 """
 
-VERSION_SCRIPT = "{ global: harness_*; local: *; };\n"
 SOURCES = ["Codec/enc_inter_prediction.c", "Codec/blend_a64_mask.c", "C_DEFAULT/inter_prediction_c.c", "C_DEFAULT/compute_sad_c.c", "Codec/aom_dsp_rtcd.c",
            "Codec/common_dsp_rtcd.c"]
 
 
 def build(ref, tmp):
-    """Compiles the sources and the harness; symbols the link still wants become stand-ins (functions that abort) and the link is repeated."""
-    lib = os.path.join(ref, "Source", "Lib")
-    inc = [f"-I{ref}/Source/API"] + [f"-I{lib}/{d}" for d in ("Codec", "C_DEFAULT", "Globals", "ASM_SSE2", "ASM_SSSE3", "ASM_SSE4_1", "ASM_AVX2")]
-    inc += [f"-I{ref}/third_party/fastfeat", f"-I{ref}/third_party/safestringlib"]
-    flags = ["-O2", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w", "-msse4.1", "-DARCH_X86_64=1", "-DEN_AVX512_SUPPORT=0", "-DEXCLUDE_HASH=1",
-             "-DREPRODUCIBLE_BUILDS=0"] + inc
-    open(os.path.join(tmp, "exports.map"), "w").write(VERSION_SCRIPT)
-    objs = []
-    for name, text in (("harness", HARNESS), ("harness_ii", HARNESS_II)):
-        open(os.path.join(tmp, name + ".c"), "w").write(text)
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, name + ".c"), "-o", os.path.join(tmp, name + ".o")], check=True)
-        objs.append(os.path.join(tmp, name + ".o"))
-    for src in SOURCES:
-        obj = os.path.join(tmp, os.path.basename(src)[:-2] + ".o")
-        # the real svt_aom_inter_prediction gets another name: the second unit's stand-in takes its place
-        rename = ["-Dsvt_aom_inter_prediction=svt_aom_inter_prediction_real"] if src.endswith("enc_inter_prediction.c") else []
-        subprocess.run(["gcc"] + flags + rename + ["-c", os.path.join(lib, src), "-o", obj], check=True)
-        objs.append(obj)
-    so = os.path.join(tmp, "libmaskref.so")
-    standins = []
-    for _ in range(4):
-        text = "\n".join(f'void {s}(void) {{ fputs("stand-in called: {s}\\n", stderr); abort(); }}' for s in standins)
-        open(os.path.join(tmp, "standins.c"), "w").write("#include <stdio.h>\n#include <stdlib.h>\n" + text + "\n")
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, "standins.c"), "-o", os.path.join(tmp, "standins.o")], check=True)
-        r = subprocess.run(["gcc", "-shared", "-o", so] + objs + [os.path.join(tmp, "standins.o"), "-Wl,--gc-sections", "-Wl,-z,defs",
-                            f"-Wl,--version-script={tmp}/exports.map", "-lm", "-lpthread"], capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        wanted = sorted({ln.split("`")[1].split("'")[0] for ln in r.stderr.splitlines() if "undefined reference to `" in ln})
-        if not wanted or set(wanted) <= set(standins):
-            raise RuntimeError(r.stderr[-4000:])
-        standins = sorted(set(standins) | set(wanted))
-    else:
-        raise RuntimeError(r.stderr[-4000:])
-    if standins:
-        print(f"stand-ins for {len(standins)} symbols the link still wants: {standins[:6]}")
-    L = C.CDLL(so)
+    """Symbols the link still wants get stand-ins: the SIMD bodies the rtcd files name and what the rest of the compiled sources calls."""
+    # the real svt_aom_inter_prediction gets another name: the second unit's stand-in takes its place
+    rename = {"Codec/enc_inter_prediction.c": ["-Dsvt_aom_inter_prediction=svt_aom_inter_prediction_real"]}
+    L = refbuild.build(ref, tmp, "maskref", SOURCES, [("harness", HARNESS), ("harness_ii", HARNESS_II)], source_flags=rename, standins=True)
     P = C.c_void_p
     L.harness_tables.argtypes = [P, P, P, P]
     L.harness_masked_predict.argtypes = [P, P, P, C.c_int, P, C.c_int, P]
@@ -487,33 +449,5 @@ def generate(L):
     return out
 
 
-def save(path, arrays):
-    """an .npz with fixed time stamps, so that the same arrays give the same bytes"""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
-        for name in sorted(arrays):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[name]), allow_pickle=False)
-            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            info.external_attr = 0o644 << 16
-            z.writestr(info, buf.getvalue(), compresslevel=9)
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--ref", required=True, help="root of the reference encoder's source tree")
-    ap.add_argument("--check", action="store_true", help="compare with the committed fixture instead of writing it")
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        out = generate(build(a.ref, tmp))
-    if a.check:
-        z = np.load(mc.GOLDEN)
-        bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-        print("identical" if not bad else f"differs: {bad}")
-        sys.exit(1 if bad else 0)
-    save(mc.GOLDEN, out)
-    print(f"wrote {mc.GOLDEN} ({os.path.getsize(mc.GOLDEN)} bytes), {len(out)} arrays")
-
-
 if __name__ == "__main__":
-    main()
+    refbuild.main(__doc__, build, {mc.GOLDEN: generate})

@@ -20,12 +20,9 @@ svt_av1_is_lossless_segment = false: lossless segments are not listed as jobs) a
 case the controls, per job the reference's qcoeff (int16), eob, cul_level and the status the restatement assigns, per case a CRC of the
 reference's dqcoeff.  --check recomputes everything and compares it with the committed file instead of writing it; either way the restatement
 of tests/rdoq_cases.py is compared with the reference on every job, and the coverage conditions are asserted on the reference's results."""
-import argparse
 import ctypes as C
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -33,6 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 import coeff_rate_cases as cr  # noqa: E402
 import rdoq_cases as rq  # noqa: E402
+import refbuild  # noqa: E402
 
 HARNESS = r"""
 #include <stdlib.h>
@@ -187,27 +185,12 @@ void harness_quantize(const int *ctl, int tx_size, const int *job, int fp, const
                                   job[3] ? NEARESTMV : DC_PRED, 0, false);
 }
 """
-VERSION_SCRIPT = "{ global: harness_*; local: *; };\n"
 SOURCES = ["Codec/rd_cost.c", "Codec/md_rate_estimation.c", "Codec/cabac_context_model.c", "Codec/aom_dsp_rtcd.c", "Codec/common_dsp_rtcd.c"]
 MEMBERS = list(cr.TABLE_SHAPES)
 
 
 def build(ref, tmp):
-    lib = os.path.join(ref, "Source", "Lib")
-    inc = [f"-I{ref}/Source/API"] + [f"-I{lib}/{d}" for d in ("Codec", "C_DEFAULT", "Globals", "ASM_SSE2", "ASM_SSSE3", "ASM_SSE4_1", "ASM_AVX2")]
-    inc += [f"-I{ref}/third_party/fastfeat", f"-I{ref}/third_party/safestringlib"]
-    flags = ["-O2", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w", "-DARCH_X86_64=1", "-DEN_AVX512_SUPPORT=0", "-DEXCLUDE_HASH=1",
-             "-DREPRODUCIBLE_BUILDS=0"] + inc
-    open(os.path.join(tmp, "harness.c"), "w").write(HARNESS)
-    open(os.path.join(tmp, "exports.map"), "w").write(VERSION_SCRIPT)
-    objs = []
-    for src in [os.path.join(lib, s) for s in SOURCES] + [os.path.join(tmp, "harness.c")]:
-        obj = os.path.join(tmp, os.path.basename(src)[:-2] + ".o")
-        subprocess.run(["gcc"] + flags + ["-c", src, "-o", obj], check=True)
-        objs.append(obj)
-    so = os.path.join(tmp, "librdoqref.so")
-    subprocess.run(["gcc", "-shared", "-o", so] + objs + ["-Wl,--gc-sections", "-Wl,-z,defs", f"-Wl,--version-script={tmp}/exports.map", "-lm"], check=True)
-    L = C.CDLL(so)
+    L = refbuild.build(ref, tmp, "rdoqref", SOURCES, [("harness", HARNESS)])
     L.harness_table.restype = C.c_size_t
     L.harness_table.argtypes = [C.c_int, C.c_void_p]
     L.harness_rows.argtypes = [C.c_void_p, C.c_int]
@@ -288,21 +271,5 @@ def generate(L):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--ref", required=True, help="root of the reference encoder's source tree")
-    ap.add_argument("--check", action="store_true", help="compare with the committed fixture instead of writing it")
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        out = generate(build(a.ref, tmp))
-    if a.check:
-        z = np.load(rq.GOLDEN)
-        bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-        print("identical" if not bad else f"differs: {bad}")
-        sys.exit(1 if bad else 0)
-    np.savez_compressed(rq.GOLDEN, **out)
-    print(f"wrote {rq.GOLDEN} ({os.path.getsize(rq.GOLDEN)} bytes): " + ", ".join(f"{k}{list(v.shape)}" for k, v in out.items()))
-
-
 if __name__ == "__main__":
-    main()
+    refbuild.main(__doc__, build, {rq.GOLDEN: generate}, save=refbuild.savez, wrote=refbuild.wrote_shapes)

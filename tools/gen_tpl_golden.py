@@ -15,12 +15,9 @@ tpl_dispenser_cases.make_case, pinned by a checksum of every input array) and th
 padded recon plane.  The sliding-window case dispenses two pictures: the second's list-0 recon-path reference is the first's TPL recon.
 The edge-case file has the same layout, except that the recon plane of the groups with many or large pictures is stored as its sha256.
 --check recomputes everything and compares it with the two committed files instead of writing them."""
-import argparse
 import ctypes as C
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -28,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 import tpl_dispenser_cases as tc  # noqa: E402
 from svt_av1_psyex_amd import tpl  # noqa: E402
+import refbuild  # noqa: E402
 
 HARNESS = r"""
 /* Calls the reference's own tpl_mc_flow_dispenser_sb_generic (static: included) for every b64 in raster order, then
@@ -246,7 +244,6 @@ AomVarianceFnPtr svt_aom_mefn_ptr[BlockSizeS_ALL];
 int svt_aom_compute_rd_mult_based_on_qindex(EbBitDepth bit_depth, SvtAv1FrameUpdateType update_type, int qindex) { abort(); }
 
 """
-VERSION_SCRIPT = "{ global: harness_*; local: *; };\n"
 SOURCES = ["Codec/enc_intra_prediction.c", "Codec/intra_prediction.c", "Codec/transforms.c", "Codec/inv_transforms.c", "Codec/pic_operators.c",
            "Codec/utility.c", "C_DEFAULT/compute_sad_c.c", "C_DEFAULT/picture_operators_c.c", "Codec/full_loop.c", "Codec/common_dsp_rtcd.c",
            "Codec/aom_dsp_rtcd.c", "Codec/svt_log.c", "Codec/mode_decision.c", "Codec/inter_prediction.c", "ASM_SSE2/pic_operators_intrin_sse2.c"]
@@ -254,23 +251,8 @@ SOURCES = ["Codec/enc_intra_prediction.c", "Codec/intra_prediction.c", "Codec/tr
 
 def build(ref, tmp, harness=HARNESS):
     """Compiles the reference sources with `harness` (C text that #includes src_ops_process.c) into a library; returns it, initialised."""
-    lib = os.path.join(ref, "Source", "Lib")
-    inc = [f"-I{ref}/Source/API"] + [f"-I{lib}/{d}" for d in ("Codec", "C_DEFAULT", "Globals", "ASM_SSE2", "ASM_SSSE3", "ASM_SSE4_1", "ASM_AVX2")]
-    inc += [f"-I{ref}/third_party/fastfeat", f"-I{ref}/third_party/safestringlib", f"-I{ROOT}/include"]
-    flags = ["-O2", "-DNDEBUG", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w", "-msse4.1", "-DARCH_X86_64=1", "-DEN_AVX512_SUPPORT=0",
-             "-DEXCLUDE_HASH=1", "-DREPRODUCIBLE_BUILDS=0"] + inc
-    open(os.path.join(tmp, "harness.c"), "w").write(harness)
-    open(os.path.join(tmp, "exports.map"), "w").write(VERSION_SCRIPT)
-    procs, objs = [], []
-    for src in [os.path.join(lib, s) for s in SOURCES] + [os.path.join(tmp, "harness.c")]:
-        obj = os.path.join(tmp, os.path.basename(src)[:-2] + ".o")
-        procs.append(subprocess.Popen(["gcc"] + flags + ["-c", src, "-o", obj]))
-        objs.append(obj)
-    if any(p.wait() for p in procs):
-        raise RuntimeError("compiling the reference sources failed")
-    so = os.path.join(tmp, "libtplref.so")
-    subprocess.run(["gcc", "-shared", "-o", so] + objs + ["-Wl,--gc-sections", "-Wl,-z,defs", f"-Wl,--version-script={tmp}/exports.map", "-lm"], check=True)
-    L = C.CDLL(so)
+    # -DNDEBUG: svt_aom_generate_r0beta asserts beta > 0, which the group cases of gen_tpl_group_golden.py do not keep; include/: the harness includes svt_hip_tpl.h
+    L = refbuild.build(ref, tmp, "tplref", SOURCES, [("harness", harness)], flags=["-DNDEBUG"], includes=[os.path.join(ROOT, "include")])
     L.harness_init()
     return L
 
@@ -313,26 +295,9 @@ def generate_edges(L):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--ref", required=True, help="root of the reference encoder's source tree")
-    ap.add_argument("--check", action="store_true", help="compare with the committed fixtures instead of writing them")
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        L = build(a.ref, tmp)
-        outs = [(tc.GOLDEN, generate(L)), (tc.GOLDEN_EDGES, generate_edges(L))]
-    if a.check:
-        worst = 0
-        for path, out in outs:
-            z = np.load(path)
-            bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-            print(f"{os.path.basename(path)}: " + ("identical" if not bad else f"differs: {bad}"))
-            worst |= bool(bad)
-        sys.exit(worst)
-    for path, out in outs:
-        np.savez_compressed(path, **out)
-        print(f"wrote {path}: {len([k for k in out if k.startswith('name_')])} cases, {os.path.getsize(path)} bytes")
+def wrote(path, out):
+    return f"wrote {path}: {len([k for k in out if k.startswith('name_')])} cases, {os.path.getsize(path)} bytes"
 
 
 if __name__ == "__main__":
-    main()
+    refbuild.main(__doc__, build, {tc.GOLDEN: generate, tc.GOLDEN_EDGES: generate_edges}, save=refbuild.savez, wrote=wrote)

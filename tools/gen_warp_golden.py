@@ -30,14 +30,9 @@ Two of the issue's conditions on the fit cannot be met by any input, and are the
                      det >= 15 (searched exhaustively below for |sx|, |sy| <= 300, the range LS_MV_MAX and the block sizes allow for a kept sample
                      is wider, but S grows quadratically); further samples add positive semi-definite terms up to the rounding of the three
                      shifts, and a random search over two to eight samples (below) finds no determinant under 15 either."""
-import argparse
 import ctypes as C
-import io
 import os
-import subprocess
 import sys
-import tempfile
-import zipfile
 
 import numpy as np
 
@@ -45,6 +40,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import warp_cases as wc  # noqa: E402
 import warp_edge_cases as ec  # noqa: E402
+import refbuild  # noqa: E402
 
 HARNESS = r"""
 #define RTCD_C
@@ -243,46 +239,12 @@ int harness_refine(const int32_t *settings, const int32_t *geom, const int32_t *
 }
 """
 
-VERSION_SCRIPT = "{ global: harness_*; local: *; };\n"
 SOURCES = ["Codec/av1me.c", "Codec/rd_cost.c", "C_DEFAULT/variance.c"]
 
 
 def build(ref, tmp):
-    """Compiles the harness; symbols the link still wants become stand-ins (functions that abort) and the link is repeated."""
-    lib = os.path.join(ref, "Source", "Lib")
-    inc = [f"-I{ref}/Source/API"] + [f"-I{lib}/{d}" for d in ("Codec", "C_DEFAULT", "Globals", "ASM_SSE2", "ASM_SSSE3", "ASM_SSE4_1", "ASM_AVX2")]
-    inc += [f"-I{ref}/third_party/fastfeat", f"-I{ref}/third_party/safestringlib"]
-    flags = ["-O2", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w", "-msse4.1", "-DARCH_X86_64=1", "-DEN_AVX512_SUPPORT=0", "-DEXCLUDE_HASH=1",
-             "-DREPRODUCIBLE_BUILDS=0"] + inc
-    open(os.path.join(tmp, "exports.map"), "w").write(VERSION_SCRIPT)
-    objs = []
-    for name, text in (("harness", HARNESS), ("harness_refine", HARNESS_REFINE)):
-        open(os.path.join(tmp, name + ".c"), "w").write(text)
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, name + ".c"), "-o", os.path.join(tmp, name + ".o")], check=True)
-        objs.append(os.path.join(tmp, name + ".o"))
-    for src in SOURCES:
-        obj = os.path.join(tmp, os.path.basename(src)[:-2] + ".o")
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(lib, src), "-o", obj], check=True)
-        objs.append(obj)
-    so = os.path.join(tmp, "libwarpref.so")
-    standins = []
-    for _ in range(4):
-        text = "\n".join(f'void {s}(void) {{ fputs("stand-in called: {s}\\n", stderr); abort(); }}' for s in standins)
-        open(os.path.join(tmp, "standins.c"), "w").write("#include <stdio.h>\n#include <stdlib.h>\n" + text + "\n")
-        subprocess.run(["gcc"] + flags + ["-c", os.path.join(tmp, "standins.c"), "-o", os.path.join(tmp, "standins.o")], check=True)
-        r = subprocess.run(["gcc", "-shared", "-o", so] + objs + [os.path.join(tmp, "standins.o"), "-Wl,--gc-sections", "-Wl,-z,defs",
-                            f"-Wl,--version-script={tmp}/exports.map", "-lm", "-lpthread"], capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        wanted = sorted({ln.split("`")[1].split("'")[0] for ln in r.stderr.splitlines() if "undefined reference to `" in ln})
-        if not wanted or set(wanted) <= set(standins):
-            raise RuntimeError(r.stderr[-4000:])
-        standins = sorted(set(standins) | set(wanted))
-    else:
-        raise RuntimeError(r.stderr[-4000:])
-    if standins:
-        print(f"stand-ins for {len(standins)} symbols the link still wants: {standins[:6]}")
-    L = C.CDLL(so)
+    """Symbols the link still wants get stand-ins: the SIMD bodies the rtcd files name and what the rest of the compiled sources calls."""
+    L = refbuild.build(ref, tmp, "warpref", SOURCES, [("harness", HARNESS), ("harness_refine", HARNESS_REFINE)], standins=True)
     P = C.c_void_p
     L.harness_warp.argtypes = [C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, P] + [C.c_int] * 8 + [P]
     L.harness_fit.argtypes = [P, P] + [C.c_int] * 10 + [P]
@@ -463,38 +425,5 @@ def generate(L):
     return out
 
 
-def save(path, arrays):
-    """an .npz with fixed time stamps, so that the same arrays give the same bytes"""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
-        for name in sorted(arrays):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[name]), allow_pickle=False)
-            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            info.external_attr = 0o644 << 16
-            z.writestr(info, buf.getvalue(), compresslevel=9)
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--ref", required=True, help="root of the reference encoder's source tree")
-    ap.add_argument("--check", action="store_true", help="compare with the committed fixture instead of writing it")
-    a = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        L = build(a.ref, tmp)
-        outs = [(wc.GOLDEN, generate(L)), (ec.GOLDEN, generate_edges(L))]
-    if a.check:
-        differs = False
-        for path, out in outs:
-            z = np.load(path)
-            bad = sorted(set(z.files) ^ set(out)) + [k for k in out if k in z.files and not (z[k].dtype == out[k].dtype and np.array_equal(z[k], out[k]))]
-            print(f"{os.path.basename(path)}: " + ("identical" if not bad else f"differs: {bad}"))
-            differs = differs or bool(bad)
-        sys.exit(1 if differs else 0)
-    for path, out in outs:
-        save(path, out)
-        print(f"wrote {path} ({os.path.getsize(path)} bytes), {len(out)} arrays")
-
-
 if __name__ == "__main__":
-    main()
+    refbuild.main(__doc__, build, {wc.GOLDEN: generate, ec.GOLDEN: generate_edges})

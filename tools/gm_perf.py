@@ -8,37 +8,19 @@
   svt_hip_gm_correspondence_batch  the 2160p picture, MV_8x8 and MV_16x16, two pairs, on synthetic ME results
 HIP events around each batch on the context stream, 5 warm-up batches, the median of --reps (default 20) with the quartiles, minimum and maximum.  Every
 job must end with status 0 and two runs must give the same bytes.  Prints one JSON line per measurement (and, with --out, writes them as text)."""
-import argparse
 import json
-import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import gm_cases as gc  # noqa: E402
 from svt_av1_psyex_amd import abi, api, gm, warp  # noqa: E402
 
 
-def timed(ctx, ext, reps, launch):
-    import torch
-    for _ in range(5):
-        launch()
-    ctx.sync()
-    ms = []
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ctx.sync()
-    q = statistics.quantiles(ms, n=4)
-    return dict(ms_median=round(statistics.median(ms), 4), ms_q1=round(q[0], 4), ms_q3=round(q[2], 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4))
+def ms_fields(ms):
+    return {f"ms_{k}": round(v, 4) for k, v in perf_common.quartiles(ms).items()}
 
 
 def refine_case(ctx, ext, reps, w, h, chess, n_jobs, wmtype, n_refinements):
@@ -49,9 +31,9 @@ def refine_case(ctx, ext, reps, w, h, chess, n_jobs, wmtype, n_refinements):
     jobs = np.zeros(n_jobs, abi.GM_REFINE_JOB_DTYPE)
     for i in range(n_jobs):
         jobs[i] = gc.job(start, wmtype, i, params_cost=300)
-    t_planes = [gm._dev(p[0]) for p in [src] + planes]
+    t_planes = [api.to_device(p[0]) for p in [src] + planes]
     refs = [warp.plane_ref(t, p[0].shape[1], p[1], p[2], p[3], p[4], p[0].shape[0]) for t, p in zip(t_planes, [src] + planes)]
-    t_jobs = gm._dev(jobs)
+    t_jobs = api.to_device(jobs)
     sizes = {k: np.dtype(dt).itemsize for k, dt in gm.REFINE_OUT_DTYPES.items()}
     outs = {k: torch.zeros((n_jobs * sz,), dtype=torch.uint8, device="cuda") for k, sz in sizes.items()}
     work = torch.empty((gm.work_bytes(n_jobs),), dtype=torch.uint8, device="cuda")
@@ -65,7 +47,7 @@ def refine_case(ctx, ext, reps, w, h, chess, n_jobs, wmtype, n_refinements):
     ctx.sync()
     first = {k: t.cpu().numpy().copy() for k, t in outs.items()}
     assert not first["status"].any(), first["status"]
-    r = timed(ctx, ext, reps, launch)
+    r = ms_fields(perf_common.timed(ctx, ext, reps, launch))
     assert all(np.array_equal(first[k], t.cpu().numpy()) for k, t in outs.items()), "two runs differ"
     best, sad = first["best_error"].view("<i8"), first["pic_sad"].view("<u4")
     r.update(what="gm_refine", picture=f"{w}x{h}", chess=chess, jobs=n_jobs, wmtype=wmtype, refinements=n_refinements, launches=3 + 2 * (6 * n_refinements + 1),
@@ -83,7 +65,7 @@ def corr_case(ctx, ext, reps, w, h, method):
               "stationary_block_present_sb": rng.integers(0, 2, (nb, 1)).astype(np.uint8), "rc_me_allow_gm": rng.integers(0, 2, (nb, 1)).astype(np.uint8)}
     me, keep = abi.MeResults(), []
     for name in gm.ME_ARRAYS:
-        keep.append(gm._dev(arrays[name]))
+        keep.append(api.to_device(arrays[name]))
         setattr(me, name, keep[-1].data_ptr())
     pairs = [(0, 0), (1, 0)]
     outs = gm.run_gm_correspondence_device(ctx, pic, method, 0, pairs, me)
@@ -91,17 +73,14 @@ def corr_case(ctx, ext, reps, w, h, method):
     cap = outs["corr"].shape[1]
     d = gm.corr_desc(pic, method, 0, pairs, cap, me, outs["corr"].data_ptr(), outs["count"].data_ptr(), outs["sums"].data_ptr())
     import ctypes as C
-    r = timed(ctx, ext, reps, lambda: ctx.check(api.lib().svt_hip_gm_correspondence_batch(ctx._h, C.byref(d)), "svt_hip_gm_correspondence_batch"))
+    r = ms_fields(perf_common.timed(ctx, ext, reps, lambda: ctx.check(api.lib().svt_hip_gm_correspondence_batch(ctx._h, C.byref(d)), "svt_hip_gm_correspondence_batch")))
     r.update(what="gm_correspondence", picture=f"{w}x{h}", method=method, pairs=len(pairs), blocks=cap, kept=outs["count"].cpu().numpy().tolist())
     return r
 
 
 def main():
     import torch
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 20)
     ctx = api.Context()
     ext = torch.cuda.ExternalStream(ctx.stream)
     rows = []
@@ -110,14 +89,12 @@ def main():
             (1920, 1080, 0, 2, gc.ROTZOOM, 0)]
     for w, h, chess, n, t, nr in plan:
         rows.append(refine_case(ctx, ext, a.reps, w, h, chess, n, t, nr))
-        print(json.dumps(rows[-1]), flush=True)
+        perf_common.emit(rows[-1])
     for method in (gc.MV_8x8, gc.MV_16x16):
         rows.append(corr_case(ctx, ext, a.reps, 3840, 2160, method))
-        print(json.dumps(rows[-1]), flush=True)
+        perf_common.emit(rows[-1])
     ctx.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(json.dumps(r) for r in rows) + "\n")
+    perf_common.write_lines(a.out, [json.dumps(r) for r in rows])
 
 
 if __name__ == "__main__":

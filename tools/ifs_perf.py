@@ -9,47 +9,18 @@ distortion when psy is on) of every block -- 18 launches, and the cost and the c
 process, a fused launch and a composed search in alternation: HIP events around each on the context stream, 5 warm-up rounds, --reps timed ones:
 median, quartiles, minimum, maximum.  Four blocks of every fused batch are compared with the restatement of tests/ifs_cases.py after the timed
 launches, and the composed search's SSE / psy columns of those blocks with the same restatement.  Prints a table (and, with --out, writes it)."""
-import argparse
 import ctypes as C
-import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import ifs_cases as ic  # noqa: E402
 from svt_av1_psyex_amd import abi, api, ifs, pred  # noqa: E402
 
 W, H, PAD = 3840, 2160, 160
 MV = (13, -11)
-
-
-def summary(ms):
-    q = statistics.quantiles(ms, n=4)
-    return dict(median=statistics.median(ms), q1=q[0], q3=q[2], min=min(ms), max=max(ms))
-
-
-def timed_alternating(ctx, ext, reps, launches):
-    """{name: summary}: every round runs each launch once, in order, each between two events of its own"""
-    import torch
-    for _ in range(5):
-        for _, launch in launches:
-            launch()
-    ctx.sync()
-    ms = {name: [] for name, _ in launches}
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            for name, launch in launches:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                launch()
-                e1.record()
-                e1.synchronize()
-                ms[name].append(e0.elapsed_time(e1))
-    ctx.sync()
-    return {name: summary(v) for name, v in ms.items()}
 
 
 def make_jobs(size):
@@ -69,10 +40,7 @@ def make_jobs(size):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the table to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 30, "also write the table to this file")
     import torch
     L = api.lib()
     ctx = api.Context(0)
@@ -123,7 +91,8 @@ def main():
                         pred.run_inter_pred_device(ctx, bd, 0, 0, refs, t_tmp, W, pj[k], n, t_st)
                         ctx.check(L.svt_hip_block_stats_batch(ctx._h, C.byref(descs[k])), "svt_hip_block_stats_batch")
 
-                t = timed_alternating(ctx, ext, a.reps, [("svt_hip_ifs_batch", fused), ("9 x (inter_pred + block_stats)", composed)])
+                ms = perf_common.timed_rounds(ctx, ext, a.reps, [("svt_hip_ifs_batch", fused), ("9 x (inter_pred + block_stats)", composed)])
+                t = {k: perf_common.quartiles(v) for k, v in ms.items()}
                 if t_st.cpu().numpy().any():
                     raise SystemExit(f"{bd} {size}: a job reported a status other than 0")
                 for what, r in t.items():
@@ -148,9 +117,7 @@ def main():
     lines += ["", "fused / composed (medians):"] + ["   " + "   ".join(ratios[k:k + 3]) for k in range(0, len(ratios), 3)]
     print("\n".join(lines[-6:]), flush=True)
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        open(a.out, "w").write("\n".join(lines) + "\n")
+    perf_common.write_lines(a.out, lines)
 
 
 if __name__ == "__main__":

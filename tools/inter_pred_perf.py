@@ -9,38 +9,21 @@ stages them, plus the samples it writes; the job records and status bytes on top
 Beside it: svt_hip_fullpel_pred_batch on the same picture (one reference, random full-pel MVs per 16x16 PU) -- the full-pel batches move the
 same bytes, so its time is what they are measured against -- and the PCIe bytes the host path would move: the prediction up, per candidate
 (2 bytes per sample).  Prints one JSON line per batch (and, with --out, writes the figures as JSON)."""
-import argparse
 import ctypes as C
-import json
-import os
 import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import inter_pred_cases as ip  # noqa: E402
 from svt_av1_psyex_amd import abi, api, pred  # noqa: E402
 
 W, H, PAD = 3840, 2160, 160
 
 
-def timed(ctx, ext, reps, launch):
-    import torch
-    for _ in range(5):
-        launch()
-    ctx.sync()
-    ms = []
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ctx.sync()
+def median_min(ms):
     return statistics.median(ms), min(ms)
 
 
@@ -71,10 +54,7 @@ def traffic(jobs, size, kind):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the figures as JSON to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 30)
     import torch
     L = api.lib()
     ctx = api.Context(0)
@@ -95,7 +75,7 @@ def main():
                                   status=t_status.data_ptr())
             d.refs[0], d.refs[1] = refs
             torch.cuda.synchronize()
-            ms, ms_min = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_inter_pred_batch(ctx._h, C.byref(d)), "svt_hip_inter_pred_batch"))
+            ms, ms_min = median_min(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_inter_pred_batch(ctx._h, C.byref(d)), "svt_hip_inter_pred_batch")))
             got = t_dst.cpu().numpy().view(np.uint16).reshape(H, W)
             if t_status.cpu().numpy().any():
                 raise SystemExit(f"{size} {kind}: a job reported a status other than 0")
@@ -108,7 +88,7 @@ def main():
             res = dict(entry="svt_hip_inter_pred_batch", block=size, kind=kind, jobs=n, ms_median=round(ms, 4), ms_min=round(ms_min, 4), bytes_read=rd_b,
                        bytes_written=wr_b, gb_per_s=round((rd_b + wr_b) / ms / 1e6, 1), host_path_pcie_bytes_up=n * size * size * 2)
             results.append(res)
-            print(json.dumps(res), flush=True)
+            perf_common.emit(res)
     # the copy kernel on the same picture: one reference, random full-pel MVs per 16x16 PU
     nb = ((W + 63) // 64) * ((H + 63) // 64)
     mvx, mvy = rng.integers(-128, 129, (nb, 8, 85)), rng.integers(-128, 129, (nb, 8, 85))
@@ -117,18 +97,16 @@ def main():
     pj = (abi.PredJob * 1)()
     pj[0].ref, pj[0].sb_best_mv, pj[0].pred = t_ref.data_ptr(), t_mv.data_ptr(), t_dst.data_ptr()
     torch.cuda.synchronize()
-    ms, ms_min = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_fullpel_pred_batch(ctx._h, W, W, H, 10, W, 1, pj), "svt_hip_fullpel_pred_batch"))
+    ms, ms_min = median_min(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_fullpel_pred_batch(ctx._h, W, W, H, 10, W, 1, pj), "svt_hip_fullpel_pred_batch")))
     res = dict(entry="svt_hip_fullpel_pred_batch", block=16, kind="fullpel", jobs=(W // 16) * (H // 16), ms_median=round(ms, 4), ms_min=round(ms_min, 4),
                bytes_read=W * H * 2, bytes_written=W * H * 2, gb_per_s=round(W * H * 4 / ms / 1e6, 1))
     results.append(res)
-    print(json.dumps(res), flush=True)
+    perf_common.emit(res)
     for r in results[:-1]:
         if r["kind"] == "fullpel":
-            print(json.dumps(dict(block=r["block"], fullpel_over_copy_kernel=round(r["ms_median"] / ms, 2))), flush=True)
+            perf_common.emit(dict(block=r["block"], fullpel_over_copy_kernel=round(r["ms_median"] / ms, 2)))
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        json.dump(results, open(a.out, "w"), indent=1)
+    perf_common.write_json(a.out, results)
 
 
 if __name__ == "__main__":

@@ -10,17 +10,13 @@ every batch is compared with the restatement of tests/intra_pred_cases.py.  Per 
 two bytes each, the job records, the samples and status bytes written) and the GB/s that makes.  Beside it: svt_hip_fullpel_pred_batch on the
 same picture, which writes the same plane with no arithmetic -- the floor the ratios are taken against -- and the PCIe bytes the host path
 would move: the prediction up, per candidate (2 bytes per sample).  Prints one JSON line per batch (and, with --out, writes them as JSON)."""
-import argparse
 import ctypes as C
-import json
-import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import intra_pred_cases as ic  # noqa: E402
 from svt_av1_psyex_amd import abi, api  # noqa: E402
 
@@ -28,23 +24,8 @@ W, H = 3840, 2160
 TX_OF = {16: 2, 32: 3, 64: 4}
 
 
-def timed(ctx, ext, reps, launch):
-    import torch
-    for _ in range(5):
-        launch()
-    ctx.sync()
-    ms = []
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ctx.sync()
-    q = statistics.quantiles(ms, n=4)
-    return dict(ms_median=round(statistics.median(ms), 4), ms_q1=round(q[0], 4), ms_q3=round(q[2], 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4))
+def ms_fields(ms):
+    return {f"ms_{k}": round(v, 4) for k, v in perf_common.quartiles(ms).items()}
 
 
 def make_jobs(rng, size, mix):
@@ -73,10 +54,7 @@ def traffic(jobs, size):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the figures as JSON to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 30)
     import torch
     L = api.lib()
     ctx = api.Context(0)
@@ -97,7 +75,7 @@ def main():
             d = abi.IntraPredDesc(bit_depth=10, disable_edge_filter=0, n_jobs=n, nbr=t_nbr.data_ptr(), nbr_stride=W, nbr_width=W, nbr_height=H,
                                   dst=t_dst.data_ptr(), dst_stride=W, dst_samples=W * H, jobs=t_jobs.data_ptr(), status=t_status.data_ptr())
             torch.cuda.synchronize()
-            t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_intra_pred_batch(ctx._h, C.byref(d)), "svt_hip_intra_pred_batch"))
+            t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_intra_pred_batch(ctx._h, C.byref(d)), "svt_hip_intra_pred_batch")))
             got = t_dst.cpu().numpy().view(np.uint16).reshape(H, W)
             if t_status.cpu().numpy().any():
                 raise SystemExit(f"{size} {mix}: a job reported a status other than 0")
@@ -110,7 +88,7 @@ def main():
             res = dict(entry="svt_hip_intra_pred_batch", block=size, mix=mix, jobs=n, **t, bytes_read=rd_b, bytes_written=wr_b,
                        gb_per_s=round((rd_b + wr_b) / t["ms_median"] / 1e6, 1), host_path_pcie_bytes_up=n * size * size * 2)
             results.append(res)
-            print(json.dumps(res), flush=True)
+            perf_common.emit(res)
     # the copy kernel on the same picture: one reference, random full-pel MVs per 16x16 PU
     nb = ((W + 63) // 64) * ((H + 63) // 64)
     mvx, mvy = rng.integers(-128, 129, (nb, 8, 85)), rng.integers(-128, 129, (nb, 8, 85))
@@ -118,18 +96,16 @@ def main():
     pj = (abi.PredJob * 1)()
     pj[0].ref, pj[0].sb_best_mv, pj[0].pred = t_nbr.data_ptr(), t_mv.data_ptr(), t_dst.data_ptr()
     torch.cuda.synchronize()
-    t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_fullpel_pred_batch(ctx._h, W, W, H, 10, W, 1, pj), "svt_hip_fullpel_pred_batch"))
+    t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_fullpel_pred_batch(ctx._h, W, W, H, 10, W, 1, pj), "svt_hip_fullpel_pred_batch")))
     floor = dict(entry="svt_hip_fullpel_pred_batch", block=16, mix="copy", jobs=(W // 16) * (H // 16), **t, bytes_read=W * H * 2, bytes_written=W * H * 2,
                  gb_per_s=round(W * H * 4 / t["ms_median"] / 1e6, 1))
-    print(json.dumps(floor), flush=True)
+    perf_common.emit(floor)
     for r in results:
         r["over_copy_kernel"] = round(r["ms_median"] / floor["ms_median"], 2)
-        print(json.dumps(dict(block=r["block"], mix=r["mix"], over_copy_kernel=r["over_copy_kernel"])), flush=True)
+        perf_common.emit(dict(block=r["block"], mix=r["mix"], over_copy_kernel=r["over_copy_kernel"]))
     results.append(floor)
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        json.dump(results, open(a.out, "w"), indent=1)
+    perf_common.write_json(a.out, results)
 
 
 if __name__ == "__main__":

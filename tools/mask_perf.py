@@ -10,40 +10,21 @@ Searches, on the same tilings, 10-bit: svt_hip_mask_search_batch kind 0 (8x8 / 1
 HIP events around each launch on the context stream, 5 warm-up launches, the median of --reps with the quartiles, minimum and maximum.  After
 the timed launches a sample of the jobs of every batch is compared with the restatement of tests/mask_cases.py.  Prints one JSON line per
 measurement (and, with --out, writes them as JSON)."""
-import argparse
 import ctypes as C
-import json
-import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import mask_cases as mc  # noqa: E402
 from svt_av1_psyex_amd import abi, api, mask, pred  # noqa: E402
 
 LW, LH, PAD = 3840, 2160, 80
 
 
-def timed(ctx, ext, reps, launch):
-    import torch
-    for _ in range(5):
-        launch()
-    ctx.sync()
-    ms = []
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ctx.sync()
-    q = statistics.quantiles(ms, n=4)
-    return dict(ms_median=round(statistics.median(ms), 4), ms_q1=round(q[0], 4), ms_q3=round(q[2], 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4))
+def ms_fields(ms):
+    return {f"ms_{k}": round(v, 4) for k, v in perf_common.quartiles(ms).items()}
 
 
 def grid(size):
@@ -62,10 +43,7 @@ def pred_fields(jobs, size):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the figures as JSON to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 30)
     import torch
     L = api.lib()
     ctx = api.Context(0)
@@ -82,7 +60,7 @@ def main():
     results = []
 
     def report(**kw):
-        print(json.dumps(kw), flush=True)
+        perf_common.emit(kw)
         results.append(kw)
 
     # ---- prediction
@@ -99,7 +77,7 @@ def main():
                 t_jobs = dev(jobs)
                 torch.cuda.synchronize()
                 d = pred.run_inter_pred_device(ctx, 10, 0, 0, refs, t_dst, LW, t_jobs, n, t_status)
-                t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_inter_pred_batch(ctx._h, C.byref(d)), "svt_hip_inter_pred_batch"))
+                t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_inter_pred_batch(ctx._h, C.byref(d)), "svt_hip_inter_pred_batch")))
             else:
                 jobs = np.zeros(n, abi.MASKED_PRED_JOB_DTYPE)
                 pred_fields(jobs["pred"], size)
@@ -109,7 +87,7 @@ def main():
                 t_jobs = dev(jobs)
                 torch.cuda.synchronize()
                 d = mask.run_masked_pred_device(ctx, 10, 0, 0, 0, refs, t_dst, LW, t_jobs, n, t_status, mask_buf=t_mask)
-                t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_masked_pred_batch(ctx._h, C.byref(d)), "svt_hip_masked_pred_batch"))
+                t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_masked_pred_batch(ctx._h, C.byref(d)), "svt_hip_masked_pred_batch")))
                 got = t_dst.cpu().numpy().view(np.uint16).reshape(LH, LW)
                 b = {"bit_depth": 10, "ss_x": 0, "ss_y": 0, "plane": 0, "planes": rplanes, "mv_array": None, "results": None, "dst_shape": (LH, LW), "dst_stride": LW}
                 for i in np.linspace(0, n - 1, 6).astype(int):  # a sample of the jobs against the restatement
@@ -145,7 +123,7 @@ def main():
             t_jobs = dev(jobs)
             torch.cuda.synchronize()
             d = mask.run_mask_search_device(ctx, 10, 0, t_src, LW, t_p0, LW, t_p1, LW, t_p0, LW, t_jobs, n, t_res, t_status)
-            t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_mask_search_batch(ctx._h, C.byref(d)), "svt_hip_mask_search_batch"))
+            t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_mask_search_batch(ctx._h, C.byref(d)), "svt_hip_mask_search_batch")))
             got = t_res.cpu().numpy().view(abi.MASK_SEARCH_RESULT_DTYPE)
             if t_status.cpu().numpy().any():
                 raise SystemExit(f"search kind {kind} {size}x{size}: a job reported a status other than 0")
@@ -163,14 +141,12 @@ def main():
         db = abi.BlockStatsDesc(bit_depth=10, n_jobs=n, src_stride=LW, ref_stride=LW, src=t_src.data_ptr(), ref=t_p1.data_ptr(), jobs=t_bjobs.data_ptr(),
                                 sse=t_sse.data_ptr())
         torch.cuda.synchronize()
-        t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_block_stats_batch(ctx._h, C.byref(db)), "svt_hip_block_stats_batch"))
+        t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_block_stats_batch(ctx._h, C.byref(db)), "svt_hip_block_stats_batch")))
         report(entry="svt_hip_block_stats_batch (SSE)", block=size, jobs=n, **t, us_per_launch=round(t["ms_median"] * 1e3, 1),
                ns_per_sample=round(t["ms_median"] * 1e6 / (n * size * size), 4))
         report(block=size, **{f"kind{k}_over_sse": round(v / t["ms_median"], 2) for k, v in medians.items()})
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        json.dump(results, open(a.out, "w"), indent=1)
+    perf_common.write_json(a.out, results)
 
 
 if __name__ == "__main__":

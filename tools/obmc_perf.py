@@ -7,40 +7,18 @@ svt_hip_inter_pred_batch's single-reference prediction of the same blocks with t
 plane is padded by 160 samples.  HIP events around each launch on the context stream, 5 warm-up launches, --reps timed ones: median, quartiles,
 minimum, maximum.  Six blocks of every batch are compared with the restatement of tests/obmc_cases.py after the timed launches (the blend on a copy of
 the prediction: a timed blend launch works in place on what the launch before it left, which costs the same).  Prints a table (and, with --out, writes it)."""
-import argparse
-import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import inter_pred_cases as ip  # noqa: E402
 import obmc_cases as oc  # noqa: E402
 from svt_av1_psyex_amd import abi, api, obmc, pred  # noqa: E402
 
 W, H, PAD = 3840, 2160, 160
 MV_A, MV_L = (13, -11), (-5, 19)
-
-
-def timed(ctx, ext, reps, launch):
-    import torch
-    for _ in range(5):
-        launch()
-    ctx.sync()
-    ms = []
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ctx.sync()
-    q = statistics.quantiles(ms, n=4)
-    return dict(median=statistics.median(ms), q1=q[0], q3=q[2], min=min(ms), max=max(ms))
 
 
 def make_blocks(size):
@@ -112,7 +90,7 @@ def search_timings(ctx, ext, reps, dev):
             p = sc.params(level, 0, 1, 8, 1)
             runs.append((what, lambda p=p: obmc.run_search_device(ctx, p, t_ref, W + 2 * PAD, t_wsrc, t_mask, t_oj, n, t_best, t_res, t_st, tables=t_tab)))
         for what, launch in runs:
-            t[what] = r = timed(ctx, ext, reps, launch)
+            t[what] = r = perf_common.quartiles(perf_common.timed(ctx, ext, reps, launch))
             out.append(f"{what:<40}{size:>6}{n:>8}{r['median']:>9.4f}{r['q1']:>9.4f}{r['q3']:>9.4f}{r['min']:>9.4f}{r['max']:>9.4f}{r['median'] * 1e3 / n:>14.4f}")
             print(out[-1], flush=True)
         if t_st.cpu().numpy().any():
@@ -131,10 +109,7 @@ def search_timings(ctx, ext, reps, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the table to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 30, "also write the table to this file")
     import torch
     ctx = api.Context(0)
     ext = torch.cuda.ExternalStream(ctx.stream, device="cuda:0")
@@ -165,7 +140,7 @@ def main():
                 ("svt_hip_obmc_target_batch", lambda: obmc.run_target_device(ctx, 10, t_blocks, n, t_tjobs, n, t_above, t_left, t_src, W, t_wsrc, t_mask, t_st))]
         t = {}
         for what, launch in runs:
-            t[what] = r = timed(ctx, ext, a.reps, launch)
+            t[what] = r = perf_common.quartiles(perf_common.timed(ctx, ext, a.reps, launch))
             if t_st.cpu().numpy().any():
                 raise SystemExit(f"{size} {what}: a job reported a status other than 0")
             lines.append(f"{what:<40}{size:>6}{n:>8}{r['median']:>9.4f}{r['q1']:>9.4f}{r['q3']:>9.4f}{r['min']:>9.4f}{r['max']:>9.4f}{r['median'] * 1e6 / (n * size * size):>14.4f}")
@@ -201,9 +176,7 @@ def main():
     print("\n".join(lines[-2:]), flush=True)
     lines += search_timings(ctx, ext, a.reps, dev)
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        open(a.out, "w").write("\n".join(lines) + "\n")
+    perf_common.write_lines(a.out, lines)
 
 
 if __name__ == "__main__":

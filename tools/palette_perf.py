@@ -9,45 +9,16 @@ rounds; a host that enqueues all 14 slots blindly pays for the refusals as well:
 HIP events around each launch on the context stream, 5 warm-up rounds, --reps timed ones, the two launches in alternation: median, quartiles,
 minimum, maximum, and the median per job.  Three blocks of every search batch are compared with the restatement of tests/palette_cases.py after
 the timed launches.  Prints a table (and, with --out, writes it)."""
-import argparse
-import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import palette_cases as pc  # noqa: E402
 from svt_av1_psyex_amd import abi, api, palette  # noqa: E402
 
 W, H = 1920, 1088
-
-
-def summary(ms):
-    q = statistics.quantiles(ms, n=4)
-    return dict(median=statistics.median(ms), q1=q[0], q3=q[2], min=min(ms), max=max(ms))
-
-
-def timed_alternating(ctx, ext, reps, launches):
-    """{name: summary}: every round runs each launch once, in order, each between two events of its own"""
-    import torch
-    for _ in range(5):
-        for _, launch in launches:
-            launch()
-    ctx.sync()
-    ms = {name: [] for name, _ in launches}
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            for name, launch in launches:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                launch()
-                e1.record()
-                e1.synchronize()
-                ms[name].append(e0.elapsed_time(e1))
-    ctx.sync()
-    return {name: summary(v) for name, v in ms.items()}
 
 
 def make_plane(rng, bd, size, k):
@@ -70,10 +41,7 @@ def make_plane(rng, bd, size, k):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=None, help="also write the table to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 20, "also write the table to this file")
     import torch
     ctx = api.Context(0)
     ext = torch.cuda.ExternalStream(ctx.stream, device="cuda:0")
@@ -110,7 +78,8 @@ def main():
                 def predict():
                     palette.run_pred_device(ctx, bd, t_src, W, t_dst, size, t_jobs, t_res, t_st, n, t_pj, m, t_pst)
 
-                t = timed_alternating(ctx, ext, a.reps, [("svt_hip_palette_search_batch", search), ("svt_hip_palette_pred_batch", predict)])
+                ms = perf_common.timed_rounds(ctx, ext, a.reps, [("svt_hip_palette_search_batch", search), ("svt_hip_palette_pred_batch", predict)])
+                t = {k: perf_common.quartiles(v) for k, v in ms.items()}
                 if t_st.cpu().numpy().any() or t_pst.cpu().numpy().any():
                     raise SystemExit(f"{bd} {size} {k}: a job reported a status other than 0")
                 for what, r in t.items():
@@ -126,9 +95,7 @@ def main():
                     if got.tobytes() != want.tobytes():
                         raise SystemExit(f"{bd} {size} {k}: block {i} differs from the restatement")
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        open(a.out, "w").write("\n".join(lines) + "\n")
+    perf_common.write_lines(a.out, lines)
 
 
 if __name__ == "__main__":

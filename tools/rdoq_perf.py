@@ -9,17 +9,14 @@ median of --reps.  Also printed: the bytes RDOQ on the host would move in the mi
 coefficient) and qcoeff and dqcoeff up again (8 bytes per coefficient), eob both ways -- against the HIP-event time.  The tables are the
 default-probability tables of tests/golden/coeff_rate.npz; the results are compared with the restatement of tests/rdoq_cases.py on a sample of
 the jobs.  Prints one JSON line per size (and, with --out, writes the figures as JSON)."""
-import argparse
 import ctypes as C
-import json
-import os
 import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import coeff_rate_cases as cr  # noqa: E402
 import rdoq_cases as rq  # noqa: E402
 from svt_av1_psyex_amd import abi, api, rate, rd  # noqa: E402
@@ -29,34 +26,12 @@ GROUP = 16
 LAMBDA = 41000
 
 
-def timed(ctx, ext, reps, launch, prepare=None):
-    import torch
-    for _ in range(5):
-        if prepare:
-            with torch.cuda.stream(ext):
-                prepare()
-        launch()
-    ctx.sync()
-    ms = []
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            if prepare:
-                prepare()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ctx.sync()
+def median_min(ms):
     return statistics.median(ms), min(ms)
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the figures as JSON to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 30)
     import torch
     L = api.lib()
     ctx = api.Context(0)
@@ -101,15 +76,17 @@ def main():
                               dist_stride=2, dist=outs["dist_coeff"].data_ptr(), rd_cost=t_cost.data_ptr(), group_start=t_gs.data_ptr(),
                               best_job=t_bj.data_ptr(), best_cost=t_bc.data_ptr())
         torch.cuda.synchronize()
-        rd_ms, rd_min = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_rd_batch(ctx._h, C.byref(d)), "svt_hip_rd_batch"))
+        rd_ms, rd_min = median_min(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_rd_batch(ctx._h, C.byref(d)), "svt_hip_rd_batch")))
         keep = {name: outs[name].clone() for name in ("qcoeff", "dqcoeff", "eob", "dist_coeff")}  # the RD batch's own: every RDOQ launch starts here
         torch.cuda.synchronize()
 
         def restore():
             for name, t in keep.items():
                 outs[name].copy_(t)
-        rdoq_ms, rdoq_min = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_rdoq_batch(ctx._h, C.byref(o)), "svt_hip_rdoq_batch"), restore)
-        rate_ms, rate_min = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_coeff_rate_batch(ctx._h, C.byref(r)), "svt_hip_coeff_rate_batch"))
+        # the batch works in place: every round puts the inputs back first, between events of its own that are not reported
+        rounds = [("restore", restore), ("rdoq", lambda: ctx.check(L.svt_hip_rdoq_batch(ctx._h, C.byref(o)), "svt_hip_rdoq_batch"))]
+        rdoq_ms, rdoq_min = median_min(perf_common.timed_rounds(ctx, ext, a.reps, rounds)["rdoq"])
+        rate_ms, rate_min = median_min(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_coeff_rate_batch(ctx._h, C.byref(r)), "svt_hip_coeff_rate_batch")))
         # a sample of the jobs against the restatement
         pick = np.linspace(0, n - 1, 48).astype(int)
         view = lambda t, dt, k: t.cpu().numpy().view(dt).reshape(n, k)[pick]
@@ -127,11 +104,9 @@ def main():
                    rdoq_ms_median=round(rdoq_ms, 4), rdoq_ms_min=round(rdoq_min, 4), rate_ms_median=round(rate_ms, 4), rate_ms_min=round(rate_min, 4),
                    rdoq_over_rd=round(rdoq_ms / rd_ms, 3), download_bytes=n * (npk * 12 + 2), upload_bytes=n * (npk * 8 + 2))
         results.append(res)
-        print(json.dumps(res), flush=True)
+        perf_common.emit(res)
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        json.dump(results, open(a.out, "w"), indent=1)
+    perf_common.write_json(a.out, results)
 
 
 if __name__ == "__main__":

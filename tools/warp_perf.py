@@ -10,40 +10,21 @@ and once: svt_hip_warp_model_batch on one fit per 8x8 block, and svt_hip_wm_refi
 diagonals and at 16 with, each with one wave and with four waves per job.  HIP events around each launch on the context stream, 5 warm-up launches,
 the median of --reps with the quartiles, minimum and maximum.  A sample of the jobs of every warp batch is compared with the restatement of
 tests/warp_cases.py.  Prints one JSON line per measurement (and, with --out, writes them as JSON)."""
-import argparse
 import ctypes as C
-import json
-import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import perf_common
+
+perf_common.repo_paths()
 import warp_cases as wc  # noqa: E402
 from svt_av1_psyex_amd import abi, api, pred, warp  # noqa: E402
 
 LW, LH, PAD = 3840, 2160, 80
 
 
-def timed(ctx, ext, reps, launch):
-    import torch
-    for _ in range(5):
-        launch()
-    ctx.sync()
-    ms = []
-    with torch.cuda.stream(ext):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    ctx.sync()
-    q = statistics.quantiles(ms, n=4)
-    return dict(ms_median=round(statistics.median(ms), 4), ms_q1=round(q[0], 4), ms_q3=round(q[2], 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4))
+def ms_fields(ms):
+    return {f"ms_{k}": round(v, 4) for k, v in perf_common.quartiles(ms).items()}
 
 
 def grid(size):
@@ -81,10 +62,7 @@ def inter_jobs(size):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=None, help="also write the figures as JSON to this file")
-    a = ap.parse_args()
+    a = perf_common.arguments(__doc__, 30)
     import torch
     L = api.lib()
     ctx = api.Context(0)
@@ -100,7 +78,7 @@ def main():
     results = []
 
     def report(**kw):
-        print(json.dumps(kw), flush=True)
+        perf_common.emit(kw)
         results.append(kw)
 
     for size in (8, 16, 32, 64):
@@ -114,13 +92,13 @@ def main():
                 t_jobs = dev(jobs)
                 torch.cuda.synchronize()
                 d = pred.run_inter_pred_device(ctx, 10, 0, 0, irefs[:1], t_dst, LW, t_jobs, n, t_status)
-                t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_inter_pred_batch(ctx._h, C.byref(d)), "svt_hip_inter_pred_batch"))
+                t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_inter_pred_batch(ctx._h, C.byref(d)), "svt_hip_inter_pred_batch")))
             else:
                 jobs = warp_jobs(size, models, what == "warp_compound")
                 t_jobs = dev(jobs)
                 torch.cuda.synchronize()
                 d = warp.run_warp_pred_device(ctx, 10, 0, 0, wrefs, t_dst, LW, t_jobs, n, t_status)
-                t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_warp_pred_batch(ctx._h, C.byref(d)), "svt_hip_warp_pred_batch"))
+                t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_warp_pred_batch(ctx._h, C.byref(d)), "svt_hip_warp_pred_batch")))
                 got = t_dst.cpu().numpy().view(np.uint16).reshape(LH, LW)
                 b = dict(bit_depth=10, ss_x=0, ss_y=0, planes=[(p, PAD, PAD, LW, LH) for p in planes], dst_shape=(LH, LW), dst_stride=LW)
                 for i in np.linspace(0, n - 1, 6).astype(int):  # a sample of the jobs against the restatement
@@ -136,7 +114,7 @@ def main():
         t_from, t_to = torch.zeros(wr_b, dtype=torch.uint8, device="cuda"), torch.zeros(wr_b, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         with torch.cuda.stream(ext):
-            c = timed(ctx, ext, a.reps, lambda: t_to.copy_(t_from))
+            c = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: t_to.copy_(t_from)))
         report(entry="device_to_device_copy", block=size, bytes=wr_b, **c)
         report(block=size, warp_over_inter_pred=round(medians["warp_single"] / medians["inter_pred"], 2),
                compound_over_single=round(medians["warp_compound"] / medians["warp_single"], 2), warp_over_copy=round(medians["warp_single"] / c["ms_median"], 2))
@@ -152,7 +130,7 @@ def main():
     t_mstatus = torch.zeros(n, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     dm = warp.run_warp_model_device(ctx, t_mjobs, n, t_models, t_mstatus, 0, 0, 65535)
-    t = timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_warp_model_batch(ctx._h, C.byref(dm)), "svt_hip_warp_model_batch"))
+    t = ms_fields(perf_common.timed(ctx, ext, a.reps, lambda: ctx.check(L.svt_hip_warp_model_batch(ctx._h, C.byref(dm)), "svt_hip_warp_model_batch")))
     got = t_models.cpu().numpy().view(abi.WARP_MODEL_DTYPE)
     for i in np.linspace(0, n - 1, 50).astype(int):
         if got[i].tobytes() != wc.fit_model(mjobs[i], (int(mjobs[i]["mv"][0]), int(mjobs[i]["mv"][1])), 0, 0, 65535).tobytes():
@@ -183,7 +161,7 @@ def main():
                 dsc = warp.refine_desc(n, settings, rrefs, t_src8.data_ptr(), LW, LW * LH, t_rjobs.data_ptr(), {k: v.data_ptr() for k, v in outs.items()}, None, 0,
                                        [x.data_ptr() for x in t_cost], waves)
                 torch.cuda.synchronize()
-                t = timed(ctx, ext, max(5, a.reps // 3), lambda: ctx.check(L.svt_hip_wm_refine_batch(ctx._h, C.byref(dsc)), "svt_hip_wm_refine_batch"))
+                t = ms_fields(perf_common.timed(ctx, ext, max(5, a.reps // 3), lambda: ctx.check(L.svt_hip_wm_refine_batch(ctx._h, C.byref(dsc)), "svt_hip_wm_refine_batch")))
                 got = {k: v.cpu().numpy().view(warp.REFINE_OUT_DTYPES[k]) for k, v in outs.items()}
                 if got["status"].any():
                     raise SystemExit("a refinement reported a status other than 0")
@@ -199,9 +177,7 @@ def main():
                 report(entry="svt_hip_wm_refine_batch", block=size, jobs=n, iterations=iters, refine_diag=diag, waves_per_job=waves, **t,
                        positions_per_job=round(float(got["n_checked"].mean()), 1), us_per_job=round(t["ms_median"] * 1e3 / n, 3))
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        json.dump(results, open(a.out, "w"), indent=1)
+    perf_common.write_json(a.out, results)
 
 
 if __name__ == "__main__":
