@@ -8,8 +8,9 @@
 // time from their structure (see dct_* below), so every register index and every cosine is a constant.  All
 // arithmetic is the reference's integer arithmetic (32-bit wrapping products, 64-bit rounding: half_btf,
 // Codec/inv_transforms.h:264-285), hence bit-exact.  Elementwise phases (quantizer, distortions) stride the block
-// across the 64 lanes and reduce with shuffles.  Memory traffic per block is the algorithmic minimum: source and
-// prediction read once, outputs written once (HBM-bound by design).
+// across the 64 lanes and reduce inside the wave (DPP where the range allows, see SVT_RD_DPP_REDUCE).  Source and prediction are read
+// twice, once for the residual and once for the reconstruction (the second read is served by the caches); outputs are written once.  The
+// kernels are bound by instruction issue, not by HBM.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -85,6 +86,26 @@ __host__ __device__ constexpr int rd_bounded_btf(int ts) {
 #ifndef SVT_RD_ROW_BOUND_FROM_QUANT
 #define SVT_RD_ROW_BOUND_FROM_QUANT 1 /* a lean-quantizer wave whose bound M on |dqcoeff| passes the clamp-free test skips measuring the row input */
 #endif
+// The cost a lane pays once per block, whatever the block holds (profiles/r23_rd_fixed_cost_before_after.txt):
+#ifndef SVT_RD_DPP_REDUCE
+#define SVT_RD_DPP_REDUCE 1 /* the wave's five magnitudes and the block's sums on DPP and scalar registers, not ds_bpermute butterflies through the LDS crossbar */
+#endif
+#ifndef SVT_RD_RUN_BASE
+#define SVT_RD_RUN_BASE 1 /* a lane's runs of samples addressed from one base per plane plus a wave-uniform multiple of the stride, not by one 64-bit product per run */
+#endif
+// Measured: -5 % at 16x16, -3 % at 64x64.  32x32 sits at its 128-register limit: with the magnitudes on DPP it spills 9 registers more, and with
+// the sums alone it keeps its allocation and its time (+-0.5 %): it keeps the butterflies.  So do the sizes that were not timed (64x16 spills 21
+// registers more with either switch).
+__host__ __device__ constexpr bool rd_square_16_or_64(int ts) { return tx_wide(ts) == tx_high(ts) && (tx_wide(ts) == 16 || tx_wide(ts) == 64); }
+__host__ __device__ constexpr bool rd_dpp_reduce(int ts) { return SVT_RD_DPP_REDUCE && rd_square_16_or_64(ts); }
+// Measured: a further -2 % at 64x64 (eight runs per lane and plane); nothing at 16x16 (two runs); 32x32 spills 9 registers more with it.  The
+// reconstruction forms its bases anew, from a lane index the compiler cannot tell from the first: 64x64 has no registers to keep them through the passes.
+__host__ __device__ constexpr bool rd_run_base(int ts) { return SVT_RD_RUN_BASE && tx_wide(ts) == 64 && tx_high(ts) == 64; }
+// one answer for the wave, in a scalar register; every lane of the wave calls it
+template <bool DPP> __device__ __forceinline__ uint32_t rd_wave_max(uint32_t v) {
+    if constexpr (DPP) return wave_max_dpp(v);
+    else return (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(v));
+}
 __host__ __device__ constexpr bool rd_clamp_free_tier(int ts) {
     return tx_wide(ts) == tx_high(ts) && (SVT_RD_CLAMP_FREE == 1 ? tx_wide(ts) == 64 : SVT_RD_CLAMP_FREE == 2 && tx_wide(ts) >= 16);
 }
@@ -131,9 +152,19 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     // runs of RUN samples per (unaligned) vector load: the planes' offsets and strides are the caller's
     constexpr int RUN = W < 8 ? W : 8, RPR = W / RUN; // run length, runs per row
     typedef Pix __attribute__((ext_vector_type(RUN), aligned(sizeof(Pix)))) RunU;
+    // A lane's runs lie RSTEP rows apart in one column of runs (i = l + it * LW, LW a multiple of RPR): run `it` of a plane is the lane's first run
+    // plus it * RSTEP * stride samples, a wave-uniform distance
+    static_assert(LW % RPR == 0, "a lane's runs share their column");
+    constexpr int RSTEP = LW / RPR;
+    constexpr bool kRunBase = rd_run_base(TS), kDpp = rd_dpp_reduce(TS);
+    auto first_run = [&](const Pix *plane, uint32_t stride, int lx) { return plane + (size_t)(lx / RPR) * stride + (lx % RPR) * RUN; };
+    auto run_at = [&](bool by_base, const Pix *plane, const Pix *first, uint32_t stride, int it, int r, int c) {
+        return reinterpret_cast<const RunU *>(by_base ? first + (size_t)(it * RSTEP) * stride : plane + (size_t)r * stride + c);
+    };
     uint32_t rmax = 0; // largest |residual| this lane produced
     {
         HiLo rhl;
+        const Pix *src0 = first_run(src, p.d.src_stride, l), *pred0 = first_run(pred, p.d.pred_stride, l);
         // a lane's runs are fetched kResidualAhead at a time, all of a group in flight before the first is used (the loop's trip count depends
         // on the lane: left to itself every run is a round trip of its own)
         constexpr int NIT = (RPR * H + LW - 1) / LW, kResidualAhead = NIT < SVT_RD_RESIDUAL_AHEAD ? NIT : SVT_RD_RESIDUAL_AHEAD;
@@ -144,8 +175,8 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
                 const int i = l + (it0 + j) * LW;
                 if (it0 + j < NIT && i < RPR * H) {
                     const int r = i / RPR, c = (i - r * RPR) * RUN;
-                    sv[j] = *reinterpret_cast<const RunU *>(src + (size_t)r * p.d.src_stride + c);
-                    pv[j] = *reinterpret_cast<const RunU *>(pred + (size_t)r * p.d.pred_stride + c);
+                    sv[j] = *run_at(kRunBase, src, src0, p.d.src_stride, it0 + j, r, c);
+                    pv[j] = *run_at(kRunBase, pred, pred0, p.d.pred_stride, it0 + j, r, c);
                 }
             }
 #pragma unroll
@@ -174,7 +205,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     // one answer for the wave (all its blocks): every residual small enough for the 24-bit multiplies of the forward passes?
     // one answer for the wave (all its blocks): small enough data for the three-instruction butterflies?  The column pass sees the residual
     // shifted up by fsh[0] (0 or 2)
-    const bool fast_col = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(rmax)) << (fsh[0] > 0 ? fsh[0] : 0), H);
+    const bool fast_col = pass_fits_17_bits(rd_wave_max<kDpp>(rmax) << (fsh[0] > 0 ? fsh[0] : 0), H);
     __syncthreads();
     // forward columns (av1_tranform_two_d_core_c, transforms.c:2287-2308)
     uint32_t cmax = 0; // largest |column output| of this lane
@@ -195,7 +226,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         for (int r = 0; r < H; r++) A[r * PA + oc] = x[r];
         cmax = vec_max_abs<H>(x);
     }
-    const bool fast_row = pass_fits_17_bits((uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(cmax)), W); // the row pass's input
+    const bool fast_row = pass_fits_17_bits(rd_wave_max<kDpp>(cmax), W); // the row pass's input
     __syncthreads();
     // forward rows (:2310-2323)
     uint32_t comax = 0; // largest |coefficient| of this lane
@@ -213,7 +244,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         comax = vec_max_abs<W>(x);
     }
     // coefficients below 2^16 in every block of the wave: the quantizer's products fit 24-bit multiplies (see the loop below)
-    const uint32_t comax_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(comax));
+    const uint32_t comax_w = rd_wave_max<kDpp>(comax);
     const bool q24 = comax_w < (1u << 16);
     __syncthreads();
     // 64-point sizes keep the top-left 32x32 (svt_handle_transform*_c, transforms.c:2374-2505)
@@ -228,7 +259,10 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
             const int r = i / W, c = i - r * W;
             if (r >= HP || c >= WP) { const int32_t v = A[r * PA + c]; tq += (u64)((i64)v * v); }
         }
-        tq = group_sum<LW>(tq);
+        // |coefficient| < 2^16 in the wave: a lane's 48 squares sum below 2^38.  The DPP form needs every lane of the wave here: `pf` is the
+        // block's, and a 64-point size has one block per wave (LW == 64), so the branch above is taken by all lanes or by none
+        static_assert(LW == 64, "one block per wave: pf is wave-uniform");
+        tq = (kDpp && q24) ? group_sum64_dpp<LW, 38>(tq) : group_sum<LW>(tq);
     }
     if constexpr (W > 32 || H > 32) __syncthreads(); // the compaction below overwrites discarded coefficients
     // SATD, quantize, coefficient-domain distortion over the kept NP coefficients (packed index rc = r*WP + c).  The
@@ -341,8 +375,14 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         }
         satd -= (uint32_t)(rnd_c[ac0] + (NP / LW - 1) * rnd1);
         eob   = (uint32_t)(last + 1);
-        dres  = dres32;
-        dpred = dpred32;
+        if constexpr (kDpp) {
+            // a lane's sums fit 32 bits (above), a block's need not: they are widened inside the reduction
+            dres  = group_sum_wide_dpp<LW>(dres32);
+            dpred = group_sum_wide_dpp<LW>(dpred32);
+        } else {
+            dres  = dres32;
+            dpred = dpred32;
+        }
     } else if (fast_q) {
         static_assert(NP % LW == 0, "every lane of a block walks the same number of coefficients");
         // The scan positions of a lane's first kScanAhead coefficients (the low frequencies: where the non-zero levels are) are fetched ahead,
@@ -471,11 +511,22 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         if (q_out) q_out[rc] = qs;
         if (dq_out) dq_out[rc] = dqs;
     }
-    satd  = group_sum<LW>(satd);
-    qsum  = group_sum<LW>(qsum);
-    eob   = group_max<LW>(eob);
-    dres  = group_sum<LW>(dres);
-    dpred = group_sum<LW>(dpred);
+    if constexpr (kDpp) {
+        // 32-bit sums (mod 2^32) and a maximum: the same values by either form; the 64-bit sums of the other two loops keep the butterfly
+        satd = group_sum_dpp<LW>(satd);
+        qsum = group_sum_dpp<LW>(qsum);
+        eob  = group_max_dpp<LW>(eob);
+        if (!lean_q) {
+            dres  = group_sum<LW>(dres);
+            dpred = group_sum<LW>(dpred);
+        }
+    } else {
+        satd  = group_sum<LW>(satd);
+        qsum  = group_sum<LW>(qsum);
+        eob   = group_max<LW>(eob);
+        dres  = group_sum<LW>(dres);
+        dpred = group_sum<LW>(dpred);
+    }
     __syncthreads();
     // inverse rows (inv_txfm2d_add_c, inv_transforms.c:2497-2511): discarded frequencies are zero
     int32_t xr[W];
@@ -492,7 +543,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         }
         if (!row_free_q) irmax = vec_max_abs<W>(xr);
     }
-    const uint32_t irmax_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(irmax)); // wave-uniform, as everything decided from it
+    const uint32_t irmax_w = rd_wave_max<kDpp>(irmax); // wave-uniform, as everything decided from it
     const int irow_tier = row_free_q ? 2 : ipass_tier<kFree>(irmax_w, W, ROW_CLAMP);
     uint32_t icmax = 0; // largest |row-pass output|: the column pass's input
     if (l < H) {
@@ -507,7 +558,7 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
         for (int c = 0; c < W; c++) A[l * PA + c] = xr[c];
         icmax = vec_max_abs<W>(xr);
     }
-    const uint32_t icmax_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(icmax));
+    const uint32_t icmax_w = rd_wave_max<kDpp>(icmax);
     const int icol_tier = ipass_tier<kFree>(icmax_w, H, COL_CLAMP);
 #ifdef SVT_RD_TIER_STATS
     if (lane == 0) { atomicAdd(&g_rd_tier_stats[irow_tier * 3 + icol_tier], 1u); if (row_free_q) atomicAdd(&g_rd_tier_stats[9], 1u); }
@@ -535,6 +586,10 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
     __syncthreads();
     {
         Pix *rec = (p.d.recon && valid) ? static_cast<Pix *>(p.d.recon) + jb.pred_offset : nullptr;
+        // the bases of the lane's first runs, formed anew from a lane index the compiler cannot tell from `l`, or it keeps the residual loop's
+        // bases alive through the passes
+        const int lb = kRunBase ? held_in_vgpr(l) : l;
+        const Pix *src0 = first_run(src, p.d.src_stride, lb), *pred0 = first_run(pred, p.d.pred_stride, lb);
         // every run's prediction and source samples are requested BEFORE the first reconstruction run is stored: vector memory operations
         // complete in issue order on this ISA, so a load issued behind a store waits for the store's acknowledgement as well
         constexpr int NIT = (RPR * H + LW - 1) / LW; // runs per lane
@@ -544,8 +599,8 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
             const int i = l + it * LW;
             if (i < RPR * H) {
                 const int r = i / RPR, c = (i - r * RPR) * RUN;
-                pv[it] = *reinterpret_cast<const RunU *>(pred + (size_t)r * p.d.pred_stride + c);
-                sv[it] = *reinterpret_cast<const RunU *>(src + (size_t)r * p.d.src_stride + c);
+                pv[it] = *run_at(kRunBase, pred, pred0, p.d.pred_stride, it, r, c);
+                sv[it] = *run_at(kRunBase, src, src0, p.d.src_stride, it, r, c);
             }
         }
 #pragma unroll
@@ -562,11 +617,12 @@ template <int TS, int BD> __global__ void __launch_bounds__(64, rd_waves_per_sim
                     const int e = (int)sv[it][k] - v;
                     sse += (u64)((uint32_t)e * (uint32_t)e); // |e| < 2^16: the low 32 bits of the (wrapping) product are the square, whatever the sign
                 }
-                if (rec) *reinterpret_cast<RunU *>(rec + (size_t)r * p.d.pred_stride + c) = out;
+                if (rec) *const_cast<RunU *>(run_at(kRunBase, rec, rec + (pred0 - pred), p.d.pred_stride, it, r, c)) = out;
             }
         }
     }
-    sse = group_sum<LW>(sse);
+    if constexpr (kDpp) sse = group_sum64_dpp<LW, 38>(sse); // a lane's W * H / LW <= 64 squares, each below 2^32
+    else sse = group_sum<LW>(sse);
     if (l == 0 && valid) {
         p.d.eob[job]  = (uint16_t)eob;
         p.d.satd[job] = satd;

@@ -82,7 +82,69 @@ __device__ __forceinline__ uint32_t wave_min_dpp(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// maximum: the same steps as wave_min_dpp.  A lane the step does not write takes 0, the identity of the unsigned maximum: with that the step is
+// one v_max_u32 with a DPP operand (with `v` itself as the old value it is a copy, a v_mov_b32_dpp and the maximum)
+template <int CTRL, int ROWS> __device__ __forceinline__ uint32_t dpp_max_step(uint32_t v) {
+    const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xF, ROWS == 0xF);
+    return t > v ? t : v;
+}
+__device__ __forceinline__ uint32_t wave_max_dpp(uint32_t v) {
+    v = dpp_max_step<0xB1, 0xF>(v);  // quad_perm [1,0,3,2]
+    v = dpp_max_step<0x4E, 0xF>(v);  // quad_perm [2,3,0,1]
+    v = dpp_max_step<0x141, 0xF>(v); // row_half_mirror
+    v = dpp_max_step<0x140, 0xF>(v); // row_mirror
+    v = dpp_max_step<0x142, 0xA>(v); // row_bcast:15 -> rows 1, 3
+    v = dpp_max_step<0x143, 0xC>(v); // row_bcast:31 -> rows 2, 3
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
 // ---- DPP forms over a part of the wave, the result in all of its lanes
+// group_sum_dpp<G> / group_max_dpp<G>: what group_sum<G> / group_max<G> return, for G = 4 .. 64 consecutive lanes, EVERY lane of the wave
+// active.  Inside a 16-lane row the steps are DPP operands of the additions themselves; a group of 32 or 64 lanes then takes its rows' results
+// (uniform inside each row) from one lane per row through scalar registers.
+template <int G> __device__ __forceinline__ uint32_t group_sum_dpp(uint32_t v) {
+    static_assert(G == 4 || G == 8 || G == 16 || G == 32 || G == 64, "a quad, half a row, a row, two rows or the wave");
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, true);
+    if constexpr (G >= 8) v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141 /* row_half_mirror */, 0xF, 0xF, true);
+    if constexpr (G >= 16) v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140 /* row_mirror */, 0xF, 0xF, true);
+    if constexpr (G >= 32) {
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
+        const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+        if constexpr (G == 64) v = r0 + r1 + r2 + r3;
+        else v = threadIdx.x < 32 ? r0 + r1 : r2 + r3; // (callers are one-wave workgroups)
+    }
+    return v;
+}
+template <int G> __device__ __forceinline__ uint32_t group_max_dpp(uint32_t v) {
+    static_assert(G == 4 || G == 8 || G == 16 || G == 32 || G == 64, "a quad, half a row, a row, two rows or the wave");
+    v = dpp_max_step<0xB1, 0xF>(v);
+    v = dpp_max_step<0x4E, 0xF>(v);
+    if constexpr (G >= 8) v = dpp_max_step<0x141, 0xF>(v);
+    if constexpr (G >= 16) v = dpp_max_step<0x140, 0xF>(v);
+    if constexpr (G >= 32) {
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
+        const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+        const uint32_t m01 = r0 > r1 ? r0 : r1, m23 = r2 > r3 ? r2 : r3;
+        if constexpr (G == 64) v = m01 > m23 ? m01 : m23;
+        else v = threadIdx.x < 32 ? m01 : m23;
+    }
+    return v;
+}
+// the 64-bit sum of a group's 32-bit values (a lane's own sum fits 32 bits, the group's may not): the two 16-bit halves are summed apart, each
+// below G * 2^16, and joined afterwards
+template <int G> __device__ __forceinline__ uint64_t group_sum_wide_dpp(uint32_t v) {
+    const uint64_t lo = group_sum_dpp<G>(v & 0xFFFFu), hi = group_sum_dpp<G>(v >> 16);
+    return (hi << 16) + lo;
+}
+// a 64-bit sum (mod 2^64) of values below 2^BITS, in pieces of 32 - log2(G) bits: none of them can overflow its 32-bit sum over G lanes
+template <int G, int BITS = 64> __device__ __forceinline__ uint64_t group_sum64_dpp(uint64_t v) {
+    constexpr int P = 32 - (G == 4 ? 2 : G == 8 ? 3 : G == 16 ? 4 : G == 32 ? 5 : 6);
+    uint64_t s = 0;
+#pragma unroll
+    for (int b = 0; b < BITS; b += P) s += (uint64_t)group_sum_dpp<G>((uint32_t)(v >> b) & ((1u << P) - 1u)) << b;
+    return s;
+}
 __device__ __forceinline__ uint32_t quad_sum(uint32_t v) { // the 4 lanes of a quad
     v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
     return v + (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, true);
