@@ -50,7 +50,7 @@ template <class Kernel> Kernel pick_hbd(unsigned bit_depth, Kernel hbd, Kernel l
 // The enqueue itself, on ctx->stream under ctx->async_mu, with one question to the runtime behind all of `launch`'s
 // hipLaunchKernelGGL calls.  An entry that takes an argument list, not a descriptor, calls this after its own checks.
 template <class Launch> int enqueue_locked(const char *entry, SvtHipContext *ctx, Launch launch) {
-    (void)hipSetDevice(ctx->device);
+    if (int rc = svt_hip_use_device(ctx)) return rc;
     std::lock_guard<std::mutex> lock(ctx->async_mu);
     launch();
     const hipError_t e = hipGetLastError();

@@ -83,7 +83,7 @@ int svt_hip_comm_create(SvtHipContext *ctx, const uint8_t id[SVT_HIP_COMM_ID_BYT
     if (!ctx || !id || !out || world < 1 || rank < 0 || rank >= world) return SVT_HIP_ERR_BAD_PARAM;
     *out = nullptr;
     if (int rc = load_rccl(ctx)) return rc;
-    SVT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = svt_hip_use_device(ctx)) return rc;
     SvtHipComm *c = new (std::nothrow) SvtHipComm();
     if (!c) return SVT_HIP_ERR_NO_MEMORY;
     c->ctx = ctx; c->rank = rank; c->world = world;
@@ -107,14 +107,15 @@ int svt_hip_comm_create(SvtHipContext *ctx, const uint8_t id[SVT_HIP_COMM_ID_BYT
 
 void svt_hip_comm_destroy(SvtHipComm *c) {
     if (!c) return;
-    hipSetDevice(c->ctx->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
+    // teardown: nothing below can act on a failure
+    (void)hipSetDevice(c->ctx->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) g_rccl.CommDestroy(c->comm);
     for (int k = 0; k < SVT_HIP_COMM_SLOTS; k++) {
-        if (c->ready[k]) hipEventDestroy(c->ready[k]);
-        if (c->landed[k]) hipEventDestroy(c->landed[k]);
+        if (c->ready[k]) (void)hipEventDestroy(c->ready[k]);
+        if (c->landed[k]) (void)hipEventDestroy(c->landed[k]);
     }
-    if (c->stream) hipStreamDestroy(c->stream);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -122,7 +123,7 @@ void svt_hip_comm_destroy(SvtHipComm *c) {
 // writes `send`); the compute enqueued afterwards on the context stream runs beside the exchange.
 static int exchange_begin(SvtHipComm *c, int slot) {
     if (!c || slot < 0 || slot >= SVT_HIP_COMM_SLOTS) return SVT_HIP_ERR_BAD_PARAM;
-    SVT_HIP_CHECK(c->ctx, hipSetDevice(c->ctx->device));
+    if (int rc = svt_hip_use_device(c->ctx)) return rc;
     SVT_HIP_CHECK(c->ctx, hipEventRecord(c->ready[slot], c->ctx->stream));
     SVT_HIP_CHECK(c->ctx, hipStreamWaitEvent(c->stream, c->ready[slot], 0));
     return SVT_HIP_OK;

@@ -161,7 +161,7 @@ static int dg_launch(SvtHipContext *ctx, hipStream_t stream, const SvtHipPaPictu
     p.metrics = metrics_dev;
     p.b64_sad = b64_sad_dev;
     p.b64_mv  = b64_mv_dev;
-    SVT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = svt_hip_use_device(ctx)) return rc;
     if (int rc = svt_hip_wait_picture(ctx, stream, src)) return rc;
     if (int rc = svt_hip_wait_picture(ctx, stream, ref)) return rc;
     SVT_HIP_CHECK(ctx, hipMemsetAsync(metrics_dev, 0, sizeof(SvtHipDgMetrics), stream));

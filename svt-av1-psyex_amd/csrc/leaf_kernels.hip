@@ -135,7 +135,6 @@ StatsOut leaf_stats(const void *src, size_t src_stride, const void *ref, size_t 
                     bool want_psy = false, double psy_rd = 0.0, int xo = 0, int yo = 0) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     const size_t bpp = bit_depth == 8 ? 1 : 2;
     const int sh = h + (yo ? 1 : 0), sw = w + (xo ? 1 : 0); // the interpolation reads one more row / column
     const size_t sb = align256(((size_t)sh - 1) * src_stride * bpp + (size_t)sw * bpp), rb = align256(((size_t)h - 1) * ref_stride * bpp + (size_t)w * bpp);
@@ -172,7 +171,6 @@ void svt_sad_loop_kernel_hip(uint8_t *src, uint32_t src_stride, uint8_t *ref, ui
                              uint32_t src_stride_raw, uint8_t skip_search_line, int16_t search_area_width, int16_t search_area_height) LEAF_TRY
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     *best_sad = 0xffffff;
     if (search_area_width <= 0 || search_area_height <= 0 || block_height == 0 || block_width == 0) return;
     const size_t sb = align256(((size_t)block_height - 1) * src_stride + block_width);
@@ -299,7 +297,6 @@ LEAF_CATCH(svt_hip_hadamard_path, input, input_stride, pred, pred_stride, block_
 static void leaf_hadamard(const int16_t *src_diff, ptrdiff_t src_stride, int32_t *coeff, int n) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     const size_t sb = align256((((size_t)n - 1) * (size_t)src_stride + n) * 2);
     uint8_t *base = leaf_scratch(ctx, sb + (size_t)n * n * 4);
     leaf_check(ctx, hipMemcpyAsync(base, src_diff, (((size_t)n - 1) * (size_t)src_stride + n) * 2, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
@@ -315,7 +312,6 @@ void svt_aom_hadamard_32x32_hip(const int16_t *src_diff, ptrdiff_t src_stride, i
 int svt_aom_satd_hip(const int32_t *coeff, int length) LEAF_TRY
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     if (length <= 0) return 0;
     const size_t cb = align256((size_t)length * 4);
     uint8_t *base = leaf_scratch(ctx, cb + 256);
@@ -333,7 +329,6 @@ LEAF_CATCH(svt_aom_satd_hip, coeff, length)
 uint8_t svt_av1_compute_cul_level_hip(const int16_t *const scan, const int32_t *const quant_coeff, uint16_t *eob) LEAF_TRY
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     const int n = *eob;
     int       top = 0;
     for (int c = 0; c < n; c++) top = scan[c] > top ? scan[c] : top;
@@ -353,7 +348,6 @@ LEAF_CATCH(svt_av1_compute_cul_level_hip, scan, quant_coeff, eob)
 void svt_av1_fwht4x4_hip(int16_t *input, int32_t *output, uint32_t stride) LEAF_TRY
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     const size_t ib = align256((3 * (size_t)stride + 4) * 2);
     uint8_t *base = leaf_scratch(ctx, ib + 256);
     leaf_check(ctx, hipMemcpyAsync(base, input, (3 * (size_t)stride + 4) * 2, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
@@ -410,7 +404,6 @@ LEAF_CATCH(svt_aom_variance_highbd_hip, a, a_stride, b, b_stride, w, h, sse)
 static void leaf_coeff_dist(const int32_t *coeff, uint32_t cstride, const int32_t *recon, uint32_t rstride, uint32_t w, uint32_t h, uint64_t out[2], int wrap32 = 0) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     out[0] = out[1] = 0;
     if (!w || !h) return;
     const size_t cb = align256((((size_t)h - 1) * cstride + w) * 4), rb = recon ? align256((((size_t)h - 1) * rstride + w) * 4) : 0;
@@ -447,7 +440,6 @@ LEAF_CATCH(svt_av1_block_error_hip, coeff, dqcoeff, block_size, ssz)
 template <typename Pix> static void leaf_residual(const Pix *in, uint32_t in_stride, const Pix *pred, uint32_t pred_stride, int16_t *res, uint32_t res_stride, uint32_t w, uint32_t h) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     if (!w || !h) return;
     const size_t ib = align256((((size_t)h - 1) * in_stride + w) * sizeof(Pix)), pb = align256((((size_t)h - 1) * pred_stride + w) * sizeof(Pix));
     const size_t rbytes = (((size_t)h - 1) * res_stride + w) * 2;
@@ -481,7 +473,6 @@ int svt_hip_estimate_transform(int16_t *residual, uint32_t residual_stride, int3
     try {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     const int W = svt_hip_tx_size_wide(tx_size), H = svt_hip_tx_size_high(tx_size), NP = (W > 32 ? 32 : W) * (H > 32 ? 32 : H);
     const size_t sb = align256((((size_t)H - 1) * residual_stride + W) * 2), zb = align256((size_t)W * H * 2);
     uint8_t *base = leaf_scratch(ctx, sb + zb + 256 + 256 + 256 + align256((size_t)NP * 4));
@@ -590,7 +581,6 @@ void leaf_ext_8x8_16x16(const uint8_t *src, uint32_t src_stride, const uint8_t *
                         uint32_t *mv8, uint32_t *mv16, uint32_t *sad16, uint32_t *sad8, bool sub_sad, int n16, int npos) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     const int    side = n16 == 16 ? 64 : 16, n8 = n16 * 4;
     const size_t sbytes = ((size_t)side - 1) * src_stride + side, rbytes = ((size_t)side - 1) * ref_stride + side + npos - 1;
     const size_t sb = align256(sbytes), rb = align256(rbytes);
@@ -619,7 +609,6 @@ void leaf_ext_8x8_16x16(const uint8_t *src, uint32_t src_stride, const uint8_t *
 void leaf_ext_32x32_64x64(const uint32_t *sad16, int npos, uint32_t mv, uint32_t *best32, uint32_t *best64, uint32_t *mv32, uint32_t *mv64, uint32_t *sad32) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     uint32_t *d_u = reinterpret_cast<uint32_t *>(leaf_scratch(ctx, 2048)); // sad16[128] best32[4] best64[1] mv32[4] mv64[1] sad32[32]
     leaf_check(ctx, hipMemcpyAsync(d_u, sad16, (size_t)16 * npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
     leaf_check(ctx, hipMemcpyAsync(d_u + 128, best32, 16, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
@@ -669,7 +658,6 @@ void svt_initialize_buffer_32bits_hip(uint32_t *pointer, uint32_t count128, uint
     if (!n) return;
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     uint32_t *d = reinterpret_cast<uint32_t *>(leaf_scratch(ctx, (size_t)n * 4));
     hipLaunchKernelGGL(fill_u32_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d, n, value);
     leaf_check(ctx, hipGetLastError(), "fill_u32_kernel launch");
@@ -744,7 +732,6 @@ void leaf_quantize(const int32_t *coeff, intptr_t n, const int16_t *zbin, const 
                    int fp) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     *eob = 0;
     if (n <= 0) return;
     const size_t cb = align256((size_t)n * 4), ib = align256((size_t)n * 2), mb = align256((size_t)n);
@@ -833,7 +820,6 @@ namespace {
 void leaf_inv_txfm(const int32_t *input, const uint16_t *out_r, int32_t stride_r, uint16_t *out_w, int32_t stride_w, int tx_type, int tx_size, int bd) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     if ((bd != 8 && bd != 10) || tx_size < 0 || tx_size >= SVT_HIP_TX_SIZES_ALL || tx_type < 0 || tx_type >= SVT_HIP_TX_TYPES || stride_r <= 0 || stride_w <= 0) {
         leaf_fail("svt_av1_inv_txfm2d_add_hip: unsupported bd %d / tx_size %d / tx_type %d", bd, tx_size, tx_type);
     }
@@ -892,7 +878,6 @@ namespace {
 void leaf_fwd_txfm(const int16_t *input, int32_t *output, uint32_t stride, int tx_type, int tx_size, int pf_shape) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     if (tx_type < 0 || tx_type >= SVT_HIP_TX_TYPES) leaf_fail("svt_av1_fwd_txfm2d_hip: tx_type %d", tx_type);
     const int W = svt_hip_tx_size_wide(tx_size), H = svt_hip_tx_size_high(tx_size);
     const size_t rbytes = (((size_t)H - 1) * stride + W) * 2, obytes = (size_t)W * H * 4;
@@ -954,7 +939,6 @@ __global__ void __launch_bounds__(256) handle_transform_kernel(const int32_t *in
 uint64_t leaf_handle_transform(int32_t *output, int w, int h, int with_energy) {
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     const int    wp = w > 32 ? 32 : w, hp = h > 32 ? 32 : h;
     const size_t ib = align256((size_t)w * h * 4), pb = align256((size_t)wp * hp * 4);
     uint8_t *base = leaf_scratch(ctx, ib + pb + 256);

@@ -19,7 +19,7 @@ namespace {
 SvtHipContext *g_leaf_ctx = nullptr;
 std::mutex     g_leaf_mutex; // the reference calls its kernels from many threads; these entries serialise on one stream
 // previous kernels of the slots svt_hip_install_rtcd wrote to, by this library's symbol name
-struct LeafPrev { char symbol[96]; void *prev; void **slot; };
+struct LeafPrev { char symbol[96]; void *prev; void **slot; void *entry; }; // entry: what the installer wrote to *slot
 LeafPrev   g_leaf_prev[640];
 int        g_leaf_nprev = 0;
 std::mutex g_leaf_prev_mutex;
@@ -42,6 +42,7 @@ thread_local int t_leaf_depth = 0;
 SvtHipContext *leaf_ctx() {
     if (g_leaf_inject.load()) leaf_fail("injected failure (svt_hip_leaf_inject_failure)");
     if (!g_leaf_ctx) leaf_fail("a _hip leaf kernel was called with no context bound (svt_hip_leaf_bind / svt_hip_install_rtcd)");
+    leaf_check(g_leaf_ctx, hipSetDevice(g_leaf_ctx->device), "hipSetDevice"); // what svt_hip_use_device does for the entries that return a code
     return g_leaf_ctx;
 }
 void leaf_check(SvtHipContext *, hipError_t e, const char *what) {
@@ -86,6 +87,16 @@ int svt_hip_leaf_bind(SvtHipContext *ctx) {
     g_leaf_ctx = ctx;
     return SVT_HIP_OK;
 }
+
+} // extern "C"
+
+// svt_hip_context_destroy: a context that goes away is bound no longer (the lock waits for an entry that is running on it)
+void svt_hip_leaf_unbind(SvtHipContext *ctx) {
+    std::lock_guard<std::mutex> lock(g_leaf_mutex);
+    if (g_leaf_ctx == ctx) g_leaf_ctx = nullptr;
+}
+
+extern "C" {
 
 // The `_hip` entry that takes the place of the reference's function pointer `name`: the exported symbol <name>_hip of this library
 // (the pointer-level entries carry the reference's pointer names), or the one the short alias table names where the reference's
@@ -137,6 +148,7 @@ int svt_hip_rtcd_store(const SvtHipRtcdSlot *slots, uint32_t n_slots, uint32_t *
         }
         g_leaf_prev[k].prev = prev;
         g_leaf_prev[k].slot = slots[i].slot;
+        g_leaf_prev[k].entry = const_cast<void *>(fn);
         *slots[i].slot = const_cast<void *>(fn);
     }
     if (n_skipped) *n_skipped = skipped;
@@ -155,14 +167,21 @@ int svt_hip_install_rtcd(SvtHipContext *ctx, const SvtHipRtcdSlot *slots, uint32
     return svt_hip_leaf_bind(ctx);
 }
 
-// Puts the previous kernels back into the slots svt_hip_install_rtcd / svt_hip_rtcd_store wrote to (an encoder that gives the device up).
+// Puts the previous kernels back into the slots svt_hip_install_rtcd / svt_hip_rtcd_store wrote to (an encoder that gives the device up).  A slot
+// that holds this library's entry no longer (the encoder ran its own set-up again) is left alone.  Either way the record goes: a later direct
+// call of the entry finds no previous kernel, not a pointer into code that may be gone.
 int svt_hip_uninstall_rtcd(const SvtHipRtcdSlot *slots, uint32_t n_slots) {
     if (!slots && n_slots) return SVT_HIP_ERR_BAD_PARAM;
     std::lock_guard<std::mutex> lock(g_leaf_prev_mutex);
     for (uint32_t i = 0; i < n_slots; i++) {
         if (!slots[i].slot) continue;
-        for (int k = 0; k < g_leaf_nprev; k++)
-            if (g_leaf_prev[k].slot == slots[i].slot && g_leaf_prev[k].prev) { *slots[i].slot = g_leaf_prev[k].prev; break; }
+        for (int k = 0; k < g_leaf_nprev; k++) {
+            LeafPrev &r = g_leaf_prev[k];
+            if (r.slot != slots[i].slot) continue;
+            if (r.prev && *r.slot == r.entry) *r.slot = r.prev;
+            r = g_leaf_prev[--g_leaf_nprev]; // the table keeps no order
+            break;
+        }
     }
     return SVT_HIP_OK;
 }

@@ -113,6 +113,8 @@ struct MeKernelParams {
 #define SVT_HIP_ME_HEADER_BYTES 256 /* sizeof(MeBatchHeader) rounded up: the parameter blocks follow at this offset */
 // Dense pre-pass (me_dense.inl): one slot per (global job index, searched (list, reference) pair, kind)
 #define SVT_HIP_ME_DENSE_KINDS 6   /* two pre-HME strips + 2 x 2 level-0 regions */
+#define SVT_HIP_ME_PROFILE_WORD 16  /* u32 index into a lane's queue_head block: SVT_HIP_ME_PROFILE_SUMS u64 phase sums of the profiling build (svt_hip_me_profile_read) */
+#define SVT_HIP_ME_PROFILE_SUMS 48
 #define SVT_HIP_ME_COUNTER_WORD 112 /* u32 index into a lane's queue_head block: two u64 counters (dense slots taken / not found) */
 /* The walk a unit of the pre-pass took (me_dense.inl): the static one, or the generic one and why.  Per path two u64 counters (units, (source
  * row, search row) pairs per wave), then seven more (static units of 16, 24 .. 56, 64 and more search rows), from u32 index
@@ -176,6 +178,7 @@ struct MeBatchHeader {
 };
 #ifdef __cplusplus
 static_assert(sizeof(MeBatchHeader) <= SVT_HIP_ME_HEADER_BYTES, "header size");
+static_assert(SVT_HIP_ME_PROFILE_WORD % 2 == 0 && SVT_HIP_ME_PROFILE_WORD + 2 * SVT_HIP_ME_PROFILE_SUMS <= SVT_HIP_ME_COUNTER_WORD, "profile sums");
 static_assert(SVT_HIP_ME_DENSE_PATH_WORD % 2 == 0 && SVT_HIP_ME_DENSE_PATH_WORD + 2 * SVT_HIP_ME_DENSE_PATH_COUNTERS <= SVT_HIP_ME_LIST_CURSOR(0), "path counters");
 #endif
 // A lane's parameter block (device copy and the pinned ring): header, SVT_HIP_ME_MAX_PICTURES parameter blocks, the dense entry table

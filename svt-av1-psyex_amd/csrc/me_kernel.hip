@@ -28,7 +28,7 @@
 #include "lds_dma.h"
 
 // Diagnostic build only (-DSVT_HIP_ME_PROFILE): lane 0 accumulates shader-clock deltas per phase (private array) and adds
-// them to queue_head[16 + 2*i] (u64) when the wave retires.  Never defined in the shipped library.
+// them to queue_head[SVT_HIP_ME_PROFILE_WORD + 2*i] (u64) when the wave retires.  Never defined in the shipped library.
 #ifdef SVT_HIP_ME_PROFILE
 // the sums live behind the wave's LDS slice (48 x u32, added with ds_add_u32: a profiling point costs one s_memtime and one LDS atomic)
 struct Prof { uint32_t *acc; unsigned long long last; int step; };
@@ -2663,7 +2663,7 @@ __device__ __forceinline__ void me_b64_body(const MeBatchHeader *__restrict__ gh
 #ifndef SVT_HIP_ME_PROFILE_MODE
 #define SVT_HIP_ME_PROFILE_MODE 0 /* which kernel of the chain adds its phase sums (one table per diagnostic build) */
 #endif
-    if (MODE == SVT_HIP_ME_PROFILE_MODE) PROF_FLUSH(hdr.queue_head + 16);
+    if (MODE == SVT_HIP_ME_PROFILE_MODE) PROF_FLUSH(hdr.queue_head + SVT_HIP_ME_PROFILE_WORD);
 #endif
     if ((MODE == kMeFull || MODE == kMeMid1) && has_dense && hdr.count_dense) { // counters of the context's diagnostics entry (svt_hip_me_dense_counters): uniform
         const uint32_t h = wave_sum_dpp(n_hit), m = wave_sum_dpp(n_miss);
@@ -2704,6 +2704,8 @@ size_t svt_hip_me_kernel_lds_bytes(void) {
 
 #include "svt_hip_internal.h"
 
+static_assert(SVT_HIP_ME_DENSE_PATHS == kMeDensePaths, "paths"); // the public header's count (svt_hip_me_dense_path_counters, me_switches.cpp)
+
 // Host launcher: zero the lane's band queues, copy the header + parameter blocks to HBM through one block of the lane's
 // pinned ring (stream ordered: the previous launch on this lane has consumed the device block before the copy lands; the ring
 // lets SVT_HIP_PARAM_RING launches be enqueued ahead before the host has to wait) and enqueue the persistent waves on the
@@ -2732,22 +2734,11 @@ int svt_hip_me_launch(SvtHipContext *ctx, SvtHipLane *lane, const MeKernelParams
     static thread_local MeDenseEntry entries[SVT_HIP_ME_DENSE_MAX_ENTRIES];
     uint32_t n_entries = 0, n_units = 0;
     if (ctx->me_dense) n_entries = dense_plan(params, n_jobs, n_pictures, entries, &n_units, (uint32_t)ctx->num_cus * 4u * SVT_HIP_ME_DENSE_WAVES, ctx->me_dense_plan);
-    auto grow = [&](void **buf, size_t *have, size_t need) -> int { // a lane's device buffers grow on demand (earlier launches of the lane may still read the old one)
-        if (need <= *have) return SVT_HIP_OK;
-        if (*buf) {
-            SVT_HIP_CHECK(ctx, hipStreamSynchronize(lane->stream));
-            (void)hipFree(*buf);
-            *buf = nullptr; *have = 0;
-        }
-        if (hipMalloc(buf, need) != hipSuccess) return svt_hip_fail(ctx, SVT_HIP_ERR_NO_MEMORY, "hipMalloc(%zu) failed (ME launch buffers)", need);
-        *have = need;
-        return SVT_HIP_OK;
-    };
     if (n_units) {
         const size_t need = (size_t)total * hdr.n_slot * SVT_HIP_ME_DENSE_KINDS * sizeof(MeDenseSlot);
-        if (int rc = grow(&lane->dense, &lane->dense_bytes, need)) return rc;
-        SVT_HIP_CHECK(ctx, hipMemsetAsync(lane->dense, 0xFF, need, lane->stream));
-        hdr.dense = static_cast<MeDenseSlot *>(lane->dense);
+        if (int rc = svt_hip_buffer_reserve(ctx, &lane->dense, need, lane->stream, "hipMalloc(%zu) failed (ME launch buffers)")) return rc; // earlier launches of the lane may still read the old block
+        SVT_HIP_CHECK(ctx, hipMemsetAsync(lane->dense.ptr, 0xFF, need, lane->stream));
+        hdr.dense = static_cast<MeDenseSlot *>(lane->dense.ptr);
         hdr.n_dense_entries = n_entries; hdr.n_dense_units = n_units;
         hdr.count_dense = ctx->me_counting ? 1u : 0u;
         hdr.dense_fast  = ctx->me_dense_fast ? 1u : 0u;
@@ -2759,8 +2750,8 @@ int svt_hip_me_launch(SvtHipContext *ctx, SvtHipLane *lane, const MeKernelParams
     const bool staged = n_units && (ctx->me_staged == 2 || (ctx->me_staged == 1 && total >= kStagedMinJobs));
     if (staged) {
         const size_t stage_bytes = (size_t)total * SVT_HIP_ME_STAGE_BYTES, words = (size_t)total * sizeof(uint32_t);
-        if (int rc = grow(&lane->stage, &lane->stage_bytes, stage_bytes + 2 * words)) return rc;
-        uint8_t *base = static_cast<uint8_t *>(lane->stage);
+        if (int rc = svt_hip_buffer_reserve(ctx, &lane->stage, stage_bytes + 2 * words, lane->stream, "hipMalloc(%zu) failed (ME launch buffers)")) return rc;
+        uint8_t *base = static_cast<uint8_t *>(lane->stage.ptr);
         hdr.stage     = base;
         hdr.job_flags = reinterpret_cast<uint32_t *>(base + stage_bytes);
         hdr.lists[0] = reinterpret_cast<uint32_t *>(base + stage_bytes + words); // the deferred blocks
@@ -2787,14 +2778,20 @@ int svt_hip_me_launch(SvtHipContext *ctx, SvtHipLane *lane, const MeKernelParams
     SVT_HIP_CHECK(ctx, hipEventRecord(lane->params_copied[slot], lane->stream));
     const MeBatchHeader  *d_hdr = reinterpret_cast<const MeBatchHeader *>(dev);
     const MeKernelParams *d_par = reinterpret_cast<const MeKernelParams *>(dev + SVT_HIP_ME_HEADER_BYTES);
-    // svt_hip_context_set_me_timing: an event in front of every kernel of the chain (me_mark[kernel]) and one behind the last (me_mark[9])
-    const bool timing = ctx->me_timing;
+    // svt_hip_context_set_me_timing: an event in front of every kernel of the chain (me_mark[kernel]) and one behind the last
+    // (me_mark[SVT_HIP_ME_CHAIN_KERNELS]).  The aid never fails a launch: when an event cannot be made or recorded, no bit of me_marked stays
+    // set and svt_hip_me_launch_times reports 0 for every kernel of this launch.
+    bool timing = ctx->me_timing;
     lane->me_marked = 0;
     auto mark = [&](int kernel) { // kernel < 0: the closing event
         if (!timing) return;
         const int i = kernel < 0 ? SVT_HIP_ME_CHAIN_KERNELS : kernel;
-        if (!lane->me_mark[i]) hipEventCreate(&lane->me_mark[i]);
-        hipEventRecord(lane->me_mark[i], lane->stream);
+        if ((!lane->me_mark[i] && hipEventCreate(&lane->me_mark[i]) != hipSuccess) || hipEventRecord(lane->me_mark[i], lane->stream) != hipSuccess) {
+            timing = false;
+            lane->me_marked = 0;
+            (void)hipGetLastError(); // the runtime keeps the failure for the next hipGetLastError: the launch's own check below must not see it
+            return;
+        }
         if (kernel >= 0) lane->me_marked |= 1u << kernel;
     };
     if (n_units) {
@@ -2826,129 +2823,5 @@ int svt_hip_me_launch(SvtHipContext *ctx, SvtHipLane *lane, const MeKernelParams
     }
     mark(-1);
     SVT_HIP_CHECK(ctx, hipGetLastError());
-    return SVT_HIP_OK;
-}
-
-static const char *const kChainKernelNames[SVT_HIP_ME_CHAIN_KERNELS] = {"svt_hip_me_dense_kernel", "svt_hip_me_mid1_kernel", "svt_hip_me_s1_kernel",  "svt_hip_me_mid2_kernel",
-                                                                        "svt_hip_me_s2_kernel",    "svt_hip_me_tail_kernel", "svt_hip_me_b64_kernel"};
-extern "C" const char *svt_hip_me_chain_kernel_name(int i) { return i >= 0 && i < SVT_HIP_ME_CHAIN_KERNELS ? kChainKernelNames[i] : nullptr; }
-
-extern "C" int svt_hip_context_set_me_counting(SvtHipContext *ctx, int on) {
-    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
-    ctx->me_counting = on != 0;
-    return SVT_HIP_OK;
-}
-
-extern "C" int svt_hip_context_set_me_timing(SvtHipContext *ctx, int on) {
-    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
-    ctx->me_timing = on != 0;
-    return SVT_HIP_OK;
-}
-
-// the kernels of the last launch enqueued through lane 0 (the context stream)
-extern "C" int svt_hip_me_launch_times(SvtHipContext *ctx, float ms[SVT_HIP_ME_CHAIN_KERNELS]) {
-    if (!ctx || !ms) return SVT_HIP_ERR_BAD_PARAM;
-    SvtHipLane &l = ctx->lane[0];
-    hipSetDevice(ctx->device);
-    SVT_HIP_CHECK(ctx, hipStreamSynchronize(l.stream));
-    for (int i = 0; i < SVT_HIP_ME_CHAIN_KERNELS; i++) {
-        ms[i] = 0.f;
-        if (!(l.me_marked >> i & 1u)) continue;
-        // the event behind kernel i is the next one recorded: the one in front of the next kernel that ran, or the closing event
-        int j = i + 1;
-        while (j < SVT_HIP_ME_CHAIN_KERNELS && !(l.me_marked >> j & 1u)) j++;
-        SVT_HIP_CHECK(ctx, hipEventElapsedTime(&ms[i], l.me_mark[i], l.me_mark[j]));
-    }
-    return SVT_HIP_OK;
-}
-
-extern "C" int svt_hip_context_set_me_staged(SvtHipContext *ctx, int on) {
-    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
-    if (on < 0 || on > 2) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_context_set_me_staged: %d is not 0 (off), 1 (large launches) or 2 (every launch)", on);
-    ctx->me_staged = on;
-    return SVT_HIP_OK;
-}
-
-extern "C" int svt_hip_context_set_me_dense(SvtHipContext *ctx, int on) {
-    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
-    ctx->me_dense = on != 0;
-    return SVT_HIP_OK;
-}
-
-// Diagnostics: searches the per-block kernel took from the dense pre-pass / pushed searches it found no slot for, summed over the lanes
-// since the last call (the call waits for the lanes' streams).
-extern "C" int svt_hip_me_dense_counters(SvtHipContext *ctx, unsigned long long out[2]) {
-    if (!ctx || !out) return SVT_HIP_ERR_BAD_PARAM;
-    out[0] = out[1] = 0;
-    hipSetDevice(ctx->device);
-    for (int i = 0; i < SVT_HIP_LANES; i++) {
-        SvtHipLane &l = ctx->lane[i];
-        if (!l.ready) continue;
-        unsigned long long v[2];
-        SVT_HIP_CHECK(ctx, hipStreamSynchronize(l.stream));
-        SVT_HIP_CHECK(ctx, hipMemcpy(v, l.queue_head + SVT_HIP_ME_COUNTER_WORD, sizeof(v), hipMemcpyDeviceToHost));
-        SVT_HIP_CHECK(ctx, hipMemset(l.queue_head + SVT_HIP_ME_COUNTER_WORD, 0, sizeof(v)));
-        out[0] += v[0]; out[1] += v[1];
-    }
-    return SVT_HIP_OK;
-}
-
-extern "C" int svt_hip_context_set_me_dense_fast(SvtHipContext *ctx, int on) {
-    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
-    ctx->me_dense_fast = on != 0;
-    return SVT_HIP_OK;
-}
-
-extern "C" int svt_hip_context_set_me_dense_plan(SvtHipContext *ctx, int plan) {
-    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
-    if (plan < 0 || plan > 3) return svt_hip_fail(ctx, SVT_HIP_ERR_BAD_PARAM, "svt_hip_context_set_me_dense_plan: %d is not 0 (by launch size), 1 (long units), 2 or 3 (fine units)", plan);
-    ctx->me_dense_plan = plan;
-    return SVT_HIP_OK;
-}
-
-// Diagnostics: the units of the pre-pass by the walk they took, and the (source row, search row) pairs of their waves, since the last call
-extern "C" int svt_hip_me_dense_path_counters(SvtHipContext *ctx, unsigned long long out[2 * SVT_HIP_ME_DENSE_PATHS + 7]) {
-    static_assert(SVT_HIP_ME_DENSE_PATHS == kMeDensePaths, "paths");
-    if (!ctx || !out) return SVT_HIP_ERR_BAD_PARAM;
-    memset(out, 0, SVT_HIP_ME_DENSE_PATH_COUNTERS * sizeof(out[0]));
-    hipSetDevice(ctx->device);
-    for (int i = 0; i < SVT_HIP_LANES; i++) {
-        SvtHipLane &l = ctx->lane[i];
-        if (!l.ready) continue;
-        unsigned long long v[SVT_HIP_ME_DENSE_PATH_COUNTERS];
-        SVT_HIP_CHECK(ctx, hipStreamSynchronize(l.stream));
-        SVT_HIP_CHECK(ctx, hipMemcpy(v, l.queue_head + SVT_HIP_ME_DENSE_PATH_WORD, sizeof(v), hipMemcpyDeviceToHost));
-        SVT_HIP_CHECK(ctx, hipMemset(l.queue_head + SVT_HIP_ME_DENSE_PATH_WORD, 0, sizeof(v)));
-        for (int k = 0; k < SVT_HIP_ME_DENSE_PATH_COUNTERS; k++) out[k] += v[k];
-    }
-    return SVT_HIP_OK;
-}
-
-// Diagnostics: the slot buffer of the context's most recent launch with a pre-pass (waits for that launch).  *bytes = its size; the slots are
-// copied when they fit `capacity`.
-extern "C" int svt_hip_me_dense_slots(SvtHipContext *ctx, void *out, size_t capacity, size_t *bytes) {
-    if (!ctx || !bytes) return SVT_HIP_ERR_BAD_PARAM;
-    *bytes = 0;
-    hipSetDevice(ctx->device);
-    const SvtHipLane *last = nullptr;
-    for (int i = 0; i < SVT_HIP_LANES; i++)
-        if (ctx->lane[i].ready && ctx->lane[i].dense_seq && (!last || ctx->lane[i].dense_seq > last->dense_seq)) last = &ctx->lane[i];
-    if (!last) return SVT_HIP_OK;
-    *bytes = last->dense_used;
-    if (!out || capacity < last->dense_used) return SVT_HIP_OK;
-    SVT_HIP_CHECK(ctx, hipStreamSynchronize(last->stream));
-    SVT_HIP_CHECK(ctx, hipMemcpy(out, last->dense, last->dense_used, hipMemcpyDeviceToHost));
-    return SVT_HIP_OK;
-}
-
-extern "C" int svt_hip_context_set_me_waves_per_cu(SvtHipContext *ctx, uint32_t waves) {
-    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
-    ctx->me_waves_per_cu = waves;
-    return SVT_HIP_OK;
-}
-
-extern "C" int svt_hip_context_set_me_max_waves(SvtHipContext *ctx, uint32_t waves) {
-    if (!ctx) return SVT_HIP_ERR_BAD_PARAM;
-    ctx->me_max_waves = waves;
     return SVT_HIP_OK;
 }

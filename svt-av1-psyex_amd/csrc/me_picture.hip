@@ -121,7 +121,7 @@ int svt_hip_me_pictures_on_lane(SvtHipContext *ctx, SvtHipLane *lane, uint32_t n
         p.n_pu = g.n_pu;
         n_jobs[i] = g.nrow * g.w64;
     }
-    hipSetDevice(ctx->device);
+    if (int rc = svt_hip_use_device(ctx)) return rc;
     // pictures whose planes were filled on another stream (svt_hip_pa_picture_create* enqueue on the context stream)
     for (uint32_t i = 0; i < n_pictures; i++) {
         const SvtHipMeJob &j = jobs[i];
@@ -156,7 +156,7 @@ int svt_hip_me_picture(SvtHipContext *ctx, const SvtHipMeConfig *cfg, const SvtH
     Geometry g;
     int rc = validate(ctx, cfg, desc, cur, refs, res, &g);
     if (rc) return rc;
-    hipSetDevice(ctx->device);
+    if ((rc = svt_hip_use_device(ctx))) return rc;
     // a lane of its own for the duration of the call: stream, queue counters, parameter block and result buffer are not shared
     // with calls made from other host threads (Globals/enc_handle.c:2265: several ME threads, several pictures in flight)
     SvtHipLaneGuard guard(ctx);

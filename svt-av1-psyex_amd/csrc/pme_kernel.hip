@@ -107,7 +107,6 @@ extern "C" void svt_pme_sad_loop_kernel_hip(const SvtHipMvCostParam *mp, uint8_t
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
     if (sa_w < 8 || sa_h < 1 || block_height == 0 || block_width == 0) return; // no position is visited
-    hipSetDevice(ctx->device);
     const int    st = step < 1 ? 1 : step;
     const size_t src_bytes = ((size_t)block_height - 1) * src_stride + block_width;
     // the reference's reads end with the last row of the last visited row of positions: the last group's eighth position plus the block

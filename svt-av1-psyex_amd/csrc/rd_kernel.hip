@@ -1031,6 +1031,6 @@ int svt_hip_rd_tables_init(SvtHipContext *ctx) {
 }
 
 void svt_hip_rd_tables_free(SvtHipContext *ctx) {
-    if (ctx->iscan_dev) hipFree(ctx->iscan_dev);
+    if (ctx->iscan_dev) (void)hipFree(ctx->iscan_dev); // teardown
     ctx->iscan_dev = nullptr;
 }

@@ -258,7 +258,6 @@ SsimLeafOut leaf_ssim(const void *src, uint32_t sp, const void *ref, uint32_t rp
     if (w < 4 || w > 128 || (w & 3) || h < 4 || h > 128 || (h & 3)) leaf_fail("SSIM block %dx%d: sides must be multiples of 4 in 4..128", w, h);
     std::lock_guard<std::mutex> lock(leaf_mutex());
     SvtHipContext *ctx = leaf_ctx();
-    hipSetDevice(ctx->device);
     const size_t bpp = bit_depth == 8 ? 1 : 2;
     const int    n   = (w >= 8 && h >= 8) ? 8 : 4;
     const int    sw  = psy_rd > 0.0 ? (w + n - 1) / n * n : w, sh = psy_rd > 0.0 ? (h + n - 1) / n * n : h;

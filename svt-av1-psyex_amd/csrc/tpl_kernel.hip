@@ -433,9 +433,7 @@ int svt_hip_tpl_tables_init(SvtHipContext *ctx) {
 
 void svt_hip_tpl_free(SvtHipContext *ctx) {
     svt_hip_tpl_group_free(ctx);
-    if (ctx->tpl_scratch) hipFree(ctx->tpl_scratch);
-    ctx->tpl_scratch = nullptr;
-    ctx->tpl_scratch_bytes = 0;
+    svt_hip_buffer_release(&ctx->tpl_scratch);
 }
 
 extern "C" {
@@ -500,13 +498,8 @@ int svt_hip_tpl_dispense_locked(SvtHipContext *ctx, const SvtHipTplDesc *d) {
     const int ts = ts_tab[d->dispenser_search_level][p.sub];
     p.iscan = ctx->iscan_dev + (size_t)ts * 3 * 1024;
     const int n_blk = p.nbx * p.nby;
-    const size_t bytes = sizeof(TplBlk) * (size_t)n_blk;
-    if (bytes > ctx->tpl_scratch_bytes) {
-        if (ctx->tpl_scratch) { SVT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); hipFree(ctx->tpl_scratch); ctx->tpl_scratch = nullptr; ctx->tpl_scratch_bytes = 0; }
-        if (hipMalloc(&ctx->tpl_scratch, bytes) != hipSuccess) return svt_hip_fail(ctx, SVT_HIP_ERR_NO_MEMORY, "TPL: hipMalloc(%zu) failed", bytes);
-        ctx->tpl_scratch_bytes = bytes;
-    }
-    p.blk = static_cast<TplBlk *>(ctx->tpl_scratch);
+    if (int rc = svt_hip_buffer_reserve(ctx, &ctx->tpl_scratch, sizeof(TplBlk) * (size_t)n_blk, ctx->stream, "TPL: hipMalloc(%zu) failed")) return rc;
+    p.blk = static_cast<TplBlk *>(ctx->tpl_scratch.ptr);
     switch (ts) {
     case 2: return launch_all<2>(ctx, p, n_blk);
     case 8: return launch_all<8>(ctx, p, n_blk);
@@ -524,7 +517,7 @@ int svt_hip_tpl_dispense(SvtHipContext *ctx, const SvtHipTplDesc *d) {
     int rc = svt_hip_tpl_check_desc(d);
     if (rc) return rc;
     std::lock_guard<std::mutex> g(ctx->async_mu);
-    hipSetDevice(ctx->device);
+    if ((rc = svt_hip_use_device(ctx))) return rc;
     return svt_hip_tpl_dispense_locked(ctx, d);
 }
 

@@ -219,11 +219,11 @@ bool any_outputs(const SvtHipTplGroupFrame &f) { return f.r0 || f.tpl_is_valid |
 
 } // namespace
 
-void svt_hip_tpl_group_free(SvtHipContext *ctx) {
+void svt_hip_tpl_group_free(SvtHipContext *ctx) { // teardown: nothing here can act on a failure
     for (hipEvent_t &e : ctx->tpl_group_done)
-        if (e) { hipEventSynchronize(e); hipEventDestroy(e); e = nullptr; }
-    if (ctx->tpl_group_dev) hipFree(ctx->tpl_group_dev);
-    if (ctx->tpl_group_host) hipHostFree(ctx->tpl_group_host);
+        if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); e = nullptr; }
+    if (ctx->tpl_group_dev) (void)hipFree(ctx->tpl_group_dev);
+    if (ctx->tpl_group_host) (void)hipHostFree(ctx->tpl_group_host);
     ctx->tpl_group_dev = ctx->tpl_group_host = nullptr;
 }
 
@@ -296,7 +296,7 @@ int svt_hip_tpl_group(SvtHipContext *ctx, const SvtHipTplGroupDesc *d) {
     if (rc) return rc;
     const GroupGeom g = geom_of(d);
     std::lock_guard<std::mutex> lk(ctx->async_mu);
-    hipSetDevice(ctx->device);
+    if ((rc = svt_hip_use_device(ctx))) return rc;
     if (!ctx->tpl_group_dev) {
         if (hipMalloc(&ctx->tpl_group_dev, kSlotBytes * SVT_HIP_TPL_GROUP_RING) != hipSuccess) {
             ctx->tpl_group_dev = nullptr;
@@ -304,7 +304,7 @@ int svt_hip_tpl_group(SvtHipContext *ctx, const SvtHipTplGroupDesc *d) {
         }
         if (hipHostMalloc(&ctx->tpl_group_host, kSlotBytes * SVT_HIP_TPL_GROUP_RING) != hipSuccess) {
             ctx->tpl_group_host = nullptr;
-            hipFree(ctx->tpl_group_dev);
+            (void)hipFree(ctx->tpl_group_dev); // the host allocation's failure is the one reported
             ctx->tpl_group_dev = nullptr;
             return svt_hip_fail(ctx, SVT_HIP_ERR_NO_MEMORY, "TPL group: hipHostMalloc of the frame tables failed");
         }

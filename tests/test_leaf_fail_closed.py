@@ -105,3 +105,62 @@ def test_direct_call_without_previous_kernel_reports_and_returns(installed):
     fb, un = C.c_ulonglong(0), C.c_ulonglong(0)
     L.svt_hip_leaf_status(C.byref(fb), C.byref(un), None, C.c_size_t(0))
     assert (fb.value, un.value) == (0, 1)
+
+
+def call_variance(L, fn=None):
+    """svt_aom_variance16x16_hip, directly or through a slot's value: (return value, sse)"""
+    a = np.arange(256, dtype=np.uint8)
+    sse = C.c_uint(0)
+    f = VAR(fn if fn is not None else C.cast(L.svt_aom_variance16x16_hip, C.c_void_p).value)
+    return f(a.ctypes.data, 16, a.ctypes.data, 16, C.byref(sse)), sse.value
+
+
+def leaf_counts(L):
+    fb, un = C.c_ulonglong(0), C.c_ulonglong(0)
+    L.svt_hip_leaf_status(C.byref(fb), C.byref(un), None, C.c_size_t(0))
+    return fb.value, un.value
+
+
+def test_uninstall_forgets_the_previous_kernels(installed):
+    """After svt_hip_uninstall_rtcd the records are gone: a direct call of an entry finds no previous kernel (the encoder's code may have been
+    unloaded since) and reports that, it does not jump to what the slot once held."""
+    L, slots, vals, prev, calls, _ = installed
+    assert L.svt_hip_rtcd_store(slots, len(prev), None) == 0
+    assert call_variance(L) == (55, 777) and calls == [("var", 16, 16)]  # while installed the direct call reaches the stand-in
+    leaf_counts(L)
+    assert L.svt_hip_uninstall_rtcd(slots, len(prev)) == 0
+    assert [v.value for v in vals] == prev
+    del calls[:]
+    assert call_variance(L) == (0, 0)
+    assert calls == [] and leaf_counts(L) == (0, 1)
+
+
+def test_uninstall_leaves_a_slot_that_was_overwritten(installed):
+    """A slot that no longer holds this library's entry (the encoder ran its own set-up again) keeps what it holds."""
+    L, slots, vals, prev, calls, _ = installed
+    assert L.svt_hip_rtcd_store(slots, len(prev), None) == 0
+    vals[1].value = 0x5678  # a foreign pointer, between store and uninstall
+    assert L.svt_hip_uninstall_rtcd(slots, len(prev)) == 0
+    assert vals[1].value == 0x5678
+    assert [v.value for i, v in enumerate(vals) if i != 1] == [p for i, p in enumerate(prev) if i != 1]  # the others went back
+    assert call_variance(L) == (0, 0) and calls == [] and leaf_counts(L) == (0, 1)  # and its record is gone with the others
+
+
+def test_store_after_uninstall_records_the_new_kernels(installed):
+    L, slots, vals, prev, calls, _ = installed
+    assert L.svt_hip_rtcd_store(slots, len(prev), None) == 0
+    assert L.svt_hip_uninstall_rtcd(slots, len(prev)) == 0
+    other = []
+
+    def var2(src, ss, ref, rs, sse):
+        other.append((ss, rs))
+        sse[0] = 9
+        return 8
+
+    keep2 = VAR(var2)
+    vals[1].value = C.cast(keep2, C.c_void_p).value
+    assert L.svt_hip_rtcd_store(slots, len(prev), None) == 0
+    assert call_variance(L, vals[1].value) == (8, 9)
+    assert other == [(16, 16)] and calls == [] and leaf_counts(L) == (1, 0)
+    assert L.svt_hip_uninstall_rtcd(slots, len(prev)) == 0
+    assert vals[1].value == C.cast(keep2, C.c_void_p).value

@@ -11,7 +11,7 @@ import me_tpl_cases as mt
 import tpl_group_cases as gc
 from me_cases import compare, fill_unsearched
 from svt_av1_psyex_amd import abi, api, tpl
-from test_tpl_dispenser_gpu import assert_same
+from tpl_dispenser_cases import assert_same
 from test_tpl_group_gpu import assert_group, from_fixture
 
 pytestmark = pytest.mark.gpu

@@ -10,7 +10,7 @@ import pytest
 
 from svt_av1_psyex_amd import api, tpl
 from test_tpl_dispenser_edges import FIXTURE_NAMES, NAMES, assert_equals_fixture, edge_fixture, restated
-from test_tpl_dispenser_gpu import assert_same
+from tpl_dispenser_cases import assert_same
 from tpl_dispenser_cases import PAD, exact_cells, restate
 
 pytestmark = pytest.mark.gpu

@@ -6,25 +6,9 @@ import numpy as np
 import pytest
 
 from svt_av1_psyex_amd import api, tpl
-from tpl_dispenser_cases import PAD, make_case, restate, seeded_grid, src_pass0_case
+from tpl_dispenser_cases import PAD, assert_same, make_case, restate, seeded_grid, src_pass0_case
 
 pytestmark = pytest.mark.gpu
-FIELDS_S = ("srcrf_dist", "recrf_dist", "srcrf_rate", "recrf_rate", "mc_dep_rate", "mc_dep_dist", "mv_row", "mv_col", "ref_frame_poc")
-FIELDS_SRC = ("srcrf_dist", "srcrf_rate", "ref_frame_poc", "mv_row", "mv_col", "best_mode", "best_rf_idx", "best_intra_mode")
-
-
-def assert_same(case, got, want, what=""):
-    (g_grid, g_src, g_rec), (w_grid, w_src, w_rec) = got, want
-    bad = np.argwhere(g_rec != w_rec)
-    assert not len(bad), f"{what}: recon differs at {len(bad)} samples, first (row, col) {tuple(bad[0])}"
-    untouched = (w_grid.view(np.uint8).reshape(len(w_grid), -1) == 0xA5).all(1)
-    assert ((g_grid.view(np.uint8).reshape(len(g_grid), -1) == 0xA5).all(1) == untouched).all(), f"{what}: written cells differ"
-    for k in FIELDS_S:
-        np.testing.assert_array_equal(g_grid[k][~untouched], w_grid[k][~untouched], err_msg=f"{what}: tpl_stats.{k}")
-    if case["src_pass"] and case["store_src_stats"]:
-        for k in FIELDS_SRC:
-            np.testing.assert_array_equal(g_src[k], w_src[k], err_msg=f"{what}: tpl_src_stats.{k}")
-
 
 @pytest.mark.parametrize("name,kw", seeded_grid())
 def test_dispense_vs_restatement(hip_ctx, name, kw):

@@ -428,6 +428,24 @@ def src_pass0_case(seed=60, **kw):
     return c2
 
 
+FIELDS_S = ("srcrf_dist", "recrf_dist", "srcrf_rate", "recrf_rate", "mc_dep_rate", "mc_dep_dist", "mv_row", "mv_col", "ref_frame_poc")
+FIELDS_SRC = ("srcrf_dist", "srcrf_rate", "ref_frame_poc", "mv_row", "mv_col", "best_mode", "best_rf_idx", "best_intra_mode")
+
+
+def assert_same(case, got, want, what=""):
+    """(tpl_stats grid, tpl_src_stats, padded recon) of a dispense against the expected triple, bit for bit; cells the dispense leaves alone keep 0xA5"""
+    (g_grid, g_src, g_rec), (w_grid, w_src, w_rec) = got, want
+    bad = np.argwhere(g_rec != w_rec)
+    assert not len(bad), f"{what}: recon differs at {len(bad)} samples, first (row, col) {tuple(bad[0])}"
+    untouched = (w_grid.view(np.uint8).reshape(len(w_grid), -1) == 0xA5).all(1)
+    assert ((g_grid.view(np.uint8).reshape(len(g_grid), -1) == 0xA5).all(1) == untouched).all(), f"{what}: written cells differ"
+    for k in FIELDS_S:
+        np.testing.assert_array_equal(g_grid[k][~untouched], w_grid[k][~untouched], err_msg=f"{what}: tpl_stats.{k}")
+    if case["src_pass"] and case["store_src_stats"]:
+        for k in FIELDS_SRC:
+            np.testing.assert_array_equal(g_src[k], w_src[k], err_msg=f"{what}: tpl_src_stats.{k}")
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # The reference fixture (tools/gen_tpl_golden.py): the cases it was made from and the checksum that pins their inputs
 import hashlib  # noqa: E402
