@@ -1,5 +1,5 @@
 // batch_host.h -- the host side that the asynchronous batch entries share: the enqueue sequence of a batch entry (the
-// nine files of inter, intra, CfL, warp, masked compound / inter-intra, OBMC, the interpolation-filter search, palette and global motion;
+// ten files of inter, intra, CfL, warp, masked compound / inter-intra, OBMC, the interpolation-filter search, palette, global motion and CDEF;
 // RD and the transforms alone, the MD searches, PME, statistics, SSIM, rate, RDOQ), and for the first eight the refusal
 // macro of their *_check_desc functions, the validation of an SvtHipInterPredRef array and the lookup behind every
 // *_layout entry.  A new batch entry supplies a check, a count and a launch; the order of the steps is here.
